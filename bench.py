@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
-"""bench.py -- users/sec evaluated (all metrics, K=10) on N MI355X, next to the CPU reference on the host cores.
+"""bench.py -- users/sec evaluated (all metrics, K=10) on N MI355X (--full: next to the CPU reference on the host cores).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|NS|C1|...] [--users M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|NS|C1|...] [--users M] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (rm_calc_metrics_dev_f32: plan + pack + positives + sweep + finalize, all ten
 metrics) over one batch of synthetic users whose inputs are already resident in HBM.  N > 1 (launched by
 torch.distributed.run, one rank per GPU): users are sharded, every rank holds a replica of the item factors and
 evaluates its own shard of the same size (weak scaling); the only exchange is one RCCL all-gather of the per-user
 metric block per step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (plus the outputs of the last timed step with
+--dump-outputs).  --full adds everything else: the parity checks against the reference, the host-pointer and Python-API
+legs, the noise-on pass, the north-star / tutorial / no-AUC / other-config legs, the CPU baseline and, with N > 1, the
+sharded-library leg.
 """
 import argparse
 import json
@@ -45,6 +50,12 @@ def parse():
     ap.add_argument("--e2e-only", action="store_true", help=argparse.SUPPRESS)       # internal: the child measures the host-pointer call alone (the large shapes)
     ap.add_argument("--sharded-child", type=int, default=0, help=argparse.SUPPRESS)  # internal: rm_set_devices([0..N-1]) against the unsharded call
     ap.add_argument("--no-other", action="store_true", help="skip the compact legs over the other BASELINE configs (C3, C4, C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beyond the headline (parity checks, host-pointer / API legs, noise-on, the other shapes and configs, "
+                         "CPU baseline, sharded-library leg); the --no-* switches and --parity-users / --cpu-seconds select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the metric arrays of the last timed step as DIR/<metric>.npy (at most 64 MB in all: "
+                         "beyond that a fixed, seeded sample of the users, listed in DIR/sampled_users.npy)")
     return ap.parse_args()
 
 
@@ -282,6 +293,28 @@ def default_build_check(prob, out, n_users, binding, cpu_seconds=10.0):
 def torch_index(out, users):
     import torch
     return torch.from_numpy(users.astype(np.int64)).to(out.device)
+
+
+# calc_reco_metrics' keywords for the ten outputs, in the C-ABI order (_binding.METRIC_ORDER)
+DUMP_NAMES = ("precision", "trunc_precision", "recall", "average_precision", "trunc_average_precision", "ndcg", "hit", "rr",
+              "roc_auc", "pr_auc")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, blocks, seed=0):
+    """--dump-outputs: the ten metric arrays of the last timed step (host arrays, [m] or [m, K], one row per user) as
+    path/<name>.npy in their own precision.  Beyond DUMP_LIMIT_BYTES in all, the rows of a fixed, seeded sample of the users
+    are written, and the sample itself as path/sampled_users.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    m = blocks[0].shape[0]
+    total = sum(int(b.nbytes) for b in blocks)
+    if total > DUMP_LIMIT_BYTES:
+        keep = int(DUMP_LIMIT_BYTES // (total / m + 8.0))
+        users = np.sort(np.random.default_rng(seed).choice(m, size=keep, replace=False))
+        np.save(os.path.join(path, "sampled_users.npy"), users.astype(np.float64))
+        blocks = [b[users] for b in blocks]
+    for name, b in zip(DUMP_NAMES, blocks):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(b))
 
 
 def e2e_host_measure(binding, host, k, K, dtype, reps=5, cumulative=False):
@@ -524,6 +557,7 @@ def measure(torch, dist, binding, prob, steps, warmup, world, gather_buf):
         if last != 0:
             prob.out.copy_(outs[last])                      # parity_check reads prob.out
     measure.last_sweep_ms = [float(x) for x in sweep_ms]      # per-step launch durations of the run just timed (the compact legs quote them)
+    measure.last_gather = gbufs[(count[0] - 1) % len(gbufs)] if world > 1 else None      # N > 1: every rank's block of the last step
     return dt, float(np.mean(sweep_ms)), float(np.mean(prep_ms)), float(np.mean(fin_ms)), binding.timings()
 
 
@@ -542,7 +576,7 @@ def main():
     # mapped) the same child measured 0.5-0.8 ms more per call than alone (profiles/r5_host_entry.txt against the round's first bench
     # lines) -- two processes' hardware queues are time-sliced.  A wrapper's process is alone on its GPU; so is the child here.
     early = {}
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_e2e:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_e2e:
         from recometrics_amd.synth import CONFIGS as _CFG
         m0 = _CFG[args.workload][0] // (8 if args.workload == "C3" else 1)
         if args.users:
@@ -637,6 +671,15 @@ def main():
     dname = "f32" if dtype == np.float32 else "f64"
 
     dt, sweep_ms, prep_ms, fin_ms, tm = measure(torch, dist, binding, prob, args.steps, args.warmup, world, gather_buf)
+    if rank == 0 and args.dump_outputs:
+        if world == 1:
+            blocks = [prob.metric(prob.out, i).cpu().numpy() for i in range(10)]
+        else:                                                # what the caller holds after the all-gather: every rank's users, padding dropped
+            from recometrics_amd.sharding import user_range
+            g = measure.last_gather.view(world, 10, m_cap)
+            counts = [m] * world if args.scaling == "weak" else [hi - lo for lo, hi in (user_range(m_total, world, r) for r in range(world))]
+            blocks = [torch.cat([g[r, i, :counts[r]] for r in range(world)]).cpu().numpy() for i in range(10)]
+        dump_outputs(args.dump_outputs, blocks)
     users_done = (world * m) if args.scaling == "weak" else m_total
     users_per_s = users_done * args.steps / dt
     # 2*n*k per user x users of one launch (`share` = the slots the timed launch covers: all of them).
@@ -668,7 +711,7 @@ def main():
     }
 
     failed = False
-    if rank == 0 and args.parity_users > 0:
+    if args.full and rank == 0 and args.parity_users > 0:
         try:
             pc = parity_check(prob, prob.out, args.parity_users, binding=binding)
         except Exception as e:      # noqa: BLE001
@@ -683,12 +726,12 @@ def main():
             except Exception as e:      # noqa: BLE001
                 line["parity_vs_default_build"] = {"ok": False, "what": repr(e)}
                 failed = True
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         child = early.get("main", {"error": "not run"})
         line["e2e_host"] = child.get("e2e_host", child)
         line["api_default"] = child.get("api_default", {"error": "no result"})
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         # the API's default, break_ties_with_noise=True (exact mt19937 noise: a second pass over the users it can touch);
         # `value` above is with the noise off, as the config string says
         try:
@@ -712,7 +755,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             line["noise_on"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_extra and args.workload != "NS":
+    if args.full and rank == 0 and world == 1 and not args.no_extra and args.workload != "NS":
         # the north-star shape (n = 1M items, 128 factors): B = 512 MB does not fit the Infinity Cache
         try:
             m2, n2, k2, _, K2, c2, s2 = CONFIGS["NS"]
@@ -748,7 +791,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             line["north_star_shape"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_extra and args.workload != "TUT":
+    if args.full and rank == 0 and world == 1 and not args.no_extra and args.workload != "TUT":
         # the only realistic workload the reference documents (examples/recometrics_example.ipynb cells 3, 5, 9, 11; BASELINE.md
         # section 1): 10,000 users x 160,112 items x 50 factors, k = 5, all metrics, API defaults -- tie noise ON.  The small-m
         # regime (79 user blocks for 256 CUs: the grid is filled by item ranges) and a factor count that is not a multiple of 8
@@ -787,7 +830,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             line["tutorial"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_extra and not args.no_other:
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.no_other:
         # The requests WITHOUT ROC / PR-AUC (the k_sweep<..., AUC = false, ...> family): the API's literal default -- precision,
         # average_precision, ndcg, tie noise on (recometrics/__init__.py:50-62) -- at BASELINE C2's shape (k = 10) and at the
         # tutorial's (k = 5), and BASELINE.md section 2's "NS, no AUC" row (the eight top-K metrics at the north-star shape).
@@ -819,7 +862,7 @@ def main():
                 noauc[lname] = {"error": repr(e)}
         line["no_auc"] = noauc
 
-    if rank == 0 and world == 1 and not args.no_extra and not args.no_other:
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.no_other:
         # every other BASELINE config in the same driver-run line, as compact legs: 3 timed steps after 1 warm-up, the sweep's
         # fraction of the MFMA peak, and a parity sample against the compiled reference bounded to ~5 s of CPU work each
         others = {}
@@ -870,9 +913,10 @@ def main():
         line["other_configs"] = others
 
     if world > 1:
+        line["multi_gpu_self_check"] = self_check
+    if world > 1 and args.full:
         # the first real multi-GPU run checks itself: the same workload through rm_set_devices([0 .. N-1]) in ONE (torch-free)
         # process must equal the unsharded call bit for bit -- two distinct devices, peer copies of the item factors over xGMI
-        line["multi_gpu_self_check"] = self_check
         # (every device idle first; the other ranks then wait for the leg on the process group's store -- a host-side wait -- and
         # not inside a collective, whose kernel would spin on the very devices the child is about to use)
         torch.cuda.synchronize()
@@ -904,7 +948,7 @@ def main():
                 pass
         dist.barrier()
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             line["cpu_baseline"] = cpu_baseline(prob.host, K, m, args.cpu_seconds, dtype)
         except Exception as e:      # noqa: BLE001

@@ -1,10 +1,10 @@
 #!/bin/bash
 # end-of-round measurements (GPU box, repo root): bash scratch/profile_round.sh r3
 RND=${1:-r3}; O=gpurun_out/${RND}_round; mkdir -p $O
-python bench.py > $O/${RND}_bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/${RND}_bench_default.json 2> $O/bench_default.err
 for w in NS C3 C4 C5; do
   extra=""; [ $w = C3 ] && extra="--users 125000"; [ $w = C4 ] && extra="--users 16384"; [ $w = C5 ] && extra="--users 50000"
-  python bench.py --workload $w $extra --no-extra --no-e2e --cpu-seconds 6 > $O/${RND}_bench_$w.json 2> $O/bench_$w.err
+  python bench.py --full --workload $w $extra --no-extra --no-e2e --cpu-seconds 6 > $O/${RND}_bench_$w.json 2> $O/bench_$w.err
 done
 bash scratch/profile_stats.sh $RND > /dev/null 2>&1
 cp gpurun_out/${RND}_stats/${RND}_bench_*_kernel_stats.csv $O/ 2>/dev/null

@@ -260,7 +260,7 @@ def test_bench_with_two_ranks(hip, scaling):
     import json
     env = dict(os.environ, RM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--users", "6001",
-                          "--no-cpu", "--no-extra", "--scaling", scaling], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--no-cpu", "--no-extra", "--scaling", scaling], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
