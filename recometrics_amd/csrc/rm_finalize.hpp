@@ -612,13 +612,6 @@ template <> struct CollectKey<double> { typedef unsigned long long T; };
 // user is a chain of round trips to memory, more of them in flight is what helps: 1.43 -> 1.04 ms at BASELINE C2's shape with K = 21, 1.78 -> 1.43 with 100)
 inline int collect_capw(int K, int lane_cap) { return K <= 128 ? 512 : (K + lane_cap <= 1024 && 2 * K <= 1024 ? 1024 : 4096); }
 constexpr int COLLECT_MAX_ENTRIES = 4096;
-
-#ifdef RM_CSTATS
-__device__ unsigned long long g_cstats[16];                    // timing build: cycle counters of k_collect_topk's phases, summed over the wavefronts
-#define RM_CSTAT(IDX, T0) do { const unsigned long long t_now = __builtin_readcyclecounter(); if (lane == 0) atomicAdd(&g_cstats[IDX], t_now - (T0)); (T0) = t_now; } while (0)
-#else
-#define RM_CSTAT(IDX, T0) do { } while (0)
-#endif
 inline unsigned collect_grid(long long blocks) { return (unsigned)((blocks + 7) / 8 * 8); }
 template <class T, class S, class ThrT, int CAPW>
 __global__ __launch_bounds__(CAPW <= 1024 ? 256 : 64) void k_collect_topk(FinalArgs<T, S> a, CollectGeom g, const char *glists, const int *lane_cnt, const ThrT *thr_shared)
@@ -636,18 +629,11 @@ __global__ __launch_bounds__(CAPW <= 1024 ? 256 : 64) void k_collect_topk(FinalA
     const int lblock = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     const int slot = lblock * WPB + wv_in_blk;
     if (slot >= a.n_slots) return;
-#ifdef RM_CSTATS
-    unsigned long long ct = __builtin_readcyclecounter();
-#endif
     // (what a wavefront does per user is a chain of round trips to memory: the loads that depend on the slot alone go out together)
     const int chunk = a.slot_chunk[slot], u = a.slot_user[slot];
     const ThrT bound_raw = thr_shared[slot];
     // (no early exit for the few slots that are not a user's first: an exit here is a wait for `chunk` in front of every other load)
     const bool live = chunk == 0;
-#ifdef RM_CSTATS
-    asm volatile("" :: "s"(chunk), "s"(u));
-    RM_CSTAT(0, ct);
-#endif
     KeyT *kh = kh_all + wv_in_blk * CAPW;
     unsigned *kl = kl_all + wv_in_blk * CAPW;
     const int K = a.K;
@@ -821,30 +807,18 @@ __global__ __launch_bounds__(CAPW <= 1024 ? 256 : 64) void k_collect_topk(FinalA
         #pragma unroll
         for (int j = 0; j < G; j++) { cn[j] = (live && on[j]) ? c[j] : 0; cmax = cn[j] > cmax ? cn[j] : cmax; }
     };
-#ifndef RM_ABL_COLLECT_NO_GATHER
     describe(0);                                                    // (the first sources' counts are on their way while the user's own test items come in)
-#endif
-#ifndef RM_ABL_COLLECT_NO_EXTRA
     if (g.extra_part >= 0) {
         const Entry<S> *px = a.pl + ((size_t)slot * a.n_part + g.extra_part) * K;
         gather(live ? K : 0, [&](int i, KeyT &key, unsigned &low) {
             Entry<S> e;                                             // (score and item in one load: the item alone first was a round trip more)
             __builtin_memcpy(&e, px + i, sizeof(e));
-#ifdef RM_ABL_COLLECT_EXTRA_DISCARD
-            if (e.idx != -77) return false;
-#endif
             if (e.idx == IDX_EMPTY) return false;
             key = ord_key(e.s); low = ~(unsigned)e.idx;
             return true;
         });
     }
-#endif
-    RM_CSTAT(1, ct);
-#ifdef RM_ABL_COLLECT_NO_GATHER
-    for (int s0 = 0; s0 < 0; s0 += G) {
-#else
     for (int s0 = 0; s0 < nsrc; s0 += G) {
-#endif
         if (s0) describe(s0);
         // (measured and dropped: two chunks of each source per batch, eight loads in flight -- the room they need in LDS brings the
         // selection in the middle of the gather forward, 1.9 -> 2.6 ms at BASELINE C2's shape with k_metrics = 100)
@@ -876,16 +850,9 @@ __global__ __launch_bounds__(CAPW <= 1024 ? 256 : 64) void k_collect_topk(FinalA
         }
     }
     wave_sync();
-    RM_CSTAT(2, ct);
-#ifndef RM_ABL_COLLECT_GATHER_ONLY                             // (timing only, scratch/build_abl.py: what the gather alone costs)
     select_best();
     sort_kept();
-#endif
-    RM_CSTAT(3, ct);
     if (!live) return;
-#ifdef RM_ABL_COLLECT_NO_WRITE
-    if (cur != 12345) return;
-#endif
     Entry<S> *M = a.merged + (size_t)u * K;
     for (int i = lane; i < K; i += WAVE) {
         Entry<S> e;
@@ -893,11 +860,6 @@ __global__ __launch_bounds__(CAPW <= 1024 ? 256 : 64) void k_collect_topk(FinalA
         else { e.s = (S)qnan<float>(); e.idx = -1; }
         M[i] = e;
     }
-#ifdef RM_CSTATS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RM_CSTAT(4, ct);
-    if (lane == 0) atomicAdd(&g_cstats[5], 1ull);
-#endif
 }
 
 template <class T, class S>
@@ -1091,9 +1053,6 @@ __global__ void k_finalize(FinalArgs<T, S> a)
         for (int i = 0; i < W; i++) { const S x = M[i].s; zone |= (x < (S)0 ? -x : x) < (S)6.103515625e-05f; }
         if (zone && atomicExch(&a.noise_flag[u], 1) == 0) atomicAdd(&a.plan->n_noise_flagged, 1);
     }
-#if defined(RM_ABL_FIN_STOP) && RM_ABL_FIN_STOP == 1
-    return;
-#endif
 
     const int *ti = a.test_i + te0;
     const T *tv = a.test_v ? a.test_v + te0 : nullptr;
@@ -1149,9 +1108,6 @@ __global__ void k_finalize(FinalArgs<T, S> a)
         }
     }
 
-#if defined(RM_ABL_FIN_STOP) && RM_ABL_FIN_STOP == 2
-    return;
-#endif
     // ---- NaN overrides (:750-788) ----
     if (kleqn) {
         if (!cum) {
@@ -1185,9 +1141,6 @@ __global__ void k_finalize(FinalArgs<T, S> a)
         } else finalize_auc(a, u, base, npos, C);
     }
 
-#if defined(RM_ABL_FIN_STOP) && RM_ABL_FIN_STOP == 3
-    return;
-#endif
     // ---- NDCG normalisation (:868-961) ----
     if (a.ndcg) {
         const int L = K < npos ? K : npos;

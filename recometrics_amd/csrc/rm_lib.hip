@@ -49,41 +49,32 @@ struct RmError { int code; std::string msg; };
 // ---- switches of tests and A/B timing ----------------------------------------------------------------------------------
 // The environment is read ONCE, when the library is loaded (and again only when a test asks: rm_debug_reload_switches), never on
 // the path of a call.  Every switch chooses among code paths that produce the same results (DESIGN.md section 7 lists them;
-// tests/test_switches_cpu.py compares this table with that list); nothing here turns a feature of the call off -- the timing
-// builds that drop the tie noise are compiled with -DRM_ABL_NOISE_OFF=1 (scratch/build_abl.py), not switched at run time.
-#ifndef RM_ABL_NOISE_OFF
-#define RM_ABL_NOISE_OFF 0
-#endif
+// tests/test_switches_cpu.py compares this table with that list); nothing here turns a feature of the call off.
 struct Switches {
-    bool no_train_bits, no_spec, no_side, ext_topk, no_early_bits, no_test_mask, hbm_lists, nsub2, no_pending, no_pos_keys, no_pos_beside,
-         no_seed, no_depth_split, rank_generic, no_fused_auc, no_defer_auc, noise_sequential, no_ext_bits, one_context, noise_per_batch,
-         host_trace, no_noise_beside_last, no_pack_beside, no_pos_flat;
-    long long free_mb, stream_budget_mb, dense_always_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed, split_slack;      // -1 = not set
+    bool no_train_bits, no_spec, no_side, ext_topk, no_test_mask, hbm_lists, nsub2, no_pending, no_pos_beside, no_seed, rank_generic,
+         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat;
+    long long free_mb, stream_budget_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed;      // -1 = not set
     double batch_users;                                                        // 0 = not set
-    int ramp;                                                                  // 0 = not set
     std::string splits;
     static bool on(const char *name) { return getenv(name) != nullptr; }
     static long long num(const char *name) { const char *e = getenv(name); return e ? atoll(e) : -1; }
     void load()
     {
         no_train_bits = on("RM_DEBUG_NO_TRAIN_BITS"); no_spec = on("RM_DEBUG_NO_SPEC"); no_side = on("RM_DEBUG_NO_SIDE");
-        ext_topk = on("RM_DEBUG_EXT_TOPK"); no_early_bits = on("RM_DEBUG_NO_EARLY_BITS"); no_test_mask = on("RM_DEBUG_NO_TEST_MASK");
+        ext_topk = on("RM_DEBUG_EXT_TOPK"); no_test_mask = on("RM_DEBUG_NO_TEST_MASK");
         hbm_lists = on("RM_DEBUG_HBM_LISTS"); nsub2 = on("RM_DEBUG_NSUB2"); no_pending = on("RM_DEBUG_NO_PENDING");
-        no_pos_keys = on("RM_DEBUG_NO_POS_KEYS"); no_pos_beside = on("RM_DEBUG_NO_POS_BESIDE"); no_seed = on("RM_DEBUG_NO_SEED");
-        no_depth_split = on("RM_DEBUG_NO_DEPTH_SPLIT"); rank_generic = on("RM_DEBUG_RANK_GENERIC"); no_fused_auc = on("RM_DEBUG_NO_FUSED_AUC");
-        no_defer_auc = on("RM_DEBUG_NO_DEFER_AUC"); noise_sequential = on("RM_DEBUG_NOISE_SEQUENTIAL"); no_ext_bits = on("RM_DEBUG_NO_EXT_BITS");
+        no_pos_beside = on("RM_DEBUG_NO_POS_BESIDE"); no_seed = on("RM_DEBUG_NO_SEED");
+        rank_generic = on("RM_DEBUG_RANK_GENERIC"); no_fused_auc = on("RM_DEBUG_NO_FUSED_AUC");
+        no_defer_auc = on("RM_DEBUG_NO_DEFER_AUC"); noise_sequential = on("RM_DEBUG_NOISE_SEQUENTIAL");
         one_context = on("RM_DEBUG_ONE_CONTEXT"); noise_per_batch = on("RM_DEBUG_NOISE_PER_BATCH"); host_trace = on("RM_HOST_TRACE");
-        no_noise_beside_last = on("RM_DEBUG_NO_NOISE_BESIDE_LAST"); no_pack_beside = on("RM_DEBUG_NO_PACK_BESIDE");
         no_pos_flat = on("RM_DEBUG_NO_POS_FLAT");
-        free_mb = num("RM_DEBUG_FREE_MB"); stream_budget_mb = num("RM_STREAM_BUDGET_MB"); dense_always_mb = num("RM_DEBUG_DENSE_ALWAYS_MB");
+        free_mb = num("RM_DEBUG_FREE_MB"); stream_budget_mb = num("RM_STREAM_BUDGET_MB");
         noise_budget_mb = num("RM_NOISE_BUDGET_MB");
         lane_min_k = num("RM_DEBUG_LANE_MIN_K");                // the smallest k_metrics that takes the lane buffers instead of LDS / HBM lists (A/B timing)
         lane_cap_set = num("RM_DEBUG_LANE_CAP");                // entries per lane buffer (A/B timing; rounded to 16, never below what a selection needs)
         sample_seed = num("RM_DEBUG_SAMPLE_SEED");            // items of the sample that seeds the lane buffers' bounds: 0 = none, else forced to 64 / 256 / 1024 / 2048 / 4096 (A/B timing, tests)
-        split_slack = num("RM_DEBUG_SPLIT_SLACK");            // percent of a round charged to the part that ends the sweep's grid (A/B timing)
         lane_cap_min = num("RM_DEBUG_LANE_CAP_MIN");          // the smallest lane buffers that work: a selection every few tiles (tests)
         const char *b = getenv("RM_BATCH_USERS"); batch_users = b ? atof(b) : 0.0;
-        const char *r = getenv("RM_DEBUG_RAMP"); ramp = r ? atoi(r) : 0;
         const char *s = getenv("RM_DEBUG_SPLITS"); splits = s ? s : "";
     }
     Switches() { load(); }
@@ -301,7 +292,6 @@ template <> struct Prec<float> {
     static constexpr int pend_cap_max = 8;                // keys per lane: measured flat from 3 to 8 at C2, best at 6-8
     static constexpr int max_nsub = 3;
     static size_t lists_b(int, int K) { return (size_t)GROUPS_PER_BLOCK * (K + 2) * GU * 8; }      // one list per group, shared by its waves
-    static constexpr bool block_carve = true;
     static void set_pending(SweepArgs &sa, int cap, int off) { sa.pend_cap = cap; sa.pend_off = off; }
     static void set_sync(SweepArgs &sa, int off) { sa.sync_off = off; }
     static void set_ublocks(SweepArgs &sa, int first, int count) { sa.ublock0 = first; sa.n_ublocks = count; }
@@ -323,7 +313,6 @@ template <> struct Prec<double> {
     static constexpr int pend_cap_max = 3;                // a user spans four lanes here: larger buffers only delay the bound (measured)
     static constexpr int max_nsub = 2;
     static size_t lists_b(int ns, int K) { return 4ull * ns * K * GU * sizeof(ListT); }               // one list per wave
-    static constexpr bool block_carve = true;
     static void set_pending(Sweep64Args &sa, int cap, int off) { sa.pend_cap = cap; sa.pend_off = off; }
     static void set_sync(Sweep64Args &sa, int off) { sa.sync_off = off; }
     static void set_ublocks(Sweep64Args &sa, int first, int count) { sa.ublock0 = first; sa.n_ublocks = count; }
@@ -441,9 +430,7 @@ inline bool dense_rows_fit(const Workspace &ws, int m, long long n)
     const long long words = dense_row_words(n);
     if (words > TRAIN_BITS_MAX_WORDS || g_sw.no_train_bits) return false;
     const unsigned long long bytes = (unsigned long long)m * (unsigned long long)words * 4ull;
-    unsigned long long always = 1ull << 30;
-    if (g_sw.dense_always_mb >= 0) always = (unsigned long long)g_sw.dense_always_mb << 20;      // (tests: the branch below at small sizes)
-    if (bytes <= always) return true;
+    if (bytes <= (1ull << 30)) return true;
     if (bytes > (8ull << 30)) return false;
     return (long long)bytes <= free_plus_owned(ws, {"train_bits", "stream_scores", "sel_hi", "sel_lo"}) / 4;
 }
@@ -588,287 +575,70 @@ void check_csr_now(const Call<T> &c, hipStream_t stream, Ctx &cx)
 // ---------------------------------------------------------------------------------------------------------------------
 // device pipeline (T = float: v_mfma_f32_32x32x2_f32 sweep; T = double: v_mfma_f64_16x16x4_f64 sweep)
 // ---------------------------------------------------------------------------------------------------------------------
-template <class T>
-void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
+// A stream of the context beside the call's (the side stream, the positives' stream), created on first use with its events.
+// `pending` counts the pieces of work forked onto it that the call's stream has not been told to wait for yet: an error between
+// a fork and its join must not leave the stream reading the call's buffers behind the caller's back, so the destructor waits.
+struct Beside {
+    hipStream_t &st; hipEvent_t *ev; int n_ev; bool high_priority; int pending = 0;
+    Beside(hipStream_t &s, hipEvent_t *e, int n, bool hp) : st(s), ev(e), n_ev(n), high_priority(hp) {}
+    ~Beside() { if (pending > 0 && st) (void)hipStreamSynchronize(st); }
+    hipStream_t get()
+    {
+        if (!st) {
+            HIP_CHECK(create_stream(&st, high_priority));
+            for (int i = 0; i < n_ev; i++) HIP_CHECK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+        }
+        return st;
+    }
+    hipStream_t fork(hipStream_t from) { hipStream_t s = get(); HIP_CHECK(hipEventRecord(ev[0], from)); HIP_CHECK(hipStreamWaitEvent(s, ev[0], 0)); pending++; return s; }
+    void join(hipStream_t into) { HIP_CHECK(hipEventRecord(ev[1], st)); HIP_CHECK(hipStreamWaitEvent(into, ev[1], 0)); pending = 0; }
+};
+
+// LDS of a sweep block of depth j (each group's positives table is aligned to its own size, 2^j rows of GU scores: worst-case
+// padding = one table)
+template <class T> inline size_t sweep_lds(int NG, int K, bool want_auc, bool with_lists, int ns, int j)
 {
     typedef Prec<T> P;
-    constexpr int GU = P::GU;
-    Workspace &ws = cx.ws;
-    double *g_timings = cx.timings;
-    hipEvent_t *g_ev = cx.ev;
-    const int m = c.m, n = c.n, k = c.k, K = c.K;
-    // reference recometrics.hpp:390-393
-    const int min_items_pool = std::max(std::max(c.min_items_pool, K), 2);
-    const int min_pos_test = std::min(c.min_pos_test, 1);
-    int req = 0;
-    for (int i = 0; i < 10; i++) if (c.out[i]) req |= (1 << i);
-    const bool want_auc = req & (RQ_ROC | RQ_PR);
+    const size_t head = P::lds_b(NG, 32 * ns) + (with_lists ? P::lists_b(ns, K) : 0);
+    const size_t tb = ((size_t)1 << j) * P::GU * sizeof(T);
+    return want_auc ? (head + tb - 1) / tb * tb + (size_t)GROUPS_PER_BLOCK * (1 << j) * P::GU * (sizeof(T) + 4) : head;
+}
 
-    const int NG = P::supported_ng(k);
-    if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
-
-    if (!cx.ev_valid) {
-        for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&cx.ev[i]));
-        HIP_CHECK(hipEventCreateWithFlags(&cx.done, hipEventDisableTiming));
-        cx.ev_valid = true;
-    } else {
-        HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // the previous call on this context may still be running on another stream
-    }
-    g_last_ctx = &cx;
-    HIP_CHECK(hipEventRecord(g_ev[0], stream));
-    // side stream of the context: kernels that do not depend on one another run beside the main stream's (the dense train rows beside
-    // the positives, the streamed users' ranks beside the rest of the finalisation; a depth-split call's second sweep launch)
-    auto side_stream = [&]() -> hipStream_t {
-        if (!cx.side_stream) {
-            HIP_CHECK(create_stream(&cx.side_stream, cx.high_priority));
-            for (int i = 0; i < 7; i++) HIP_CHECK(hipEventCreateWithFlags(&cx.side_ev[i], hipEventDisableTiming));
-        }
-        return cx.side_stream;
-    };
-    // (an error between a fork and its join must not leave the side stream reading the call's buffers behind the caller's back)
-    struct SideGuard {
-        Ctx &cx; int pending = 0;                               // pieces of side-stream work the main stream has not been told to wait for yet
-        ~SideGuard() { if (pending > 0 && cx.side_stream) (void)hipStreamSynchronize(cx.side_stream); }
-    } side_guard{cx};
-    auto fork_side = [&]() { hipStream_t sd = side_stream(); HIP_CHECK(hipEventRecord(cx.side_ev[0], stream)); HIP_CHECK(hipStreamWaitEvent(sd, cx.side_ev[0], 0)); side_guard.pending++; return sd; };
-    auto join_side = [&]() { HIP_CHECK(hipEventRecord(cx.side_ev[1], cx.side_stream)); HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[1], 0)); side_guard.pending = 0; };
-    const bool use_side = !g_sw.no_side;
-
-    RM_TRACE_POINT("run: start");
-    // ---- plan ----
-    int *flags = (int *)ws.get("flags", sizeof(int) * (size_t)m);
-    int *user_nslots = (int *)ws.get("user_nslots", sizeof(int) * (size_t)m);
-    int *uslot_base = (int *)ws.get("uslot_base", sizeof(int) * (size_t)m);
-    Plan *plan = (Plan *)ws.get("plan", sizeof(Plan));
-    int *heavy_users = (int *)ws.get("heavy_users", sizeof(int) * (size_t)m);
-    ClassifyArgs ca{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
-                    flags, user_nslots, heavy_users, plan};
-    ca.only = c.only_users;
-    ca.heavy_npos = K > FIN_TOPV ? FIN_TOPV : HEAVY_NPOS;
-    // the caller's CSR arrays are validated in front of everything that indexes by them (an out-of-range column index in
-    // k_train_bits would be a memory fault; on the CPU reference it is a segfault): the index pointers by k_classify itself, the
-    // 80 MB of indices of BASELINE C2 by k_check_csr_rows beside the plan chain (~40 us)
-    ca.check_ptr = c.csr_checked ? 0 : 1; ca.nnz_train = c.nnz_train; ca.nnz_test = c.nnz_test;
-    // Users with more than POS_CHUNK test items are "streamed" (rm_device.hpp STREAM_CLASS) when a score row for each of
-    // them fits the HBM budget: a third of the free memory unless RM_STREAM_BUDGET_MB says otherwise (0 = never; such
-    // users then take one sweep slot per chunk of their test row -- same results, the contraction repeated per chunk).
-    // The plan assumes they fit; the host looks at their number in the read-back and, should the rows not fit, plans once more
-    // without streaming (what used to be two launches in front of k_classify -- count, decide -- on every call).
-    const long long stream_ld_max = ((long long)n + 191) / 192 * 192;             // row stride for either tile size (64 / 96 items)
-    // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
-    // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
-    const bool want_lane = lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
-    const bool ext_topk = (!want_lane && K > 256) || g_sw.ext_topk;
-    long long stream_cap = 0;
-    if (want_auc || ext_topk) {
-        stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
-        // (a pass over a subset of the users -- the exact second pass of the fp32 tie noise -- stores rows for that subset only)
-        const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
-        if (ext_topk) {
-            if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, "k_metrics > 256 keeps one score row (" + std::to_string(stream_ld_max * (long long)sizeof(T)) +
-                                       " B) per user in device memory: " + std::to_string(m_rows) + " users do not fit, at most " + std::to_string(stream_cap) + " per call"};
-            ca.force_stream = 1;
-        } else if (stream_cap > 0) ca.allow_stream = 1;
-    }
-    const long long slot_bound = (long long)m + c.nnz_test / POS_CHUNK + 1;
-    const long long group_bound = slot_bound / GU + 2;
-    int *slot_user = (int *)ws.get("slot_user", sizeof(int) * (size_t)slot_bound);
-    int *slot_chunk = (int *)ws.get("slot_chunk", sizeof(int) * (size_t)slot_bound);
-    int *slot_index = (int *)ws.get("slot_index", sizeof(int) * (size_t)slot_bound);
-    unsigned char *slot_j = (unsigned char *)ws.get("slot_j", (size_t)slot_bound);
-    int *gj = (int *)ws.get("gj", sizeof(int) * (size_t)group_bound);
-    long long *grow = (long long *)ws.get("grow", sizeof(long long) * (size_t)group_bound);
-    int *sc_user = (int *)ws.get("sc_user", sizeof(int) * (size_t)slot_bound);
-    int *sc_chunk = (int *)ws.get("sc_chunk", sizeof(int) * (size_t)slot_bound);
-    int *tile_total = nullptr, *tile_offset = nullptr;
-    const int n_tiles = (int)cdiv(m, 1024);
-    if (m > 8192) {                                          // one block walking the whole array costs ~0.5 us per 1024 entries
-        tile_total = (int *)ws.get("scan_tile_total", sizeof(int) * (size_t)n_tiles);
-        tile_offset = (int *)ws.get("scan_tile_offset", sizeof(int) * (size_t)n_tiles);
-    }
-    const bool items_known = c.items_tag != 0 && c.items_tag == cx.packed_tag;       // a later batch of the same host call
-    // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
-    // depends on K alone: it stays in the workspace, and only a longer one (or a moved buffer) is uploaded again -- the copy
-    // comes from pageable memory, which blocks the host and waits for the stream
-    double *log2tab = (double *)ws.get("log2tab", sizeof(double) * (size_t)K);
-    if (cx.log2_ptr != (const void *)log2tab || cx.log2_K < K) {
-        std::vector<double> lt((size_t)K);
-        for (int i = 0; i < K; i++) lt[i] = std::log2(i + 2);
-        HIP_CHECK(hipMemcpy(log2tab, lt.data(), sizeof(double) * (size_t)K, hipMemcpyHostToDevice));       // (synchronous: `lt` is on the stack)
-        cx.log2_ptr = (const void *)log2tab; cx.log2_K = K;
-    }
-    if (!cx.pinned_plan) HIP_CHECK(hipHostMalloc((void **)&cx.pinned_plan, sizeof(Plan), hipHostMallocDefault));
-    // (one answer per call: a later pass -- the exact passes of the tie noise, on this or on a peer context with less free memory --
-    // carries the first pass's answer; rows handed over by another pass are proof that they fit)
-    const bool dense_ok = std::is_same<T, float>::value && (c.ext_bits ? true : c.dense_fit >= 0 ? c.dense_fit != 0 : dense_rows_fit(ws, m, n));
-    bool bits_early = false, bits_early_masked = false, masked_from_bits = false;
-    // the positives' stream: the streamed users' chain beside the table users', and what is made per test entry beside the plan chain
-    struct PosGuard { hipStream_t st = nullptr; ~PosGuard() { if (st) (void)hipStreamSynchronize(st); } } pos_guard;     // (an error between fork and join)
-    auto pos_stream = [&]() {
-        if (!cx.pos_stream) {
-            HIP_CHECK(create_stream(&cx.pos_stream, cx.high_priority));
-            for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreateWithFlags(&cx.pos_ev[i], hipEventDisableTiming));
-        }
-        return cx.pos_stream;
-    };
-    const bool flat_early = want_auc && !c.only_users && c.nnz_test > 0 && !g_sw.no_pos_flat;
-    int *ent_user = nullptr; unsigned char *ent_masked = nullptr;
-    PosArgs<T> pf{};
-    if (flat_early) {
-        ent_user = (int *)ws.get("ent_user", sizeof(int) * (size_t)c.nnz_test);
-        ent_masked = (unsigned char *)ws.get("ent_masked", (size_t)c.nnz_test);
-        pf.m = m; pf.n = n; pf.k = k; pf.A = c.A; pf.lda = c.lda; pf.B = c.B; pf.ldb = c.ldb;
-        pf.train_p = c.train_p; pf.train_i = c.train_i; pf.test_p = c.test_p; pf.test_i = c.test_i; pf.flags = flags;
-        pf.pos_tmp = (T *)ws.get("pos_tmp", sizeof(T) * (size_t)c.nnz_test);
-        if (sizeof(T) == 4 && !g_sw.no_pos_keys) pf.pos_key = (unsigned long long *)ws.get("pos_key", 8 * ((size_t)c.nnz_test + 8));
-        pf.noise_row = c.noise_row; pf.noise_row0 = c.noise_row0; pf.noise_E = c.noise_E; pf.noise_ld = c.noise_ld;
-        pf.noise_flag = c.noise_flag; pf.plan = plan;
-    }
-    auto launch_flat = [&](hipStream_t es) {
-        hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, es, pf, ent_user);
-        // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
-        if (masked_from_bits) HIP_CHECK(hipStreamWaitEvent(es, cx.side_ev[5], 0));
-        else hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, es, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
-        hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, es, pf, ent_masked);
-    };
-    Plan hp;
-    for (int attempt = 0; ; attempt++) {
-        // ---- the plan chain: five launches that depend on one another, on the call's stream (index pointers only) ----
-        if (attempt == 0) HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
-        else {
-            // (a second plan keeps the count of the users the tie noise's first pass has flagged so far: the positives' scores of the
-            // first attempt, which count them, are not made again)
-            const size_t at = offsetof(Plan, n_noise_flagged);
-            HIP_CHECK(hipMemsetAsync(plan, 0, at, stream));
-            HIP_CHECK(hipMemsetAsync((char *)plan + at + sizeof(int), 0, sizeof(Plan) - at - sizeof(int), stream));
-        }
-        hipLaunchKernelGGL(k_classify, dim3(cdiv(m, 1024)), dim3(1024), 0, stream, ca);
-        // (the two forks behind k_classify, recorded BEFORE the rest of the chain is enqueued: the host needs ~4 us per launch, and the
-        // chain's kernels used to reach the device 60 us late, behind everything that was enqueued for the other streams)
-        if (use_side) {
-            side_stream(); pos_stream();
-            HIP_CHECK(hipEventRecord(cx.side_ev[0], stream));
-            HIP_CHECK(hipEventRecord(cx.pos_ev[0], stream));
-        }
-        if (tile_total) {
-            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(1024), 0, stream, user_nslots, uslot_base, m, tile_total);
-            hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, tile_total, tile_offset, n_tiles, &plan->n_slots, plan, GU);
-        } else {
-            hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, user_nslots, uslot_base, m, &plan->n_slots, plan, GU);
-        }
-        AssignArgs aa{m, c.test_p, flags, user_nslots, uslot_base, want_auc ? 1 : 0, plan, slot_user, slot_chunk, slot_index, slot_j, sc_user, sc_chunk,
-                      ext_topk ? 1 : 0, tile_offset};
-        hipLaunchKernelGGL(k_assign_slots, dim3(cdiv(m, ASSIGN_THREADS)), dim3(ASSIGN_THREADS), 0, stream, aa);
-        hipLaunchKernelGGL(k_block_tables, dim3(1), dim3(1024), 0, stream, plan, slot_j, gj, grow, GU);
-        // ---- beside it: what reads the index arrays and the factors ----
-        // On the side stream the CSR rows' validation (gated on the index pointers k_classify has just checked), then the dense train
-        // rows (fp32, small item counts; set_train_bits), which depend on the CSR inputs alone: they run during the rest of the plan
-        // chain, the read-back -- the host's one wait of the call -- and the positives' scores.  Whether the rows also mark the test
-        // items (`mask_test`) is only decided behind the read-back; the guess here is the usual answer, and a wrong guess costs one
-        // more launch of the kernel behind it.  On the positives' stream max |A| and max |B| and the user of every test entry.  The
-        // plan carries the checks' verdicts and the maxima: its read-back waits for both streams.
-        hipStream_t aux = stream, aux2 = stream;
-        if (use_side) {
-            aux = cx.side_stream; aux2 = cx.pos_stream;
-            HIP_CHECK(hipStreamWaitEvent(aux, cx.side_ev[0], 0)); side_guard.pending++;
-            HIP_CHECK(hipStreamWaitEvent(aux2, cx.pos_ev[0], 0)); pos_guard.st = aux2;
-        }
-        if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
-        if (use_side) HIP_CHECK(hipEventRecord(cx.side_ev[2], aux));
-        hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
-        if (!items_known) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
-        if (use_side) HIP_CHECK(hipEventRecord(cx.pos_ev[2], aux2));
-        // (the user of every test entry, for the positives' scores by entry: index pointers only)
-        if (attempt == 0 && flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, aux2, m, c.test_p, ent_user, plan);
-        // (463 MB of writes at BASELINE C2; four resident blocks per CU leave half of the wave slots to the plan's kernels and the
-        // read-back's copy.  With the positives' scores by entry the kernel also says which test items are train items, `ent_masked`:
-        // a bit of the row it has just built.)
-        if (attempt == 0 && std::is_same<T, float>::value && use_side && !c.ext_bits && dense_ok && !g_sw.no_early_bits) {
-            SweepArgs probe{};
-            const bool guess = want_auc && !ext_topk && !g_sw.no_test_mask;
-            const unsigned *had = (const unsigned *)cx.bits_ptr;
-            const bool reuse = c.same_train_rows && had && !cx.bits_partial && cx.bits_words == dense_row_words(n) && cx.bits_m == m && cx.bits_masked == guess &&
-                               had == (const unsigned *)ws.get("train_bits", (size_t)m * (size_t)dense_row_words(n) * 4);
-            if (!reuse) {
-                set_train_bits(probe, cx, c, m, n, dense_ok, aux, guess, false, false, flat_early ? ent_masked : nullptr);
-                HIP_CHECK(hipEventRecord(cx.side_ev[4], aux));
-                HIP_CHECK(hipEventRecord(cx.side_ev[5], aux));
-                bits_early = true; bits_early_masked = guess; masked_from_bits = flat_early;
-            }
-        }
-        if (use_side) { HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[2], 0)); HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[2], 0)); }
-        HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
-        if (attempt == 0 && flat_early) {
-            // The scores of the test entries (k_pos_scores_flat) depend on the inputs and on the users' flags alone: they run on the
-            // positives' stream beside the read-back and the host's work behind it.  They index the item factors by the test items, so
-            // they follow the index checks (and return when those found a defect) -- and they follow the plan's last kernel and the
-            // copy: their blocks take every wave slot they find, and a plan kernel's block of 1,024 threads then waits for sixteen
-            // slots of one CU to fall free at once (measured: the read-back 0.2 ms late).  Without dense train rows k_test_masked says
-            // which test items are train items, behind the scores.
-            if (use_side) {
-                HIP_CHECK(hipEventRecord(cx.pos_ev[3], stream));
-                HIP_CHECK(hipStreamWaitEvent(cx.pos_stream, cx.pos_ev[3], 0));
-            }
-            launch_flat(aux2);
-            if (use_side) HIP_CHECK(hipEventRecord(cx.pos_ev[1], cx.pos_stream));
-        }
-        RM_TRACE_POINT("run: plan chain + side kernels enqueued");
-        HIP_CHECK(hipStreamSynchronize(stream));
-        RM_TRACE_POINT("run: plan read back");
-        // (the stream has waited for the checks and the maxima: only the dense train rows of the first attempt may still be running on
-        // the side stream, only the positives' scores on theirs)
-        if (use_side && !(attempt == 0 && bits_early)) side_guard.pending--;
-        if (use_side && !flat_early) pos_guard.st = nullptr;
-        hp = *cx.pinned_plan;
-        throw_csr_defects(hp, c, cx);
-        // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
-        if (ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0) {
-            ca.allow_stream = 0; ca.check_ptr = 0;
-            // (attempt 0's kernels on BOTH side streams read `flags` and `plan`, which the second plan rewrites: wait for them)
-            if (use_side) {
-                HIP_CHECK(hipStreamSynchronize(cx.side_stream)); side_guard.pending = bits_early ? 1 : 0;
-                if (cx.pos_stream) HIP_CHECK(hipStreamSynchronize(cx.pos_stream));
-            }
-            continue;
-        }
-        break;
-    }
-    throw_csr_defects(hp, c, cx);
-
-    const int n_slots = hp.n_slots, n_groups = hp.n_groups;
-    const int jmax = want_auc ? hp.jmax : 0;
-    // streamed users own the last slots; the tables and their kernels cover slots [0, stream_slot0)
-    const int n_stream = (want_auc || ext_topk) ? hp.class_count[STREAM_CLASS] : 0;
-    const int stream_slot0 = n_stream > 0 ? hp.class_offset[STREAM_CLASS] : n_slots;
-    // |any partial sum| <= k * max|A| * max|B|: if that is comfortably finite in T, no score is NaN / Inf
-    if (items_known) { hp.amax_b = cx.packed_amax_b; hp.nonfinite_b = cx.packed_nonfinite_b; }
-    else { cx.packed_amax_b = hp.amax_b; cx.packed_nonfinite_b = hp.nonfinite_b; }
-    double amax_a, amax_b;
-    std::memcpy(&amax_a, &hp.amax_a, 8); std::memcpy(&amax_b, &hp.amax_b, 8);
-    const double tmax = std::is_same<T, float>::value ? 3.0e38 : 1.0e308;
-    const bool check_nan = hp.nonfinite || hp.nonfinite_b || !((double)k * amax_a * 1.001 < tmax / std::max(amax_b, 1e-300));
-    const int n_ublocks = (n_groups + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK;
-
-    // ---- sweep geometry ----
-    // (each group's positives table is aligned to its own size, 2^j rows of GU scores: worst-case padding = one table)
+// The sweep's geometry: sub-tiles, the two-level grid, the list scheme, the LDS carve-up and the depth split.  A pure function of
+// the plan's read-back, the call's shape and the switches.
+struct Geometry {
+    int jmax, n_ublocks, nsub, tile_items, n_waves, tiles_total;
+    int n_splits, tail_ublocks, tail_splits, part_splits;
+    bool mask_test, use_ext_bits, list_in_lds, want_pending;
+    int n_part, part_extra;
+    size_t per_key, lds_total, sync_off; int pend_cap;
+    int u_split, j_shallow; size_t lds_l;                  // depth split: the shallow user blocks [0, u_split) with their lists in LDS
+};
+template <class T>
+Geometry sweep_geometry(const Call<T> &c, const Plan &hp, int NG, bool want_auc, bool want_lane, bool ext_topk, bool check_nan, bool dense_ok,
+                        const Switches &sw)
+{
+    typedef Prec<T> P;
+    const int n = c.n, K = c.K;
+    Geometry g{};
+    g.jmax = want_auc ? hp.jmax : 0;
+    g.n_ublocks = (hp.n_groups + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK;
+    const int n_ublocks = g.n_ublocks;
+    auto lds_need_n = [&](bool with_lists, int ns) { return sweep_lds<T>(NG, K, want_auc, with_lists, ns, g.jmax); };
     // sub-tiles per step (waves per block = 4 nsub): three when the fp32 kernel for <= 64 factors keeps its lists in LDS
     // next to the larger item tile -- the third wave per SIMD fills the vector pipe the epilogue leaves idle
-    int nsub = 2;
-    auto lds_need_j = [&](bool with_lists, int ns, int j) {                      // LDS of a block of depth j
-        const size_t head = P::lds_b(NG, 32 * ns) + (with_lists ? P::lists_b(ns, K) : 0);
-        const size_t tb = ((size_t)1 << j) * GU * sizeof(T);
-        return want_auc ? (head + tb - 1) / tb * tb + (size_t)GROUPS_PER_BLOCK * (1 << j) * GU * (sizeof(T) + 4) : head;
-    };
-    auto lds_need_n = [&](bool with_lists, int ns) { return lds_need_j(with_lists, ns, jmax); };
     // (three sub-tiles with the lane buffers of larger k_metrics were built and measured in round 6 -- 162-168 VGPRs, no spills -- and are
     // SLOWER: a user's candidates are then spread over three waves whose bounds each see a third of the items; BASELINE C2's shape at
     // K = 100: 13.4 against 12.4 ms, profiles/r6_ab_c2.txt)
-    if (!ext_topk && !want_lane && P::max_nsub >= 3 && NG <= 8 && lds_need_n(true, 3) + SYNC_BYTES <= LDS_LIMIT && !g_sw.hbm_lists && !g_sw.nsub2)
-        nsub = 3;
+    g.nsub = 2;
+    if (!ext_topk && !want_lane && P::max_nsub >= 3 && NG <= 8 && lds_need_n(true, 3) + SYNC_BYTES <= LDS_LIMIT && !sw.hbm_lists && !sw.nsub2)
+        g.nsub = 3;
     // (four sub-tiles -- sixteen waves, four per SIMD, 128 registers each -- were built in round 5, passed the parity tests and were
     // 1.9 % SLOWER at BASELINE C2: profiles/r5_ab_c2.txt r5a; the patches are scratch/dropped/r5_nsub4*)
-    const int tile_items = 32 * nsub, n_waves = 4 * nsub;
-    const int tiles_total = (n + tile_items - 1) / tile_items;
+    const int nsub = g.nsub;
+    g.tile_items = 32 * nsub; g.n_waves = 4 * nsub;
+    g.tiles_total = (n + g.tile_items - 1) / g.tile_items;
+    const int tiles_total = g.tiles_total;
     // LDS admits one block per CU, so the grid runs in rounds of 256 blocks, and a block costs its tiles plus a fixed part:
     //   block(s) = tiles_total / s + 13 (tables into LDS, the top-K lists filling up, list sort, histogram flush)
     //              + 0.4 % of the sweep per 10 of k_metrics (every item range restarts the streaming top-K lists)
@@ -888,7 +658,7 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
         auto block = [&](int sct) { return (double)tiles_total / sct + fixed; };
         // (0.2 of a round with the lane buffers, whose blocks differ by their selections; 0.1 with the lists: round 6, scratch/r6_slack.sh --
         // tutorial shape 2.57 -> 2.54 ms, 20,000 users of C2 1.14 -> 1.11, north-star shape 77.3 -> 77.2; C4 / C5 lose 5 % / 1 % below 0.2)
-        const double slack = g_sw.split_slack >= 0 ? g_sw.split_slack / 100.0 : (want_lane ? 0.2 : 0.1);
+        const double slack = want_lane ? 0.2 : 0.1;
         auto last = [&](double rounds) { return std::max(std::ceil(rounds - 1e-9), rounds + slack); };
         double best = 1e300;
         for (int sct = 1; sct <= max_splits; sct++) {
@@ -903,77 +673,322 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
             }
         }
     }
-    if (const char *e = g_sw.splits.empty() ? nullptr : g_sw.splits.c_str()) {                                // A/B timing and tests: "S" or "S,tail_ublocks,tail_splits"
+    if (!sw.splits.empty()) {                                // A/B timing and tests: "S" or "S,tail_ublocks,tail_splits"
         int v[3] = {1, 0, 0};
-        sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]);
+        sscanf(sw.splits.c_str(), "%d,%d,%d", &v[0], &v[1], &v[2]);
         n_splits = std::max(1, std::min(v[0], std::max(1, MAX_PARTS / nsub)));
         tail_ublocks = std::max(0, std::min(v[1], n_ublocks)); tail_splits = std::max(1, std::min(v[2], std::max(1, MAX_PARTS / nsub)));
         if (tail_ublocks == 0) tail_splits = 0;
     }
-    const int part_splits = std::max(n_splits, tail_splits);
+    g.n_splits = n_splits; g.tail_ublocks = tail_ublocks; g.tail_splits = tail_splits;
+    g.part_splits = std::max(n_splits, tail_splits);
     // fp32, small item counts (dense train rows), ROC / PR-AUC wanted: the rows mark the users' test items too, the sweep never
     // meets a candidate that IS one of the user's positives (an exact tie, resolved by the tie rule three tiles out of four at
     // 27k items), and k_merge_positives puts the test items back.  Not when a score can be non-finite (a test item masked by the
     // train row is marked +inf in the tables), not with chunked long rows (more slots than users: their best positives are not in the primary slot),
     // not beyond the lists (k_select_topk works on the stored rows).
-    bool mask_test = std::is_same<T, float>::value && want_auc && !ext_topk && !check_nan && n_slots > 0 &&
-                     dense_ok && hp.n_slots == hp.n_active && hp.n_only_ndcg == 0 &&
-                     nsub * part_splits + 1 <= MAX_PARTS && !g_sw.no_test_mask;
+    g.mask_test = std::is_same<T, float>::value && want_auc && !ext_topk && !check_nan && hp.n_slots > 0 &&
+                  dense_ok && hp.n_slots == hp.n_active && hp.n_only_ndcg == 0 &&
+                  nsub * g.part_splits + 1 <= MAX_PARTS && !sw.no_test_mask;
     // rows handed over by another pass: usable when they were built the way this pass would build them (unmasked rows are
     // always valid: the old scheme)
-    const bool use_ext_bits = c.ext_bits != nullptr && c.ext_words == dense_row_words(n) && (!c.ext_masked || mask_test);
-    if (use_ext_bits) mask_test = c.ext_masked;
-    const int n_part = nsub * part_splits + (mask_test ? 1 : 0);
-    const int part_extra = mask_test ? 1 : 0;
-    auto lds_need = [&](bool with_lists) { return lds_need_n(with_lists, nsub); };
-    const bool list_in_lds = !ext_topk && !want_lane && lds_need(true) + SYNC_BYTES <= LDS_LIMIT && !g_sw.hbm_lists;
-    size_t lds_total = lds_need(list_in_lds);
-    // per-lane pending buffers for top-K candidates behind everything else when 2..8 keys per lane still fit
-    // (fp32: not for the append-buffer lists of K > 32, whose appends are already single stores)
-    const bool want_pending = !ext_topk && !want_lane && P::has_pending && !g_sw.no_pending;
-    const size_t per_key = (size_t)n_waves * WAVE * P::pend_key_bytes;            // one key per lane and wave
-    int pend_cap = 0; size_t pend_off = 0, sync_off = 0;
-    if (P::block_carve) {
-        // the kernel sizes its tables per block (by the block's own depth) and computes the pending capacity from what
-        // is left below the counter: allocate for the deepest block plus, if it still fits, 8 keys per lane
-        pend_cap = want_pending ? P::pend_cap_max : 0;
-        lds_total = std::min<size_t>(LDS_LIMIT, lds_total + SYNC_BYTES + pend_cap * per_key);
-        sync_off = lds_total - SYNC_BYTES;                         // split-barrier counter of the sweep, last 16 bytes
-    } else {
-        sync_off = lds_total; lds_total += SYNC_BYTES;
-        pend_off = lds_total;
-        if (want_pending) {
-            pend_cap = (int)std::min<size_t>(8, (LDS_LIMIT - lds_total) / per_key);
-            if (pend_cap < 2) pend_cap = 0;
-            lds_total += pend_cap * per_key;
+    g.use_ext_bits = c.ext_bits != nullptr && c.ext_words == dense_row_words(n) && (!c.ext_masked || g.mask_test);
+    if (g.use_ext_bits) g.mask_test = c.ext_masked;
+    g.n_part = nsub * g.part_splits + (g.mask_test ? 1 : 0);
+    g.part_extra = g.mask_test ? 1 : 0;
+    g.list_in_lds = !ext_topk && !want_lane && lds_need_n(true, nsub) + SYNC_BYTES <= LDS_LIMIT && !sw.hbm_lists;
+    // per-lane pending buffers for top-K candidates behind everything else (fp32: not for the append-buffer lists of K > 32, whose
+    // appends are already single stores).  The kernel sizes its tables per block (by the block's own depth) and computes the
+    // pending capacity from what is left below the counter: allocate for the deepest block plus, if it still fits, the keys per lane
+    g.want_pending = !ext_topk && !want_lane && P::has_pending && !sw.no_pending;
+    g.per_key = (size_t)g.n_waves * WAVE * P::pend_key_bytes;            // one key per lane and wave
+    g.pend_cap = g.want_pending ? P::pend_cap_max : 0;
+    g.lds_total = std::min<size_t>(LDS_LIMIT, lds_need_n(g.list_in_lds, nsub) + SYNC_BYTES + g.pend_cap * g.per_key);
+    g.sync_off = g.lds_total - SYNC_BYTES;                              // split-barrier counter of the sweep, last 16 bytes
+    // Depth split: when only the deepest user blocks force the lists out of LDS (the allocation is sized per launch, the tables per
+    // block), the shallow blocks [0, u_split) get their own launch with LDS lists.
+    g.u_split = 0; g.j_shallow = -1; g.lds_l = 0;
+    if (!g.list_in_lds && !want_lane && K <= 32 && want_auc && !sw.hbm_lists) {
+        for (int j = g.jmax - 1; j >= 0 && g.j_shallow < 0; j--)
+            if (sweep_lds<T>(NG, K, want_auc, true, nsub, j) + SYNC_BYTES <= LDS_LIMIT) g.j_shallow = j;
+        if (g.j_shallow >= 0) g.u_split = hp.class_offset[g.j_shallow + 1] / (GROUPS_PER_BLOCK * P::GU);
+    }
+    if (g.u_split > 0)
+        g.lds_l = std::min<size_t>(LDS_LIMIT, sweep_lds<T>(NG, K, want_auc, true, nsub, g.j_shallow) + SYNC_BYTES + g.pend_cap * g.per_key);
+    return g;
+}
+
+// One call through the device pipeline: the stages of DESIGN.md section 1 as members, the state they hand on as fields.
+template <class T>
+struct Pipeline {
+    typedef Prec<T> P;
+    typedef typename std::remove_pointer<decltype(typename P::Args{}.thr_shared)>::type ThrT;
+    static constexpr int GU = P::GU;
+    const Call<T> &c; hipStream_t stream; Ctx &cx; Workspace &ws;
+    const int m, n, k, K;
+    Beside side, pos;                       // kernels that do not depend on one another run beside the call's stream (run_stages)
+    bool use_side = !g_sw.no_side;
+    // begin
+    int min_items_pool = 0, min_pos_test = 0, req = 0, NG = 0; bool want_auc = false;
+    // plan
+    int *flags = nullptr, *user_nslots = nullptr, *uslot_base = nullptr, *heavy_users = nullptr; Plan *plan = nullptr;
+    int *slot_user = nullptr, *slot_chunk = nullptr, *slot_index = nullptr, *gj = nullptr, *sc_user = nullptr, *sc_chunk = nullptr;
+    long long *grow = nullptr; double *log2tab = nullptr;
+    ClassifyArgs ca{};
+    bool want_lane = false, ext_topk = false, items_known = false, dense_ok = false;
+    bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
+    Plan hp{};
+    int n_slots = 0, n_stream = 0, stream_slot0 = 0; bool check_nan = false;
+    // geometry
+    Geometry g{};
+    // prep
+    FinalArgs<T, T> fa{};
+    Entry<T> *merged = nullptr; long long *rank_sorted = nullptr;
+    bool topv_pending = false;
+    T *pos_score = nullptr; unsigned *hist = nullptr; int *pos_order = nullptr, *pos_item = nullptr;
+    Entry<T> *pl = nullptr; PartialStat<T> *pst = nullptr;
+    T *stream_scores = nullptr, *spos_score = nullptr; int *spos_item = nullptr; unsigned *shist = nullptr;
+    long long stream_ld = 0;
+    typename P::Args sa{};
+    typename P::ListT *glists = nullptr; int *lane_cnt = nullptr; ThrT *thr_shared = nullptr;
+    bool lane_lists = false, bits_wait = false;
+    // sweep
+    bool collect = false; CollectGeom collect_g{};
+
+    Pipeline(const Call<T> &c_, hipStream_t s, Ctx &cx_)
+        : c(c_), stream(s), cx(cx_), ws(cx_.ws), m(c_.m), n(c_.n), k(c_.k), K(c_.K),
+          side(cx_.side_stream, cx_.side_ev, 7, cx_.high_priority), pos(cx_.pos_stream, cx_.pos_ev, 5, cx_.high_priority) {}
+
+    // ---- begin: the reference's clamps, the metrics asked for, the context's events ----
+    void begin()
+    {
+        // reference recometrics.hpp:390-393
+        min_items_pool = std::max(std::max(c.min_items_pool, K), 2);
+        min_pos_test = std::min(c.min_pos_test, 1);
+        for (int i = 0; i < 10; i++) if (c.out[i]) req |= (1 << i);
+        want_auc = req & (RQ_ROC | RQ_PR);
+        NG = P::supported_ng(k);
+        if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
+        if (!cx.ev_valid) {
+            for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&cx.ev[i]));
+            HIP_CHECK(hipEventCreateWithFlags(&cx.done, hipEventDisableTiming));
+            cx.ev_valid = true;
+        } else {
+            HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // the previous call on this context may still be running on another stream
         }
+        g_last_ctx = &cx;
+        HIP_CHECK(hipEventRecord(cx.ev[0], stream));
+        RM_TRACE_POINT("run: start");
     }
 
-    Entry<T> *merged = (Entry<T> *)ws.get("merged", sizeof(Entry<T>) * (size_t)m * K);
-    // the argument block of the finalisation kernels is filled in as the pieces come into being
-    long long *rank_sorted = nullptr;
-    if (c.pos_rank) rank_sorted = (long long *)ws.get("rank_sorted", sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1));
-    if (rank_sorted) HIP_CHECK(hipMemsetAsync(rank_sorted, 0, sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1), stream));
-    FinalArgs<T, T> fa{};
-    fa.m = m; fa.n = n; fa.K = K; fa.req = req; fa.cumulative = c.cumulative ? 1 : 0; fa.noise = c.noise ? 1 : 0; fa.gu = GU;
-    fa.train_p = c.train_p; fa.test_p = c.test_p; fa.test_i = c.test_i; fa.test_v = c.test_v;
-    fa.flags = flags; fa.user_nslots = user_nslots; fa.uslot_base = uslot_base; fa.slot_index = slot_index;
-    fa.gj = gj; fa.grow = grow; fa.log2tab = log2tab;
-    fa.p = c.out[0]; fa.tp = c.out[1]; fa.r = c.out[2]; fa.ap = c.out[3]; fa.tap = c.out[4];
-    fa.ndcg = c.out[5]; fa.hit = c.out[6]; fa.rr = c.out[7]; fa.roc = c.out[8]; fa.pr = c.out[9];
-    fa.merged = merged; fa.rank_sorted = rank_sorted; fa.status = c.status;
-    fa.noise_flag = c.noise_flag; fa.plan = plan;
-    fa.n_slots = n_slots; fa.slot_user = slot_user; fa.slot_chunk = slot_chunk;
-    fa.stream_slot0 = stream_slot0;
-    if (want_auc && n_slots > 0) fa.auc_part = (AucPart *)ws.get("auc_part", sizeof(AucPart) * (size_t)n_slots);
+    // ---- plan: classify the users, slots and groups; beside it the CSR checks, the maxima, the early dense rows; read back ----
+    void plan_stage()
+    {
+        flags = (int *)ws.get("flags", sizeof(int) * (size_t)m);
+        user_nslots = (int *)ws.get("user_nslots", sizeof(int) * (size_t)m);
+        uslot_base = (int *)ws.get("uslot_base", sizeof(int) * (size_t)m);
+        plan = (Plan *)ws.get("plan", sizeof(Plan));
+        heavy_users = (int *)ws.get("heavy_users", sizeof(int) * (size_t)m);
+        ca = ClassifyArgs{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
+                          flags, user_nslots, heavy_users, plan};
+        ca.only = c.only_users;
+        ca.heavy_npos = K > FIN_TOPV ? FIN_TOPV : HEAVY_NPOS;
+        // the caller's CSR arrays are validated in front of everything that indexes by them (an out-of-range column index in
+        // k_train_bits would be a memory fault; on the CPU reference it is a segfault): the index pointers by k_classify itself, the
+        // 80 MB of indices of BASELINE C2 by k_check_csr_rows beside the plan chain (~40 us)
+        ca.check_ptr = c.csr_checked ? 0 : 1; ca.nnz_train = c.nnz_train; ca.nnz_test = c.nnz_test;
+        // Users with more than POS_CHUNK test items are "streamed" (rm_device.hpp STREAM_CLASS) when a score row for each of
+        // them fits the HBM budget: a third of the free memory unless RM_STREAM_BUDGET_MB says otherwise (0 = never; such
+        // users then take one sweep slot per chunk of their test row -- same results, the contraction repeated per chunk).
+        // The plan assumes they fit; the host looks at their number in the read-back and, should the rows not fit, plans once more
+        // without streaming (what used to be two launches in front of k_classify -- count, decide -- on every call).
+        const long long stream_ld_max = ((long long)n + 191) / 192 * 192;             // row stride for either tile size (64 / 96 items)
+        // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
+        // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
+        want_lane = lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
+        ext_topk = (!want_lane && K > 256) || g_sw.ext_topk;
+        long long stream_cap = 0;
+        if (want_auc || ext_topk) {
+            stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
+            // (a pass over a subset of the users -- the exact second pass of the fp32 tie noise -- stores rows for that subset only)
+            const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
+            if (ext_topk) {
+                if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, "k_metrics > 256 keeps one score row (" + std::to_string(stream_ld_max * (long long)sizeof(T)) +
+                                           " B) per user in device memory: " + std::to_string(m_rows) + " users do not fit, at most " + std::to_string(stream_cap) + " per call"};
+                ca.force_stream = 1;
+            } else if (stream_cap > 0) ca.allow_stream = 1;
+        }
+        const long long slot_bound = (long long)m + c.nnz_test / POS_CHUNK + 1;
+        const long long group_bound = slot_bound / GU + 2;
+        slot_user = (int *)ws.get("slot_user", sizeof(int) * (size_t)slot_bound);
+        slot_chunk = (int *)ws.get("slot_chunk", sizeof(int) * (size_t)slot_bound);
+        slot_index = (int *)ws.get("slot_index", sizeof(int) * (size_t)slot_bound);
+        unsigned char *slot_j = (unsigned char *)ws.get("slot_j", (size_t)slot_bound);
+        gj = (int *)ws.get("gj", sizeof(int) * (size_t)group_bound);
+        grow = (long long *)ws.get("grow", sizeof(long long) * (size_t)group_bound);
+        sc_user = (int *)ws.get("sc_user", sizeof(int) * (size_t)slot_bound);
+        sc_chunk = (int *)ws.get("sc_chunk", sizeof(int) * (size_t)slot_bound);
+        int *tile_total = nullptr, *tile_offset = nullptr;
+        const int n_tiles = (int)cdiv(m, 1024);
+        if (m > 8192) {                                          // one block walking the whole array costs ~0.5 us per 1024 entries
+            tile_total = (int *)ws.get("scan_tile_total", sizeof(int) * (size_t)n_tiles);
+            tile_offset = (int *)ws.get("scan_tile_offset", sizeof(int) * (size_t)n_tiles);
+        }
+        items_known = c.items_tag != 0 && c.items_tag == cx.packed_tag;       // a later batch of the same host call
+        // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
+        // depends on K alone: it stays in the workspace, and only a longer one (or a moved buffer) is uploaded again -- the copy
+        // comes from pageable memory, which blocks the host and waits for the stream
+        log2tab = (double *)ws.get("log2tab", sizeof(double) * (size_t)K);
+        if (cx.log2_ptr != (const void *)log2tab || cx.log2_K < K) {
+            std::vector<double> lt((size_t)K);
+            for (int i = 0; i < K; i++) lt[i] = std::log2(i + 2);
+            HIP_CHECK(hipMemcpy(log2tab, lt.data(), sizeof(double) * (size_t)K, hipMemcpyHostToDevice));       // (synchronous: `lt` is on the stack)
+            cx.log2_ptr = (const void *)log2tab; cx.log2_K = K;
+        }
+        if (!cx.pinned_plan) HIP_CHECK(hipHostMalloc((void **)&cx.pinned_plan, sizeof(Plan), hipHostMallocDefault));
+        // (one answer per call: a later pass -- the exact passes of the tie noise, on this or on a peer context with less free memory --
+        // carries the first pass's answer; rows handed over by another pass are proof that they fit)
+        dense_ok = std::is_same<T, float>::value && (c.ext_bits ? true : c.dense_fit >= 0 ? c.dense_fit != 0 : dense_rows_fit(ws, m, n));
+        // the positives' stream: the streamed users' chain beside the table users', and what is made per test entry beside the plan chain
+        flat_early = want_auc && !c.only_users && c.nnz_test > 0 && !g_sw.no_pos_flat;
+        int *ent_user = nullptr; unsigned char *ent_masked = nullptr;
+        PosArgs<T> pf{};
+        if (flat_early) {
+            ent_user = (int *)ws.get("ent_user", sizeof(int) * (size_t)c.nnz_test);
+            ent_masked = (unsigned char *)ws.get("ent_masked", (size_t)c.nnz_test);
+            pf.m = m; pf.n = n; pf.k = k; pf.A = c.A; pf.lda = c.lda; pf.B = c.B; pf.ldb = c.ldb;
+            pf.train_p = c.train_p; pf.train_i = c.train_i; pf.test_p = c.test_p; pf.test_i = c.test_i; pf.flags = flags;
+            pf.pos_tmp = (T *)ws.get("pos_tmp", sizeof(T) * (size_t)c.nnz_test);
+            if (sizeof(T) == 4) pf.pos_key = (unsigned long long *)ws.get("pos_key", 8 * ((size_t)c.nnz_test + 8));
+            pf.noise_row = c.noise_row; pf.noise_row0 = c.noise_row0; pf.noise_E = c.noise_E; pf.noise_ld = c.noise_ld;
+            pf.noise_flag = c.noise_flag; pf.plan = plan;
+        }
+        for (int attempt = 0; ; attempt++) {
+            // ---- the plan chain: five launches that depend on one another, on the call's stream (index pointers only) ----
+            if (attempt == 0) HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
+            else {
+                // (a second plan keeps the count of the users the tie noise's first pass has flagged so far: the positives' scores of the
+                // first attempt, which count them, are not made again)
+                const size_t at = offsetof(Plan, n_noise_flagged);
+                HIP_CHECK(hipMemsetAsync(plan, 0, at, stream));
+                HIP_CHECK(hipMemsetAsync((char *)plan + at + sizeof(int), 0, sizeof(Plan) - at - sizeof(int), stream));
+            }
+            hipLaunchKernelGGL(k_classify, dim3(cdiv(m, 1024)), dim3(1024), 0, stream, ca);
+            // (the two forks behind k_classify, recorded BEFORE the rest of the chain is enqueued: the host needs ~4 us per launch, and the
+            // chain's kernels used to reach the device 60 us late, behind everything that was enqueued for the other streams)
+            if (use_side) {
+                side.get(); pos.get();
+                HIP_CHECK(hipEventRecord(cx.side_ev[0], stream));
+                HIP_CHECK(hipEventRecord(cx.pos_ev[0], stream));
+            }
+            if (tile_total) {
+                hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(1024), 0, stream, user_nslots, uslot_base, m, tile_total);
+                hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, tile_total, tile_offset, n_tiles, &plan->n_slots, plan, GU);
+            } else {
+                hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, user_nslots, uslot_base, m, &plan->n_slots, plan, GU);
+            }
+            AssignArgs aa{m, c.test_p, flags, user_nslots, uslot_base, want_auc ? 1 : 0, plan, slot_user, slot_chunk, slot_index, slot_j, sc_user, sc_chunk,
+                          ext_topk ? 1 : 0, tile_offset};
+            hipLaunchKernelGGL(k_assign_slots, dim3(cdiv(m, ASSIGN_THREADS)), dim3(ASSIGN_THREADS), 0, stream, aa);
+            hipLaunchKernelGGL(k_block_tables, dim3(1), dim3(1024), 0, stream, plan, slot_j, gj, grow, GU);
+            // ---- beside it: what reads the index arrays and the factors ----
+            // On the side stream the CSR rows' validation (gated on the index pointers k_classify has just checked), then the dense train
+            // rows (fp32, small item counts; set_train_bits), which depend on the CSR inputs alone: they run during the rest of the plan
+            // chain, the read-back -- the host's one wait of the call -- and the positives' scores.  Whether the rows also mark the test
+            // items (`mask_test`) is only decided behind the read-back; the guess here is the usual answer, and a wrong guess costs one
+            // more launch of the kernel behind it.  On the positives' stream max |A| and max |B| and the user of every test entry.  The
+            // plan carries the checks' verdicts and the maxima: its read-back waits for both streams.
+            hipStream_t aux = stream, aux2 = stream;
+            if (use_side) {
+                aux = cx.side_stream; aux2 = cx.pos_stream;
+                HIP_CHECK(hipStreamWaitEvent(aux, cx.side_ev[0], 0)); side.pending++;
+                HIP_CHECK(hipStreamWaitEvent(aux2, cx.pos_ev[0], 0)); pos.pending = 1;
+            }
+            if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
+            if (use_side) HIP_CHECK(hipEventRecord(cx.side_ev[2], aux));
+            hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
+            if (!items_known) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
+            if (use_side) HIP_CHECK(hipEventRecord(cx.pos_ev[2], aux2));
+            // (the user of every test entry, for the positives' scores by entry: index pointers only)
+            if (attempt == 0 && flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, aux2, m, c.test_p, ent_user, plan);
+            // (463 MB of writes at BASELINE C2; four resident blocks per CU leave half of the wave slots to the plan's kernels and the
+            // read-back's copy.  With the positives' scores by entry the kernel also says which test items are train items, `ent_masked`:
+            // a bit of the row it has just built.)
+            if (attempt == 0 && std::is_same<T, float>::value && use_side && !c.ext_bits && dense_ok) {
+                SweepArgs probe{};
+                const bool guess = want_auc && !ext_topk && !g_sw.no_test_mask;
+                const unsigned *had = (const unsigned *)cx.bits_ptr;
+                const bool reuse = c.same_train_rows && had && !cx.bits_partial && cx.bits_words == dense_row_words(n) && cx.bits_m == m && cx.bits_masked == guess &&
+                                   had == (const unsigned *)ws.get("train_bits", (size_t)m * (size_t)dense_row_words(n) * 4);
+                if (!reuse) {
+                    set_train_bits(probe, cx, c, m, n, dense_ok, aux, guess, false, false, flat_early ? ent_masked : nullptr);
+                    HIP_CHECK(hipEventRecord(cx.side_ev[4], aux));
+                    HIP_CHECK(hipEventRecord(cx.side_ev[5], aux));
+                    bits_early = true; bits_early_masked = guess; masked_from_bits = flat_early;
+                }
+            }
+            if (use_side) { HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[2], 0)); HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[2], 0)); }
+            HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
+            if (attempt == 0 && flat_early) {
+                // The scores of the test entries (k_pos_scores_flat) depend on the inputs and on the users' flags alone: they run on the
+                // positives' stream beside the read-back and the host's work behind it.  They index the item factors by the test items, so
+                // they follow the index checks (and return when those found a defect) -- and they follow the plan's last kernel and the
+                // copy: their blocks take every wave slot they find, and a plan kernel's block of 1,024 threads then waits for sixteen
+                // slots of one CU to fall free at once (measured: the read-back 0.2 ms late).  Without dense train rows k_test_masked says
+                // which test items are train items, behind the scores.
+                if (use_side) {
+                    HIP_CHECK(hipEventRecord(cx.pos_ev[3], stream));
+                    HIP_CHECK(hipStreamWaitEvent(cx.pos_stream, cx.pos_ev[3], 0));
+                }
+                hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, aux2, pf, ent_user);
+                // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
+                if (masked_from_bits) HIP_CHECK(hipStreamWaitEvent(aux2, cx.side_ev[5], 0));
+                else hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, aux2, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
+                hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, aux2, pf, ent_masked);
+                if (use_side) HIP_CHECK(hipEventRecord(cx.pos_ev[1], cx.pos_stream));
+            }
+            RM_TRACE_POINT("run: plan chain + side kernels enqueued");
+            HIP_CHECK(hipStreamSynchronize(stream));
+            RM_TRACE_POINT("run: plan read back");
+            // (the stream has waited for the checks and the maxima: only the dense train rows of the first attempt may still be running on
+            // the side stream, only the positives' scores on theirs)
+            if (use_side && !(attempt == 0 && bits_early)) side.pending--;
+            if (use_side && !flat_early) pos.pending = 0;
+            hp = *cx.pinned_plan;
+            throw_csr_defects(hp, c, cx);
+            // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
+            if (ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0) {
+                ca.allow_stream = 0; ca.check_ptr = 0;
+                // (attempt 0's kernels on BOTH side streams read `flags` and `plan`, which the second plan rewrites: wait for them)
+                if (use_side) {
+                    HIP_CHECK(hipStreamSynchronize(cx.side_stream)); side.pending = bits_early ? 1 : 0;
+                    if (cx.pos_stream) HIP_CHECK(hipStreamSynchronize(cx.pos_stream));
+                }
+                continue;
+            }
+            break;
+        }
+        throw_csr_defects(hp, c, cx);
+        n_slots = hp.n_slots;
+        // streamed users own the last slots; the tables and their kernels cover slots [0, stream_slot0)
+        n_stream = (want_auc || ext_topk) ? hp.class_count[STREAM_CLASS] : 0;
+        stream_slot0 = n_stream > 0 ? hp.class_offset[STREAM_CLASS] : n_slots;
+        // |any partial sum| <= k * max|A| * max|B|: if that is comfortably finite in T, no score is NaN / Inf
+        if (items_known) { hp.amax_b = cx.packed_amax_b; hp.nonfinite_b = cx.packed_nonfinite_b; }
+        else { cx.packed_amax_b = hp.amax_b; cx.packed_nonfinite_b = hp.nonfinite_b; }
+        double amax_a, amax_b;
+        std::memcpy(&amax_a, &hp.amax_a, 8); std::memcpy(&amax_b, &hp.amax_b, 8);
+        const double tmax = std::is_same<T, float>::value ? 3.0e38 : 1.0e308;
+        check_nan = hp.nonfinite || hp.nonfinite_b || !((double)k * amax_a * 1.001 < tmax / std::max(amax_b, 1e-300));
+    }
+
     // ideal-DCG values of the users with very long test rows (k_top_values: a wavefront per such user, a chain of K dependent
     // rounds -- latency, 0.16 ms at BASELINE C2): they depend on the test rows alone, so they are computed on the side stream
     // beside the preparation kernels instead of between the sweep and k_finalize, which waits for them
     // (launched BEHIND the operand packing on the side stream, which the sweep waits for: with k_metrics > 64 every row of more than
     // 64 test items is listed and the kernel is half a millisecond at BASELINE C2's shape)
-    bool topv_pending = false;
-    fa.heavy_npos = ca.heavy_npos;
-    auto launch_top_values = [&]() {
+    void launch_top_values()
+    {
         if (!(fa.ndcg && hp.n_heavy > 0)) return;
         // (min(K, longest test row) values per user: with a cap of 256 the rows beyond it fell back to k_finalize's repeated selection on
         // one thread -- L x positives dependent loads: 160 of the 190 ms of a K = 300 step at BASELINE C2's shape)
@@ -982,27 +997,34 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
         fa.heavy_nan = (unsigned char *)ws.get("heavy_nan", (size_t)m);
         fa.heavy_users = heavy_users; fa.n_heavy = hp.n_heavy;
         hipStream_t tv_stream = stream;
-        if (use_side) tv_stream = fork_side();
+        if (use_side) tv_stream = side.fork(stream);
         hipLaunchKernelGGL((k_top_values<T, T>), dim3(cdiv((long long)hp.n_heavy * WAVE, 256)), dim3(256), 0, tv_stream, fa);
         if (use_side) { HIP_CHECK(hipEventRecord(cx.side_ev[3], tv_stream)); topv_pending = true; }
-    };
-    const int stream_parts = (int)cdiv(n, STREAM_RANK_THREADS * STREAM_RANK_ITEMS);
-    const int stream_ipt = ((int)cdiv(n, (long long)stream_parts * STREAM_RANK_THREADS) + 7) / 8 * 8;     // equal pieces of the row
-    auto rank_streamed_rows = [&](int r0, int r1, hipStream_t st) {
-        if (r1 <= r0) return;
-        hipLaunchKernelGGL((k_rank_streamed<T, T>), dim3((unsigned)((long long)(r1 - r0) * stream_parts)), dim3(STREAM_RANK_THREADS), 0, st, fa, stream_parts, stream_ipt, r0);
-    };
-    auto auc_streamed_rows = [&](int r0, int r1, hipStream_t st) {
-        if (r1 <= r0) return;
-        hipLaunchKernelGGL((k_auc_streamed<T, T>), dim3(cdiv((long long)(r1 - r0) * WAVE, 256)), dim3(256), 0, st, fa, r0, r1);
-    };
-    T *pos_score = nullptr; unsigned *hist = nullptr; int *pos_order = nullptr, *pos_item = nullptr;
-    Entry<T> *pl = nullptr; PartialStat<T> *pst = nullptr;
-    T *stream_scores = nullptr, *spos_score = nullptr; int *spos_item = nullptr; unsigned *shist = nullptr;
-    const long long stream_ld = (long long)tiles_total * tile_items;
-    struct { bool on = false; const char *glists = nullptr; const int *lane_cnt = nullptr; const void *thr = nullptr; CollectGeom g{}; } collect;
+    }
 
-    if (n_slots > 0) {
+    // ---- prep: the finalisation's arguments, operand packing, dense train rows, positives tables, seeds ----
+    void prep()
+    {
+        merged = (Entry<T> *)ws.get("merged", sizeof(Entry<T>) * (size_t)m * K);
+        if (c.pos_rank) rank_sorted = (long long *)ws.get("rank_sorted", sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1));
+        if (rank_sorted) HIP_CHECK(hipMemsetAsync(rank_sorted, 0, sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1), stream));
+        // the argument block of the finalisation kernels is filled in as the pieces come into being
+        fa.m = m; fa.n = n; fa.K = K; fa.req = req; fa.cumulative = c.cumulative ? 1 : 0; fa.noise = c.noise ? 1 : 0; fa.gu = GU;
+        fa.train_p = c.train_p; fa.test_p = c.test_p; fa.test_i = c.test_i; fa.test_v = c.test_v;
+        fa.flags = flags; fa.user_nslots = user_nslots; fa.uslot_base = uslot_base; fa.slot_index = slot_index;
+        fa.gj = gj; fa.grow = grow; fa.log2tab = log2tab;
+        fa.p = c.out[0]; fa.tp = c.out[1]; fa.r = c.out[2]; fa.ap = c.out[3]; fa.tap = c.out[4];
+        fa.ndcg = c.out[5]; fa.hit = c.out[6]; fa.rr = c.out[7]; fa.roc = c.out[8]; fa.pr = c.out[9];
+        fa.merged = merged; fa.rank_sorted = rank_sorted; fa.status = c.status;
+        fa.noise_flag = c.noise_flag; fa.plan = plan;
+        fa.n_slots = n_slots; fa.slot_user = slot_user; fa.slot_chunk = slot_chunk;
+        fa.stream_slot0 = stream_slot0;
+        if (want_auc && n_slots > 0) fa.auc_part = (AucPart *)ws.get("auc_part", sizeof(AucPart) * (size_t)n_slots);
+        fa.heavy_npos = ca.heavy_npos;
+        stream_ld = (long long)g.tiles_total * g.tile_items;
+        if (n_slots == 0) return;
+        const int n_groups = hp.n_groups, tiles_total = g.tiles_total, tile_items = g.tile_items;
+
         // ---- pack operands into the MFMA images ----
         const long long bp_units = P::items_units(tiles_total, NG, tile_items), ap_units = P::users_units(n_groups, NG);
         typename P::PackT *Bp = (typename P::PackT *)ws.get("Bp", 16 * (size_t)bp_units);
@@ -1011,116 +1033,60 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
         const bool items_packed = items_known && cx.packed_tile == tile_items && cx.packed_ng == NG && cx.packed_ptr == (const void *)Bp;
         // Only the sweep reads the packed images: with a side stream they are made there, behind the dense train rows and beside the
         // positives' kernels (120 us of BASELINE C2's preparation that sat in front of k_pos_scores); the sweep's launch waits for both.
-        const bool packs_side = use_side && want_auc && cx.side_stream != nullptr && !g_sw.no_pack_beside;
+        const bool packs_side = use_side && want_auc && cx.side_stream != nullptr;
         pack_operands(c.A, c.lda, c.B, c.ldb, n, k, NG, tile_items, slot_user, n_slots, Ap, ap_units, Bp, bp_units, packs_side ? cx.side_stream : stream, !items_packed);
         if (packs_side) {
             HIP_CHECK(hipEventRecord(cx.side_ev[4], cx.side_stream));   // (behind the rows, when they were launched: one event for both)
-            if (!bits_early) side_guard.pending++;
+            if (!bits_early) side.pending++;
         }
         cx.packed_tag = c.items_tag; cx.packed_tile = tile_items; cx.packed_ng = NG; cx.packed_ptr = (const void *)Bp;
         launch_top_values();
 
         // ---- dense train rows (fp32, small item counts) ----
         // (measured: on the side stream beside the positives' kernels they gain nothing -- both are bound by memory; r3_ab_c2.txt)
-        typename P::Args sa{};
         // (rows launched beside the plan read-back that turn out not to be the ones wanted -- a wrong guess of `mask_test`, rows handed over
         // by another pass -- are waited for here, before anything is launched over them; the usual case waits in front of the sweep)
-        bool bits_wait = bits_early || packs_side;
-        if (bits_early && (bits_early_masked != mask_test || (use_ext_bits && dense_ok))) {
+        bits_wait = bits_early || packs_side;
+        if (bits_early && (bits_early_masked != g.mask_test || (g.use_ext_bits && dense_ok))) {
             HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[4], 0));
-            side_guard.pending--; bits_wait = false;
+            side.pending--; bits_wait = false;
         }
-        if (use_ext_bits && dense_ok) set_ext_bits(sa, c.ext_bits, (int)c.ext_words);
-        else set_train_bits(sa, cx, c, m, n, dense_ok, stream, mask_test, bits_early, bits_early_masked);
+        if (g.use_ext_bits && dense_ok) set_ext_bits(sa, c.ext_bits, (int)c.ext_words);
+        else set_train_bits(sa, cx, c, m, n, dense_ok, stream, g.mask_test, bits_early, bits_early_masked);
 
-        // ---- positives ----
-        if (want_auc) {
-            const long long rows = hp.total_rows + n_groups;       // 2^j rows per group (one +inf pad row each)
-            pos_score = (T *)ws.get("pos_score", sizeof(T) * (size_t)(rows + 1) * GU);
-            pos_item = (int *)ws.get("pos_item", sizeof(int) * (size_t)(rows + 1) * GU);
-            hist = (unsigned *)ws.get("hist", sizeof(unsigned) * (size_t)(rows + 1) * GU);
-            T *pos_tmp = (T *)ws.get("pos_tmp", sizeof(T) * (size_t)std::max<long long>(c.nnz_test, 1));
-            pos_order = (int *)ws.get("pos_order", sizeof(int) * (size_t)std::max<long long>(c.nnz_test, 1));
-            PosArgs<T> pa{m, n, k, c.A, c.lda, c.B, c.ldb, c.train_p, c.train_i, c.test_p, c.test_i,
-                          flags, user_nslots, uslot_base, slot_index, grow, pos_tmp, pos_order, pos_score, pos_item, GU};
-            pa.noise_row = c.noise_row; pa.noise_row0 = c.noise_row0; pa.noise_E = c.noise_E; pa.noise_ld = c.noise_ld;
-            pa.noise_flag = c.noise_flag; pa.plan = plan;
-            if (sizeof(T) == 4 && !g_sw.no_pos_keys)
-                pa.pos_key = (unsigned long long *)ws.get("pos_key", 8 * ((size_t)std::max<long long>(c.nnz_test, 1) + 8));
-            // Scores of the test entries: by entry (k_pos_scores_flat, launched beside the plan chain: every lane busy) unless the call
-            // evaluates a few of its users only -- then a wavefront per slot is less work.
-            const bool flat = flat_early;
-            // The streamed users' positives (the all-pairs rank of long test rows: vector work) run on a stream of their own beside
-            // the table users'
-            hipStream_t ps = stream;
-            const bool pos_beside = use_side && n_stream > 0 && stream_slot0 > 0 && !g_sw.no_pos_beside;
-            if (pos_beside) {
-                // (not the side stream: that one carries the dense train rows and the operand packing, 0.3 ms the streamed users' chain
-                // used to queue behind.  The host has waited for the call's stream since: nothing to wait for over there.)
-                ps = pos_stream();
-                pos_guard.st = ps;
-            }
-            PosArgs<T> pb = pa;
-            // (with the scores by entry the positives' stream is busy with them: the tables are filled on the call's stream meanwhile)
-            const hipStream_t fill = (flat && pos_beside) ? stream : ps;
-            if (n_stream > 0) {
-                const size_t nz = (size_t)std::max<long long>(c.nnz_test, 1);
-                spos_score = (T *)ws.get("spos_score", sizeof(T) * nz);
-                spos_item = (int *)ws.get("spos_item", sizeof(int) * nz);
-                shist = (unsigned *)ws.get("shist", sizeof(unsigned) * nz);
-                pb.stream = 1; pb.spos_score = spos_score; pb.spos_item = spos_item;
-                // (+inf in every rank: entries that repeat an item -- a non-canonical CSR row -- share a rank and leave one unused)
-                hipLaunchKernelGGL(k_init_tables<T>, dim3(cdiv((long long)nz, 256)), dim3(256), 0, fill, spos_score, shist, (long long)nz);
-            }
-            const int nsc = hp.n_stream_chunks;
-            hipLaunchKernelGGL(k_init_tables<T>, dim3(cdiv(rows * GU, 256)), dim3(256), 0, stream, pos_score, hist, rows * GU);
-            if (flat) {
-                if (pos_beside && n_stream > 0) { HIP_CHECK(hipEventRecord(cx.pos_ev[2], stream)); HIP_CHECK(hipStreamWaitEvent(ps, cx.pos_ev[2], 0)); }
-                // (the scores are the last thing on the positives' stream: whoever is not on it waits for them)
-                if (use_side) { HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[1], 0)); if (!pos_beside) pos_guard.st = nullptr; }
-            } else {
-                if (n_stream > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(nsc, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, ps, pb, sc_user, sc_chunk, nsc);
-                if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(stream_slot0, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
-            }
-            if (n_stream > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)nsc * WAVE, 256)), dim3(256), 0, ps, pb, sc_user, sc_chunk, nsc);
-            if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)stream_slot0 * WAVE, 256)), dim3(256), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
-            if (pos_beside) { HIP_CHECK(hipEventRecord(cx.pos_ev[4], ps)); HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[4], 0)); pos_guard.st = nullptr; }
-        }
+        if (want_auc) positives();
 
         if (n_stream > 0) stream_scores = (T *)ws.get("stream_scores", sizeof(T) * (size_t)n_stream * (size_t)stream_ld);
-        if (!ext_topk) pl = (Entry<T> *)ws.get("pl", sizeof(Entry<T>) * (size_t)n_slots * n_part * K);
-        pst = (PartialStat<T> *)ws.get("pst", sizeof(PartialStat<T>) * (size_t)n_slots * n_part);
-        typename P::ListT *glists = nullptr;
-        const unsigned n_blocks = (unsigned)((n_ublocks - tail_ublocks) * n_splits + tail_ublocks * tail_splits);
-        const bool lane_lists = want_lane && !ext_topk;                     // per-lane append buffers + k_collect_topk (rm_list.hpp)
+        if (!ext_topk) pl = (Entry<T> *)ws.get("pl", sizeof(Entry<T>) * (size_t)n_slots * g.n_part * K);
+        pst = (PartialStat<T> *)ws.get("pst", sizeof(PartialStat<T>) * (size_t)n_slots * g.n_part);
+        const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
+        lane_lists = want_lane && !ext_topk;                     // per-lane append buffers + k_collect_topk (rm_list.hpp)
         int lane_cap = lane_lists ? P::lane_cap(K) : 0;
         if (lane_lists && g_sw.lane_cap_set > 0) lane_cap = (int)std::min<long long>(std::max<long long>(P::lane_cap(K), (g_sw.lane_cap_set + 15) / 16 * 16), (COLLECT_MAX_ENTRIES - K) / 16 * 16);
         if (lane_lists && g_sw.lane_cap_min >= 0)        // K + slack survivors and one tile's appends (16: both precisions' bound) in one lane
             lane_cap = std::min(lane_cap, (K + lane_sel_slack(K) + 16 + 1 + 15) / 16 * 16);
-        int *lane_cnt = nullptr;
         if (lane_lists) {
-            glists = (typename P::ListT *)ws.get("glists", (size_t)n_blocks * n_waves * WAVE * (size_t)lane_cap * (sizeof(T) + 4));
-            lane_cnt = (int *)ws.get("lane_cnt", sizeof(int) * (size_t)n_blocks * n_waves * WAVE);
-        } else if (!list_in_lds && !ext_topk) {
-            glists = (typename P::ListT *)ws.get("glists", sizeof(typename P::ListT) * (size_t)n_blocks * n_waves * GU * (2 * K + 32));
+            glists = (typename P::ListT *)ws.get("glists", (size_t)n_blocks * g.n_waves * WAVE * (size_t)lane_cap * (sizeof(T) + 4));
+            lane_cnt = (int *)ws.get("lane_cnt", sizeof(int) * (size_t)n_blocks * g.n_waves * WAVE);
+        } else if (!g.list_in_lds && !ext_topk) {
+            glists = (typename P::ListT *)ws.get("glists", sizeof(typename P::ListT) * (size_t)n_blocks * g.n_waves * GU * (2 * K + 32));
         }
 
-        typedef typename std::remove_pointer<decltype(typename P::Args{}.thr_shared)>::type ThrT;
-        ThrT *thr_shared = (ThrT *)ws.get("thr_shared", sizeof(ThrT) * (size_t)n_slots);
+        thr_shared = (ThrT *)ws.get("thr_shared", sizeof(ThrT) * (size_t)n_slots);
         if (want_auc && !ext_topk && !g_sw.no_seed)
             hipLaunchKernelGGL((k_seed_thresholds<T, ThrT>), dim3(cdiv(n_slots, 256)), dim3(256), 0, stream, n_slots, stream_slot0, K, GU, slot_user, slot_chunk,
                                user_nslots, flags, c.test_p, grow, pos_score, spos_score, thr_shared);
         else HIP_CHECK(hipMemsetAsync(thr_shared, 0, sizeof(ThrT) * (size_t)n_slots, stream));
         sa.thr_shared = thr_shared;
-        sa.n = n; sa.K = K; sa.ngt = NG; sa.n_slots = n_slots; sa.n_groups = n_groups; sa.n_ublocks = n_ublocks;
-        sa.n_splits = n_splits; sa.tail_ublocks = tail_ublocks; sa.tail_splits = tail_splits; sa.part_splits = part_splits; sa.tiles_total = tiles_total; sa.jmax = jmax; sa.check_nan = check_nan ? 1 : 0; sa.buffered_lists = (want_lane || ext_topk) ? 1 : 0; sa.ext_topk = ext_topk ? 1 : 0;
+        sa.n = n; sa.K = K; sa.ngt = NG; sa.n_slots = n_slots; sa.n_groups = n_groups; sa.n_ublocks = g.n_ublocks;
+        sa.n_splits = g.n_splits; sa.tail_ublocks = g.tail_ublocks; sa.tail_splits = g.tail_splits; sa.part_splits = g.part_splits; sa.tiles_total = tiles_total; sa.jmax = g.jmax; sa.check_nan = check_nan ? 1 : 0; sa.buffered_lists = (want_lane || ext_topk) ? 1 : 0; sa.ext_topk = ext_topk ? 1 : 0;
         sa.Ap = (decltype(sa.Ap))Ap; sa.Bp = (decltype(sa.Bp))Bp; sa.slot_user = slot_user; sa.slot_chunk = slot_chunk;
         sa.train_p = c.train_p; sa.train_i = c.train_i; sa.gj = gj; sa.grow = grow;
         sa.pos_score = pos_score; sa.pos_item = pos_item; sa.hist = hist; sa.glists = glists; sa.lane_cap = lane_cap; sa.lane_cnt = lane_cnt; sa.pl = pl; sa.pst = pst; sa.dump = nullptr;
-        P::set_pending(sa, pend_cap, (int)pend_off);
-        P::set_sync(sa, (int)sync_off);
+        P::set_pending(sa, g.pend_cap, 0);
+        P::set_sync(sa, (int)g.sync_off);
         sa.stream_slot0 = stream_slot0; sa.stream_ld = stream_ld; sa.stream_scores = stream_scores;
-        set_part_extra(sa, part_extra);
+        set_part_extra(sa, g.part_extra);
         sa.noise_row = c.noise_row; sa.noise_row0 = c.noise_row0; sa.noise_E = c.noise_E; sa.noise_ld = c.noise_ld;
         set_spec(sa);
 
@@ -1128,175 +1094,268 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
         // `flags_event` (their noise rows, their own sweeps) -- nothing in front of this point does
         if (bits_wait) {
             HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[4], 0));
-            side_guard.pending--;
+            side.pending--;
         }
         // Sample seeds (k_seed_from_sample, rm_prep.hpp): the sweep's DUMP variant scores the first S items for every slot, a
         // wavefront per slot takes the K-th best candidate of them, and the lane buffers start with a pass rate of K / S.
         const bool sample_lists = !lane_lists && !ext_topk && sizeof(T) == 4;      // (the LDS / HBM lists: seeded as well, from a smaller sample)
         const int sample_S = (lane_lists || sample_lists) ? sample_seed_items<T>(ws, K, n, n_slots, check_nan || c.noise_E != nullptr, sample_lists) : 0;
-        if (sample_S > 0 && !sample_lists) seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, n_ublocks, stream);
+        if (sample_S > 0 && !sample_lists) seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, g.n_ublocks, stream);
         else if (sample_S > 0) {
             const long long units = P::items_units(sample_S / TILE_ITEMS, NG);
             typename P::PackT *Bs = (typename P::PackT *)ws.get("sample_items", 16 * (size_t)units);
-            void *Ls = ws.get("sample_lists", sizeof(typename P::ListT) * (size_t)n_ublocks * 8 * GU * (2 + 32));
+            void *Ls = ws.get("sample_lists", sizeof(typename P::ListT) * (size_t)g.n_ublocks * 8 * GU * (2 + 32));
             pack_operands(c.A, c.lda, c.B, c.ldb, sample_S, k, NG, TILE_ITEMS, slot_user, 0, Ap, 0, Bs, units, stream, true);
-            seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, n_ublocks, stream, Bs, Ls);
-        }
-        if (c.flag_snapshot) {
-            HIP_CHECK(hipMemcpyAsync(c.flag_snapshot, c.noise_flag, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(c.flag_count_host, &plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipEventRecord(c.flags_event, stream));
+            seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, g.n_ublocks, stream, Bs, Ls);
         }
         RM_TRACE_POINT("run: preparation enqueued");
-        HIP_CHECK(hipEventRecord(g_ev[1], stream));
-        // Depth split: when only the deepest user blocks force the lists out of LDS (the allocation is sized per launch,
-        // the tables per block), the shallow blocks [0, u_split) get their own launch with LDS lists.  The two launches
-        // run side by side on two streams so that neither pays a partially filled last round of its own.
-        int u_split = 0, j_shallow = -1;
-        if (P::block_carve && !list_in_lds && !want_lane && K <= 32 && want_auc && !g_sw.hbm_lists && !g_sw.no_depth_split) {
-            for (int j = jmax - 1; j >= 0 && j_shallow < 0; j--)
-                if (lds_need_j(true, nsub, j) + SYNC_BYTES <= LDS_LIMIT) j_shallow = j;
-            if (j_shallow >= 0) u_split = hp.class_offset[j_shallow + 1] / (GROUPS_PER_BLOCK * GU);
+    }
+
+    // the positives' tables: scores of the test items, their ranks among themselves, placed per group (prep)
+    void positives()
+    {
+        const int n_groups = hp.n_groups;
+        const long long rows = hp.total_rows + n_groups;       // 2^j rows per group (one +inf pad row each)
+        pos_score = (T *)ws.get("pos_score", sizeof(T) * (size_t)(rows + 1) * GU);
+        pos_item = (int *)ws.get("pos_item", sizeof(int) * (size_t)(rows + 1) * GU);
+        hist = (unsigned *)ws.get("hist", sizeof(unsigned) * (size_t)(rows + 1) * GU);
+        T *pos_tmp = (T *)ws.get("pos_tmp", sizeof(T) * (size_t)std::max<long long>(c.nnz_test, 1));
+        pos_order = (int *)ws.get("pos_order", sizeof(int) * (size_t)std::max<long long>(c.nnz_test, 1));
+        PosArgs<T> pa{m, n, k, c.A, c.lda, c.B, c.ldb, c.train_p, c.train_i, c.test_p, c.test_i,
+                      flags, user_nslots, uslot_base, slot_index, grow, pos_tmp, pos_order, pos_score, pos_item, GU};
+        pa.noise_row = c.noise_row; pa.noise_row0 = c.noise_row0; pa.noise_E = c.noise_E; pa.noise_ld = c.noise_ld;
+        pa.noise_flag = c.noise_flag; pa.plan = plan;
+        if (sizeof(T) == 4)
+            pa.pos_key = (unsigned long long *)ws.get("pos_key", 8 * ((size_t)std::max<long long>(c.nnz_test, 1) + 8));
+        // Scores of the test entries: by entry (k_pos_scores_flat, launched beside the plan chain: every lane busy) unless the call
+        // evaluates a few of its users only -- then a wavefront per slot is less work.
+        const bool flat = flat_early;
+        // The streamed users' positives (the all-pairs rank of long test rows: vector work) run on a stream of their own beside
+        // the table users'
+        hipStream_t ps = stream;
+        const bool pos_beside = use_side && n_stream > 0 && stream_slot0 > 0 && !g_sw.no_pos_beside;
+        if (pos_beside) {
+            // (not the side stream: that one carries the dense train rows and the operand packing, 0.3 ms the streamed users' chain
+            // used to queue behind.  The host has waited for the call's stream since: nothing to wait for over there.)
+            ps = pos.get();
+            pos.pending = 1;
         }
-        if (u_split > 0) {
-            hipStream_t g_side_stream = side_stream();
-            hipEvent_t *g_side_ev = cx.side_ev;
+        PosArgs<T> pb = pa;
+        // (with the scores by entry the positives' stream is busy with them: the tables are filled on the call's stream meanwhile)
+        const hipStream_t fill = (flat && pos_beside) ? stream : ps;
+        if (n_stream > 0) {
+            const size_t nz = (size_t)std::max<long long>(c.nnz_test, 1);
+            spos_score = (T *)ws.get("spos_score", sizeof(T) * nz);
+            spos_item = (int *)ws.get("spos_item", sizeof(int) * nz);
+            shist = (unsigned *)ws.get("shist", sizeof(unsigned) * nz);
+            pb.stream = 1; pb.spos_score = spos_score; pb.spos_item = spos_item;
+            // (+inf in every rank: entries that repeat an item -- a non-canonical CSR row -- share a rank and leave one unused)
+            hipLaunchKernelGGL(k_init_tables<T>, dim3(cdiv((long long)nz, 256)), dim3(256), 0, fill, spos_score, shist, (long long)nz);
+        }
+        const int nsc = hp.n_stream_chunks;
+        hipLaunchKernelGGL(k_init_tables<T>, dim3(cdiv(rows * GU, 256)), dim3(256), 0, stream, pos_score, hist, rows * GU);
+        if (flat) {
+            if (pos_beside && n_stream > 0) { HIP_CHECK(hipEventRecord(cx.pos_ev[2], stream)); HIP_CHECK(hipStreamWaitEvent(ps, cx.pos_ev[2], 0)); }
+            // (the scores are the last thing on the positives' stream: whoever is not on it waits for them)
+            if (use_side) { HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[1], 0)); if (!pos_beside) pos.pending = 0; }
+        } else {
+            if (n_stream > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(nsc, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, ps, pb, sc_user, sc_chunk, nsc);
+            if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(stream_slot0, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
+        }
+        if (n_stream > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)nsc * WAVE, 256)), dim3(256), 0, ps, pb, sc_user, sc_chunk, nsc);
+        if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)stream_slot0 * WAVE, 256)), dim3(256), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
+        if (pos_beside) { HIP_CHECK(hipEventRecord(cx.pos_ev[4], ps)); HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[4], 0)); pos.pending = 0; }
+    }
+
+    // ---- sweep: the flags for the tie noise's exact pass, then the sweep launch (two with a depth split) ----
+    void sweep()
+    {
+        if (c.flag_snapshot) {
+            if (n_slots > 0) {
+                HIP_CHECK(hipMemcpyAsync(c.flag_snapshot, c.noise_flag, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, stream));
+                HIP_CHECK(hipMemcpyAsync(c.flag_count_host, &plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, stream));
+            } else {                                                 // (no user to evaluate: nothing is flagged)
+                HIP_CHECK(hipMemsetAsync(c.flag_snapshot, 0, sizeof(int) * (size_t)m, stream));
+                *c.flag_count_host = 0;
+            }
+            HIP_CHECK(hipEventRecord(c.flags_event, stream));
+        }
+        HIP_CHECK(hipEventRecord(cx.ev[1], stream));
+        double *tm = cx.timings;
+        if (n_slots == 0) {
+            HIP_CHECK(hipEventRecord(cx.ev[2], stream));
+            tm[4] = 0; tm[5] = 0; tm[6] = 0; tm[7] = 0;
+            return;
+        }
+        const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
+        if (g.u_split > 0) {
+            // Depth split: the two launches run side by side on two streams so that neither pays a partially filled last round of its own.
+            const int u_split = g.u_split, n_ublocks = g.n_ublocks;
+            hipStream_t sd = side.get();
             typename P::Args sb = sa;                              // the deep blocks: lists in HBM, as computed above
             P::set_ublocks(sb, u_split, n_ublocks - u_split);
             typename P::Args sl = sa;                              // the shallow blocks: lists in LDS
             P::set_ublocks(sl, 0, u_split);
             // (the tail of the two-level grid = the cheapest user blocks = the first ones: the shallow launch's, then the deep one's)
-            sl.tail_ublocks = std::min(tail_ublocks, u_split);
-            sb.tail_ublocks = tail_ublocks - sl.tail_ublocks;
-            const size_t lds_l = std::min<size_t>(LDS_LIMIT, lds_need_j(true, nsub, j_shallow) + SYNC_BYTES + (want_pending ? P::pend_cap_max : 0) * per_key);
-            P::set_pending(sl, want_pending ? P::pend_cap_max : 0, 0);
-            P::set_sync(sl, (int)(lds_l - SYNC_BYTES));
-            HIP_CHECK(hipEventRecord(g_side_ev[0], stream));
-            HIP_CHECK(hipStreamWaitEvent(g_side_stream, g_side_ev[0], 0));
-            dispatch_sweep(want_auc, false, false, nsub, NG, dim3((unsigned)((n_ublocks - u_split - sb.tail_ublocks) * n_splits + sb.tail_ublocks * tail_splits)), lds_total, g_side_stream, sb);
-            HIP_CHECK(hipEventRecord(g_side_ev[1], g_side_stream));
-            dispatch_sweep(want_auc, false, true, nsub, NG, dim3((unsigned)((u_split - sl.tail_ublocks) * n_splits + sl.tail_ublocks * tail_splits)), lds_l, stream, sl);
-            HIP_CHECK(hipStreamWaitEvent(stream, g_side_ev[1], 0));
+            sl.tail_ublocks = std::min(g.tail_ublocks, u_split);
+            sb.tail_ublocks = g.tail_ublocks - sl.tail_ublocks;
+            P::set_pending(sl, g.pend_cap, 0);
+            P::set_sync(sl, (int)(g.lds_l - SYNC_BYTES));
+            HIP_CHECK(hipEventRecord(cx.side_ev[0], stream));
+            HIP_CHECK(hipStreamWaitEvent(sd, cx.side_ev[0], 0));
+            dispatch_sweep(want_auc, false, false, g.nsub, NG, dim3((unsigned)((n_ublocks - u_split - sb.tail_ublocks) * g.n_splits + sb.tail_ublocks * g.tail_splits)), g.lds_total, sd, sb);
+            HIP_CHECK(hipEventRecord(cx.side_ev[1], sd));
+            dispatch_sweep(want_auc, false, true, g.nsub, NG, dim3((unsigned)((u_split - sl.tail_ublocks) * g.n_splits + sl.tail_ublocks * g.tail_splits)), g.lds_l, stream, sl);
+            HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[1], 0));
         } else {
             // (Measured and dropped: the blocks made of streamed users only as a second launch of the sweep variant without rank
             // counting on a side stream, followed there by k_rank_streamed, beside the main launch.  At C2 the step time did
             // not move -- 11.61 vs 11.59 ms -- and at the north-star shape, where one launch is exactly one round of 256
             // blocks, the side launch ran AFTER the main one instead of beside it: 61 ms of tail.  gpurun_out r2q.)
-            dispatch_sweep(want_auc, false, list_in_lds, nsub, NG, dim3(n_blocks), lds_total, stream, sa);
+            dispatch_sweep(want_auc, false, g.list_in_lds, g.nsub, NG, dim3(n_blocks), g.lds_total, stream, sa);
         }
         RM_TRACE_POINT("run: sweep enqueued");
-        HIP_CHECK(hipEventRecord(g_ev[2], stream));
+        HIP_CHECK(hipEventRecord(cx.ev[2], stream));
         if (lane_lists) {
-            collect.on = true; collect.glists = (const char *)glists; collect.lane_cnt = lane_cnt; collect.thr = (const void *)thr_shared;
-            collect.g = CollectGeom{sa.ublock0, sa.n_ublocks, n_splits, tail_ublocks, tail_splits, nsub, GU, P::lanes_per_user, lane_cap, part_extra ? n_part - 1 : -1};
+            collect = true;
+            collect_g = CollectGeom{sa.ublock0, sa.n_ublocks, g.n_splits, g.tail_ublocks, g.tail_splits, g.nsub, GU, P::lanes_per_user, sa.lane_cap, g.part_extra ? g.n_part - 1 : -1};
         }
-        g_timings[4] = u_split > 0 ? 2 : 1; g_timings[5] = n_splits; g_timings[6] = n_blocks; g_timings[7] = (double)lds_total;
+        tm[4] = g.u_split > 0 ? 2 : 1; tm[5] = g.n_splits; tm[6] = n_blocks; tm[7] = (double)g.lds_total;
         cx.timed_slots = n_slots;
         cx.total_slots = n_slots;
-    } else {
-        if (c.flag_snapshot) {                                       // (no user to evaluate: nothing is flagged)
-            HIP_CHECK(hipMemsetAsync(c.flag_snapshot, 0, sizeof(int) * (size_t)m, stream));
-            *c.flag_count_host = 0;
-            HIP_CHECK(hipEventRecord(c.flags_event, stream));
-        }
-        HIP_CHECK(hipEventRecord(g_ev[1], stream));
-        HIP_CHECK(hipEventRecord(g_ev[2], stream));
-        g_timings[4] = 0; g_timings[5] = 0; g_timings[6] = 0; g_timings[7] = 0;
     }
 
-    // ---- finalize ----
-    fa.n_part = n_part; fa.pl = pl; fa.pst = pst; fa.hist = hist; fa.pos_score = pos_score; fa.pos_item_tab = pos_item;
-    // the streamed users' ranks (HBM-bound: the stored score rows) run on the side stream beside the short kernels of the others
-    fa.stream_slot0 = stream_slot0; fa.stream_scores = stream_scores; fa.stream_ld = stream_ld;
-    fa.spos_score = spos_score; fa.spos_item = spos_item; fa.shist = shist;
-    fa.rank_generic = (g_sw.rank_generic ? 1 : 0);
-    const bool ranks_beside = use_side && n_slots > 0 && want_auc && n_stream > 0;
-    // one block of k_rank_streamed per row (rows up to 32,768 items) with the user's table in LDS: the block also walks its counts
-    // (k_auc_streamed's job); k_auc_streamed is then only launched when some row is too long for that
-    bool auc_launch = true;
-    if (stream_parts == 1 && !g_sw.no_fused_auc) {
-        fa.fused_auc = 1 | (mask_test ? 2 : 0);
-        long long top = 1;
-        while (top <= hp.max_npos) top <<= 1;
-        // (k_metrics > 256 streams everybody without counting the long rows first: the longest one is not known then)
-        auc_launch = ext_topk || !(top * (long long)(sizeof(T) / 4) + hp.max_npos + 1 <= STREAM_RANK_LDS / 4);
+    int stream_parts() const { return (int)cdiv(n, STREAM_RANK_THREADS * STREAM_RANK_ITEMS); }
+    void rank_streamed_rows(int r0, int r1, hipStream_t st)
+    {
+        if (r1 <= r0) return;
+        const int parts = stream_parts();
+        const int ipt = ((int)cdiv(n, (long long)parts * STREAM_RANK_THREADS) + 7) / 8 * 8;     // equal pieces of the row
+        hipLaunchKernelGGL((k_rank_streamed<T, T>), dim3((unsigned)((long long)(r1 - r0) * parts)), dim3(STREAM_RANK_THREADS), 0, st, fa, parts, ipt, r0);
     }
-    hipStream_t rank_stream = stream;
-    if (ranks_beside) { rank_stream = fork_side(); rank_streamed_rows(0, n_stream, rank_stream); }
-    if (mask_test) {
-        // (the table users' test items were put back by the sweep, rm_sweep.hpp; the streamed users' are this kernel's)
-        if (n_slots > stream_slot0)
-            hipLaunchKernelGGL((k_merge_positives<T, T>), dim3(cdiv(n_slots - stream_slot0, MERGE_WAVES)), dim3(MERGE_WAVES * WAVE), 0, stream, fa, n_part - 1, stream_slot0);
-        if (ranks_beside && auc_launch) {                          // (it counts the streamed users' own test items: before k_auc_streamed)
-            HIP_CHECK(hipEventRecord(cx.side_ev[2], stream));
-            HIP_CHECK(hipStreamWaitEvent(rank_stream, cx.side_ev[2], 0));
+    void auc_streamed_rows(int r0, int r1, hipStream_t st)
+    {
+        if (r1 <= r0) return;
+        hipLaunchKernelGGL((k_auc_streamed<T, T>), dim3(cdiv((long long)(r1 - r0) * WAVE, 256)), dim3(256), 0, st, fa, r0, r1);
+    }
+    void finalize_slots(int s0, int s1, size_t fin_lds)
+    {
+        if (s1 <= s0) return;
+        fa.fin_slot0 = s0; fa.fin_slot1 = s1;
+        hipLaunchKernelGGL((k_finalize<T, T>), dim3(cdiv(s1 - s0, FIN_THREADS)), dim3(FIN_THREADS), fin_lds, stream, fa);
+    }
+
+    // ---- finalize: merge, streamed ranks and AUC, top-K collection / selection, the metrics ----
+    void finalize()
+    {
+        fa.n_part = g.n_part; fa.pl = pl; fa.pst = pst; fa.hist = hist; fa.pos_score = pos_score; fa.pos_item_tab = pos_item;
+        // the streamed users' ranks (HBM-bound: the stored score rows) run on the side stream beside the short kernels of the others
+        fa.stream_slot0 = stream_slot0; fa.stream_scores = stream_scores; fa.stream_ld = stream_ld;
+        fa.spos_score = spos_score; fa.spos_item = spos_item; fa.shist = shist;
+        fa.rank_generic = (g_sw.rank_generic ? 1 : 0);
+        const bool ranks_beside = use_side && n_slots > 0 && want_auc && n_stream > 0;
+        // one block of k_rank_streamed per row (rows up to 32,768 items) with the user's table in LDS: the block also walks its counts
+        // (k_auc_streamed's job); k_auc_streamed is then only launched when some row is too long for that
+        bool auc_launch = true;
+        if (stream_parts() == 1 && !g_sw.no_fused_auc) {
+            fa.fused_auc = 1 | (g.mask_test ? 2 : 0);
+            long long top = 1;
+            while (top <= hp.max_npos) top <<= 1;
+            // (k_metrics > 256 streams everybody without counting the long rows first: the longest one is not known then)
+            auc_launch = ext_topk || !(top * (long long)(sizeof(T) / 4) + hp.max_npos + 1 <= STREAM_RANK_LDS / 4);
         }
-    }
-    if (ranks_beside && auc_launch) auc_streamed_rows(0, n_stream, rank_stream);
-    hipLaunchKernelGGL((k_finalize_skipped<T, T>), dim3(cdiv(m, 256)), dim3(256), 0, stream, fa);
-    if (topv_pending) {                                           // (k_top_values, launched beside the preparation)
-        HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[3], 0));
-        side_guard.pending--;
-    }
-    if (collect.on) {
-        // k_metrics beyond the LDS lists: the users' ordered top-K out of the sweep's lane buffers, straight into `merged` (behind
-        // k_merge_positives, whose part of `pl` -- the streamed users' own test items -- is one of the inputs)
-        typedef typename std::remove_pointer<decltype(typename P::Args{}.thr_shared)>::type ThrT;
-        fa.collected = 1;
-        if (collect_capw(K, collect.g.lane_cap) == 512)
-            hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 512>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect.g, collect.glists, collect.lane_cnt, (const ThrT *)collect.thr);
-        else if (collect_capw(K, collect.g.lane_cap) == 1024)
-            hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 1024>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect.g, collect.glists, collect.lane_cnt, (const ThrT *)collect.thr);
-        else
-            hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 4096>), dim3(collect_grid(n_slots)), dim3(64), 0, stream, fa, collect.g, collect.glists, collect.lane_cnt, (const ThrT *)collect.thr);
-    }
-    if (n_slots > 0 && ext_topk) {
-        int sel_ld = 2;
-        while (sel_ld < K) sel_ld <<= 1;
-        fa.ext_topk = 1; fa.sel_ld = sel_ld;
-        fa.sel_hi = (unsigned long long *)ws.get("sel_hi", sizeof(unsigned long long) * (size_t)n_slots * sel_ld);
-        fa.sel_lo = (unsigned *)ws.get("sel_lo", sizeof(unsigned) * (size_t)n_slots * sel_ld);
-        hipLaunchKernelGGL((k_select_topk<T, T>), dim3(n_slots), dim3(SELECT_THREADS), 0, stream, fa);
-    }
-    if (n_slots > 0) {
-        if (want_auc) {
-            if (n_stream > 0 && !ranks_beside) { rank_streamed_rows(0, n_stream, stream); if (auc_launch) auc_streamed_rows(0, n_stream, stream); }
-            if (stream_slot0 > 0) hipLaunchKernelGGL((k_auc_slots<T, T>), dim3(cdiv(stream_slot0, 256)), dim3(256), 0, stream, fa);
+        hipStream_t rank_stream = stream;
+        if (ranks_beside) { rank_stream = side.fork(stream); rank_streamed_rows(0, n_stream, rank_stream); }
+        if (g.mask_test) {
+            // (the table users' test items were put back by the sweep, rm_sweep.hpp; the streamed users' are this kernel's)
+            if (n_slots > stream_slot0)
+                hipLaunchKernelGGL((k_merge_positives<T, T>), dim3(cdiv(n_slots - stream_slot0, MERGE_WAVES)), dim3(MERGE_WAVES * WAVE), 0, stream, fa, g.n_part - 1, stream_slot0);
+            if (ranks_beside && auc_launch) {                          // (it counts the streamed users' own test items: before k_auc_streamed)
+                HIP_CHECK(hipEventRecord(cx.side_ev[2], stream));
+                HIP_CHECK(hipStreamWaitEvent(rank_stream, cx.side_ev[2], 0));
+            }
         }
-        const size_t fin_lds = finalize_lds_bytes<T>(K, n_part);
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_finalize<T, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds));
-        auto finalize_slots = [&](int s0, int s1) {
-            if (s1 <= s0) return;
-            fa.fin_slot0 = s0; fa.fin_slot1 = s1;
-            hipLaunchKernelGGL((k_finalize<T, T>), dim3(cdiv(s1 - s0, FIN_THREADS)), dim3(FIN_THREADS), fin_lds, stream, fa);
-        };
-        fa.auc_defer_slot0 = n_slots;
-        if (ranks_beside && (req & (RQ_ROC | RQ_PR)) && !g_sw.no_defer_auc) {
-            // nothing of k_finalize but the two AUC values of the streamed users needs the side stream: it runs for everybody while
-            // their ranks are still being counted there, and a short kernel fills those two in behind the join
-            fa.auc_defer_slot0 = stream_slot0;
-            finalize_slots(0, n_slots);
-            join_side();
-            hipLaunchKernelGGL((k_finalize_auc<T, T>), dim3(cdiv(n_slots - stream_slot0, 256)), dim3(256), 0, stream, fa);
-        } else if (ranks_beside) {
-            finalize_slots(0, stream_slot0);
-            join_side();
-            finalize_slots(stream_slot0, n_slots);
-        } else finalize_slots(0, n_slots);
+        if (ranks_beside && auc_launch) auc_streamed_rows(0, n_stream, rank_stream);
+        hipLaunchKernelGGL((k_finalize_skipped<T, T>), dim3(cdiv(m, 256)), dim3(256), 0, stream, fa);
+        if (topv_pending) {                                           // (k_top_values, launched beside the preparation)
+            HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[3], 0));
+            side.pending--;
+        }
+        if (collect) {
+            // k_metrics beyond the LDS lists: the users' ordered top-K out of the sweep's lane buffers, straight into `merged` (behind
+            // k_merge_positives, whose part of `pl` -- the streamed users' own test items -- is one of the inputs)
+            fa.collected = 1;
+            const char *gl = (const char *)glists;
+            if (collect_capw(K, collect_g.lane_cap) == 512)
+                hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 512>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
+            else if (collect_capw(K, collect_g.lane_cap) == 1024)
+                hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 1024>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
+            else
+                hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 4096>), dim3(collect_grid(n_slots)), dim3(64), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
+        }
+        if (n_slots > 0 && ext_topk) {
+            int sel_ld = 2;
+            while (sel_ld < K) sel_ld <<= 1;
+            fa.ext_topk = 1; fa.sel_ld = sel_ld;
+            fa.sel_hi = (unsigned long long *)ws.get("sel_hi", sizeof(unsigned long long) * (size_t)n_slots * sel_ld);
+            fa.sel_lo = (unsigned *)ws.get("sel_lo", sizeof(unsigned) * (size_t)n_slots * sel_ld);
+            hipLaunchKernelGGL((k_select_topk<T, T>), dim3(n_slots), dim3(SELECT_THREADS), 0, stream, fa);
+        }
+        if (n_slots > 0) {
+            if (want_auc) {
+                if (n_stream > 0 && !ranks_beside) { rank_streamed_rows(0, n_stream, stream); if (auc_launch) auc_streamed_rows(0, n_stream, stream); }
+                if (stream_slot0 > 0) hipLaunchKernelGGL((k_auc_slots<T, T>), dim3(cdiv(stream_slot0, 256)), dim3(256), 0, stream, fa);
+            }
+            const size_t fin_lds = finalize_lds_bytes<T>(K, g.n_part);
+            HIP_CHECK(hipFuncSetAttribute((const void *)k_finalize<T, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds));
+            fa.auc_defer_slot0 = n_slots;
+            if (ranks_beside && (req & (RQ_ROC | RQ_PR)) && !g_sw.no_defer_auc) {
+                // nothing of k_finalize but the two AUC values of the streamed users needs the side stream: it runs for everybody while
+                // their ranks are still being counted there, and a short kernel fills those two in behind the join
+                fa.auc_defer_slot0 = stream_slot0;
+                finalize_slots(0, n_slots, fin_lds);
+                side.join(stream);
+                hipLaunchKernelGGL((k_finalize_auc<T, T>), dim3(cdiv(n_slots - stream_slot0, 256)), dim3(256), 0, stream, fa);
+            } else if (ranks_beside) {
+                finalize_slots(0, stream_slot0, fin_lds);
+                side.join(stream);
+                finalize_slots(stream_slot0, n_slots, fin_lds);
+            } else finalize_slots(0, n_slots, fin_lds);
+        }
+        HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipGetLastError());
-    if (c.topk_idx)
-        hipLaunchKernelGGL(k_export_rank<T>, dim3(cdiv((long long)m * K, 256)), dim3(256), 0, stream, m, K, merged, c.topk_idx, c.topk_score, flags);
-    if (c.pos_rank)           // (per user, never a memset of the whole array: a batch must not clear what other batches wrote)
-        hipLaunchKernelGGL(k_export_pos_rank, dim3(cdiv(m, 128)), dim3(128), 0, stream, c.nnz_test, m, c.test_p, flags, pos_order, rank_sorted, c.pos_rank,
-                           (want_auc && n_slots > 0) ? 1 : 0);
-    RM_TRACE_POINT("run: finalisation enqueued");
-    HIP_CHECK(hipEventRecord(g_ev[3], stream));
-    HIP_CHECK(hipEventRecord(cx.done, stream));
-    cx.ev_recorded = true;
-    HIP_CHECK(hipGetLastError());
+
+    // ---- export: the ranking outputs of rm_rank_*, the context's events ----
+    void export_ranks()
+    {
+        if (c.topk_idx)
+            hipLaunchKernelGGL(k_export_rank<T>, dim3(cdiv((long long)m * K, 256)), dim3(256), 0, stream, m, K, merged, c.topk_idx, c.topk_score, flags);
+        if (c.pos_rank)           // (per user, never a memset of the whole array: a batch must not clear what other batches wrote)
+            hipLaunchKernelGGL(k_export_pos_rank, dim3(cdiv(m, 128)), dim3(128), 0, stream, c.nnz_test, m, c.test_p, flags, pos_order, rank_sorted, c.pos_rank,
+                               (want_auc && n_slots > 0) ? 1 : 0);
+        RM_TRACE_POINT("run: finalisation enqueued");
+        HIP_CHECK(hipEventRecord(cx.ev[3], stream));
+        HIP_CHECK(hipEventRecord(cx.done, stream));
+        cx.ev_recorded = true;
+        HIP_CHECK(hipGetLastError());
+    }
+};
+
+// One pass of a call: DESIGN.md section 1, stage by stage.  Side streams: the context's side stream carries the CSR index checks,
+// the early dense train rows, the operand packing, k_top_values, a depth-split call's second sweep launch and the streamed users'
+// ranks; the positives' stream carries the maxima, the positives' scores by entry and the streamed users' positives.
+template <class T>
+void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
+{
+    Pipeline<T> p(c, stream, cx);
+    p.begin();
+    p.plan_stage();
+    p.g = sweep_geometry<T>(c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
+    p.prep();
+    p.sweep();
+    p.finalize();
+    p.export_ranks();
 }
-
 
 // ---- tie noise on top of run() (rm_noise.hpp) ---------------------------------------------------------------------------
 // fp64: the noise (|e| <= 1e-12) is far above an ulp of any ordinary score, every score changes: every user is evaluated
@@ -1388,7 +1447,7 @@ template <class T>
 void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bool()> *defer = nullptr)
 {
     if (defer) *defer = nullptr;
-    if (!c_in.noise || RM_ABL_NOISE_OFF) { run<T>(c_in, stream, cx); return; }
+    if (!c_in.noise) { run<T>(c_in, stream, cx); return; }
     Call<T> c0 = c_in;
     if (c0.items_tag == 0) c0.items_tag = g_call_counter.fetch_add(1);                   // (a device-pointer call: its passes share B)
     Workspace &ws = cx.ws;
@@ -1490,7 +1549,7 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
             c.only_users = only; c.noise_row = noise_row; c.noise_row0 = 0; c.noise_E = E; c.noise_ld = e_ld; c.noise_flag = nullptr;
             c.eval_users = n_early;
             c.csr_checked = true;
-            if (cx.bits_tag != 0 && cx.bits_tag == c0.items_tag && cx.bits_train_p == c0.train_p && cx.bits_m == m && !cx.bits_partial && !g_sw.no_ext_bits) {
+            if (cx.bits_tag != 0 && cx.bits_tag == c0.items_tag && cx.bits_train_p == c0.train_p && cx.bits_m == m && !cx.bits_partial) {
                 c.ext_bits = (const unsigned *)cx.bits_ptr; c.ext_words = cx.bits_words; c.ext_masked = cx.bits_masked;      // the first pass's rows
             }
             // (whatever fails in there -- the peer context duplicates workspace under memory pressure --, nothing of it may still be
@@ -1621,6 +1680,106 @@ inline void enable_peer_access(int dst_device, int src_device)
 }
 
 
+// RM_HOST_TRACE: the host entry's time stamps and run()'s, on stderr at the end of a host call
+inline void print_host_trace(int n_batches, const std::vector<std::pair<const char *, double>> &stamps)
+{
+    std::string line = "rm host trace (" + std::to_string(n_batches) + " batches, ms):";
+    for (auto &st : stamps) { char buf[96]; snprintf(buf, sizeof buf, " [%s %.3f]", st.first, st.second); line += buf; }
+    fprintf(stderr, "%s\n", line.c_str());
+    std::lock_guard<std::mutex> tl(g_run_trace.mu);
+    std::string l2 = "rm run trace (ms since the library was loaded):";
+    for (auto &pt : g_run_trace.pts) { char buf[112]; snprintf(buf, sizeof buf, " [%s %.3f]", pt.first, pt.second); l2 += buf; }
+    fprintf(stderr, "%s\n", l2.c_str());
+    g_run_trace.pts.clear();
+}
+
+// Users per batch of a host call at most: ~0.4 s of device work at the rate the sweep sustains (2 n k flop per user), whole user
+// blocks, or RM_BATCH_USERS (tests: equal batches of this size); with k_metrics > 256 what one context's lane buffers or score rows hold.
+template <class T> long long batch_users_max(const Workspace &ws, int n, int k, int K)
+{
+    const double rate = std::is_same<T, float>::value ? 6.0e13 : 2.5e13;
+    double bu = 0.4 * rate / (2.0 * (double)n * (double)k);
+    if (g_sw.batch_users > 0) bu = g_sw.batch_users;
+    long long batch = (long long)std::min<double>(std::max(bu, 1024.0), 2.0e9);
+    batch = (batch + 1023) / 1024 * 1024;
+    // k_metrics > 256: the lane buffers when they fit at all (run(): want_lane; one block's worth per 4 GU users on top of the grid's
+    // floor -- lane_blocks_bound), sized so that run() finds every batch fitting; else score rows (ext_topk)
+    const long long lane_blocks = K > 256 && lane_lists_possible<T>(K) ? lane_budget_bytes(ws) * 3 / 4 / lane_list_bytes<T>(K, 1) - lane_blocks_bound<T>(0) : 0;
+    if (lane_blocks >= 8) batch = std::max<long long>(1024, std::min<long long>(batch, lane_blocks * 4 * Prec<T>::GU / 1024 * 1024));
+    else if (K > 256) {                                            // one score row per user of the batch (run(): ext_topk),
+        const long long row = (((long long)n + 191) / 192 * 192) * (long long)sizeof(T);    // with a margin for what run() allocates first
+        batch = std::max<long long>(1, std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row));
+    }
+    return batch;
+}
+// Batch boundaries of m users, at most `batch` per batch (`forced`: all of that size): a first batch of a QUARTER of the users (whole
+// kilo-users) when the range is large enough for the pipeline to matter -- its upload is the only one nothing hides --, then three
+// times the batch before (its upload hides behind the batch before, whose kernels take ~2.5 x as long per user as the copy).
+// BASELINE C2: 34,816 + 103,677 users.
+// Every batch pays the fixed parts of preparation and finalisation again and its plan only comes back when the sweep in front
+// of it has drained, so fewer batches win once the first upload is paid for: round 5 (preparation 0.88 -> 0.56 ms) 9.6 ms per
+// call against 9.9 with (1/8, 3/8, 1/2), and with the tie noise 10.3 against 10.85 (one batch fewer for the exact pass to
+// wait behind; `profiles/r5_host_entry.txt`).  Round 3, when a batch's fixed parts cost twice as much: (1/8, 3/8, 1/2) 10.4,
+// (1/4, 3/4) 10.6, without the second context 11.7 (`profiles/r3_host_entry.txt`).
+inline std::vector<long long> batch_cuts(long long m, long long batch, bool forced)
+{
+    std::vector<long long> cuts{0};
+    long long next = (forced || m <= 16384) ? batch : std::min<long long>(batch, std::max<long long>(8192, (m / 4 + 1023) / 1024 * 1024));
+    while (cuts.back() < m) {
+        long long b1 = std::min<long long>(m, cuts.back() + next);
+        if (m - b1 < 2048 && m - cuts.back() <= batch) b1 = m;                  // no crumb at the end
+        cuts.push_back(b1);
+        next = forced ? batch : std::min<long long>(batch, next * 3);
+    }
+    return cuts;
+}
+
+// The item factors of a host call, dense rows of k, into `dB` on the upload stream.  In a sharded call shard 0 uploads them from
+// the host and publishes the buffer; the others copy it device-to-device (xGMI) and report when they are done with it.
+// Whatever happens, the other shards must neither wait for item factors that never come nor copy from a buffer that is being
+// reused: the destructor has shard 0 publish (possibly a failure) and then wait for every copy, and the others report theirs.
+template <class T> struct ItemUpload {
+    const HostCall<T> &h; SharedItems *sh; int shard; bool published = false, reported = false;
+    ~ItemUpload()
+    {
+        if (!sh) return;
+        if (shard == 0) {
+            std::unique_lock<std::mutex> sl(sh->mu);
+            if (!published) { sh->ready = true; sh->failed = true; sh->cv.notify_all(); }
+            sh->cv.wait(sl, [&] { return sh->copies_pending <= 0; });
+        } else if (!reported) sh->copy_done();
+    }
+    void run(T *dB, int device, hipStream_t up)
+    {
+        const int n = h.n, k = h.k;
+        if (!sh || shard == 0) {
+            // (dense rows: ONE plain copy -- a 2-D copy of pageable memory goes through a staging buffer and a second,
+            // device-side pass: 1.1 ms more for BASELINE C2's A and B)
+            hipError_t e = h.ldb == (size_t)k ? hipMemcpyAsync(dB, h.B, sizeof(T) * (size_t)n * k, hipMemcpyHostToDevice, up)
+                                              : hipMemcpy2DAsync(dB, sizeof(T) * k, h.B, sizeof(T) * h.ldb, sizeof(T) * k, n, hipMemcpyHostToDevice, up);
+            if (sh) {
+                if (e == hipSuccess) e = hipStreamSynchronize(up);
+                std::lock_guard<std::mutex> sl(sh->mu);
+                sh->ready = true; sh->failed = e != hipSuccess; sh->src = dB; sh->src_device = device;
+                published = true;
+                sh->cv.notify_all();
+            }
+            HIP_CHECK(e);
+        } else {
+            {
+                std::unique_lock<std::mutex> sl(sh->mu);
+                sh->cv.wait(sl, [&] { return sh->ready; });
+                if (sh->failed) throw RmError{RM_ERR_HIP, "upload of the item factors failed on the first device"};
+            }
+            enable_peer_access(device, sh->src_device);
+            HIP_CHECK(hipMemcpyPeerAsync(dB, device, sh->src, sh->src_device, sizeof(T) * (size_t)n * k, up));
+            HIP_CHECK(hipStreamSynchronize(up));                      // the source buffer is shard 0's: tell it when we are done with it
+            reported = true;
+            sh->copy_done();
+        }
+    }
+};
+
 // Users [u0, u1) of a host call on the current device.  The inputs are staged into HBM batch by batch and the batches are
 // pipelined: while the kernels of batch i run on the call's stream, the rows of batch i + 1 (user factors, train / test CSR
 // rows) are uploaded on a second stream into their places in the range's device arrays -- a batch only ever reads its own
@@ -1635,20 +1794,7 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     const int m = u1 - u0, n = h.n, k = h.k, K = h.K;
     cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0; cx.ev_recorded = false;
     g_last_ctx = &cx;
-    // whatever happens below, the other shards must neither wait for item factors that never come nor copy from a buffer
-    // that is being reused: shard 0 publishes (possibly a failure) and then waits for every copy; the others report theirs
-    struct SharedGuard {
-        SharedItems *sh; int shard; bool published = false, reported = false;
-        ~SharedGuard()
-        {
-            if (!sh) return;
-            if (shard == 0) {
-                std::unique_lock<std::mutex> sl(sh->mu);
-                if (!published) { sh->ready = true; sh->failed = true; sh->cv.notify_all(); }
-                sh->cv.wait(sl, [&] { return sh->copies_pending <= 0; });
-            } else if (!reported) sh->copy_done();
-        }
-    } guard{shared, shard};
+    ItemUpload<T> items{h, shared, shard};         // (its destructor completes the handshake with the other shards, whatever happens below)
     if (!cx.up_stream) {
         HIP_CHECK(hipStreamCreateWithFlags(&cx.up_stream, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&cx.up_ev[i], hipEventDisableTiming));
@@ -1657,34 +1803,7 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(up, cx.done, 0));   // the previous call on this context may still read the buffers
     // item factors, dense rows of k
     T *dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
-    auto upload_items = [&]() {
-        if (!shared || shard == 0) {
-            // (dense rows: ONE plain copy -- a 2-D copy of pageable memory goes through a staging buffer and a second,
-            // device-side pass: 1.1 ms more for BASELINE C2's A and B)
-            hipError_t e = h.ldb == (size_t)k ? hipMemcpyAsync(dB, h.B, sizeof(T) * (size_t)n * k, hipMemcpyHostToDevice, up)
-                                              : hipMemcpy2DAsync(dB, sizeof(T) * k, h.B, sizeof(T) * h.ldb, sizeof(T) * k, n, hipMemcpyHostToDevice, up);
-            if (shared) {
-                if (e == hipSuccess) e = hipStreamSynchronize(up);
-                std::lock_guard<std::mutex> sl(shared->mu);
-                shared->ready = true; shared->failed = e != hipSuccess; shared->src = dB; shared->src_device = cx.device;
-                guard.published = true;
-                shared->cv.notify_all();
-            }
-            HIP_CHECK(e);
-        } else {
-            {
-                std::unique_lock<std::mutex> sl(shared->mu);
-                shared->cv.wait(sl, [&] { return shared->ready; });
-                if (shared->failed) throw RmError{RM_ERR_HIP, "upload of the item factors failed on the first device"};
-            }
-            enable_peer_access(cx.device, shared->src_device);
-            HIP_CHECK(hipMemcpyPeerAsync(dB, cx.device, shared->src, shared->src_device, sizeof(T) * (size_t)n * k, up));
-            HIP_CHECK(hipStreamSynchronize(up));                      // the source buffer is shard 0's: tell it when we are done with it
-            guard.reported = true;
-            shared->copy_done();
-        }
-    };
-    if (m <= 0) { upload_items(); HIP_CHECK(hipStreamSynchronize(up)); return; }
+    if (m <= 0) { items.run(dB, cx.device, up); HIP_CHECK(hipStreamSynchronize(up)); return; }
     // this range's users: factors, CSR rows with the index pointers rebased to the range
     const long long tr0 = h.trp[u0], te0 = h.tep[u0];
     const long long nnz_tr = (long long)h.trp[u1] - tr0, nnz_te = (long long)h.tep[u1] - te0;
@@ -1713,40 +1832,8 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
         d_pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
         d_status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
     }
-    // largest batch: ~0.4 s of device work at the rate the sweep sustains (2 n k flop per user), whole user blocks
-    const double rate = std::is_same<T, float>::value ? 6.0e13 : 2.5e13;
-    double bu = 0.4 * rate / (2.0 * (double)n * (double)k);
     const bool forced = g_sw.batch_users > 0;                        // tests: equal batches of this size
-    if (forced) bu = g_sw.batch_users;
-    long long batch = (long long)std::min<double>(std::max(bu, 1024.0), 2.0e9);
-    batch = (batch + 1023) / 1024 * 1024;
-    // k_metrics > 256: the lane buffers when they fit at all (run(): want_lane; one block's worth per 4 GU users on top of the grid's
-    // floor -- lane_blocks_bound), sized so that run() finds every batch fitting; else score rows (ext_topk)
-    const long long lane_blocks = K > 256 && lane_lists_possible<T>(K) ? lane_budget_bytes(ws) * 3 / 4 / lane_list_bytes<T>(K, 1) - lane_blocks_bound<T>(0) : 0;
-    if (lane_blocks >= 8) batch = std::max<long long>(1024, std::min<long long>(batch, lane_blocks * 4 * Prec<T>::GU / 1024 * 1024));
-    else if (K > 256) {                                            // one score row per user of the batch (run(): ext_topk),
-        const long long row = (((long long)n + 191) / 192 * 192) * (long long)sizeof(T);    // with a margin for what run() allocates first
-        batch = std::max<long long>(1, std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row));
-    }
-    // batch boundaries: a first batch of a QUARTER of the users (whole kilo-users) when the range is large enough for the pipeline to
-    // matter -- its upload is the only one nothing hides --, then three times the batch before (its upload hides behind the batch
-    // before, whose kernels take ~2.5 x as long per user as the copy), at most `batch` users.  BASELINE C2: 34,816 + 103,677 users.
-    // Every batch pays the fixed parts of preparation and finalisation again and its plan only comes back when the sweep in front
-    // of it has drained, so fewer batches win once the first upload is paid for: round 5 (preparation 0.88 -> 0.56 ms) 9.6 ms per
-    // call against 9.9 with (1/8, 3/8, 1/2), and with the tie noise 10.3 against 10.85 (one batch fewer for the exact pass to
-    // wait behind; `profiles/r5_host_entry.txt`).  Round 3, when a batch's fixed parts cost twice as much: (1/8, 3/8, 1/2) 10.4,
-    // (1/4, 3/4) 10.6, without the second context 11.7 (`profiles/r3_host_entry.txt`).
-    std::vector<long long> cuts{0};
-    {
-        const int r0 = g_sw.ramp > 0 ? std::max(2, g_sw.ramp) : 4;    // (RM_DEBUG_RAMP, A/B timing: another first fraction; default: a quarter)
-        long long next = (forced || m <= 16384) ? batch : std::min<long long>(batch, std::max<long long>(8192, ((long long)m / r0 + 1023) / 1024 * 1024));
-        while (cuts.back() < m) {
-            long long b1 = std::min<long long>(m, cuts.back() + next);
-            if (m - b1 < 2048 && m - cuts.back() <= batch) b1 = m;                  // no crumb at the end
-            cuts.push_back(b1);
-            next = forced ? batch : std::min<long long>(batch, next * 3);
-        }
-    }
+    const std::vector<long long> cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K), forced);
     const int n_batches = (int)cuts.size() - 1;
     long long mb_max = 0;
     for (int bi = 0; bi < n_batches; bi++) mb_max = std::max(mb_max, cuts[bi + 1] - cuts[bi]);
@@ -1778,14 +1865,14 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     // slice of `range_flag`; ONE exact pass over the flagged users of the whole range follows the last batch.  (Per batch, the
     // exact pass costs two waits on the host -- for the flags, for its own plan -- during which the next batch is not enqueued:
     // 14.6 ms against 10.2 without noise at BASELINE C2, profiles/r4_host_entry.txt.)  Not with the ranking outputs of rm_rank_*.
-    const bool range_noise = h.noise && std::is_same<T, float>::value && n_batches > 1 && !h.topk_idx && !RM_ABL_NOISE_OFF &&
+    const bool range_noise = h.noise && std::is_same<T, float>::value && n_batches > 1 && !h.topk_idx &&
                              !g_sw.noise_per_batch;
     int *range_flag = nullptr, *range_snap = nullptr;
     // ... and the users flagged by the time the LAST batch launches its sweep -- every user with a test item in the noise zone, in
     // practice all of them -- are evaluated exactly BESIDE that sweep on a context of their own (`besides` below), as the device entry
     // does (run_call); what remains behind the last batch is the host-side scatter of their values, and an exact pass over the few
     // users only a batch's k_finalize flagged (a top-K score in the zone), usually none
-    const bool beside_last = range_noise && !g_sw.no_noise_beside_last;
+    const bool beside_last = range_noise;
     if (range_noise) {
         range_flag = (int *)ws.get("noise_flag_range", sizeof(int) * (size_t)m);
         HIP_CHECK(hipMemsetAsync(range_flag, 0, sizeof(int) * (size_t)m, up));      // (in front of batch 0's rows: every batch waits for its rows' event)
@@ -1816,8 +1903,8 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     const auto t_start = std::chrono::steady_clock::now();
     auto stamp = [&](const char *what) { if (trace) stamps.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count()); };
     // shard 0 sends the item factors first (the other shards are waiting for them); the others send their own rows first
-    if (!shared || shard == 0) { upload_items(); stamp("items enqueued"); upload_users(0); }
-    else { upload_users(0); upload_items(); HIP_CHECK(hipEventRecord(cx.up_ev[0], up)); }
+    if (!shared || shard == 0) { items.run(dB, cx.device, up); stamp("items enqueued"); upload_users(0); }
+    else { upload_users(0); items.run(dB, cx.device, up); HIP_CHECK(hipEventRecord(cx.up_ev[0], up)); }
     stamp("batch 0 rows enqueued");
     // (`tail`: what the fp32 tie noise still has to look at once the batch is through, run_call; `copy_out`: the batch's device-to-host
     // copies, enqueued behind the batch and once more when the tail rewrote outputs)
@@ -2065,16 +2152,7 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
         throw;
     }
     HIP_CHECK(hipStreamSynchronize(up));                              // `rb` and the caller's arrays go out of use (also after an interrupt)
-    if (trace) {
-        std::string line = "rm host trace (" + std::to_string(n_batches) + " batches, ms):";
-        for (auto &st : stamps) { char buf[96]; snprintf(buf, sizeof buf, " [%s %.3f]", st.first, st.second); line += buf; }
-        fprintf(stderr, "%s\n", line.c_str());
-        std::lock_guard<std::mutex> tl(g_run_trace.mu);
-        std::string l2 = "rm run trace (ms since the library was loaded):";
-        for (auto &pt : g_run_trace.pts) { char buf[112]; snprintf(buf, sizeof buf, " [%s %.3f]", pt.first, pt.second); l2 += buf; }
-        fprintf(stderr, "%s\n", l2.c_str());
-        g_run_trace.pts.clear();
-    }
+    if (trace) print_host_trace(n_batches, stamps);
 }
 
 // (m == 0 is not an error: the reference's loop over users, src/recometrics.hpp:428-437, simply does not run; the entry
@@ -2262,14 +2340,6 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
 
 } // namespace
 
-#ifdef RM_CSTATS
-extern "C" int rm_debug_stats_collect(unsigned long long *out, int reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(rm::g_cstats), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(rm::g_cstats), z, sizeof(z)); }
-    return 0;
-}
-#endif
 // =====================================================================================================================
 // C-ABI
 // =====================================================================================================================

@@ -10,13 +10,6 @@
 
 namespace rm {
 
-#ifdef RM_STATS
-__device__ unsigned long long g_stats[16];      // timing builds only (scratch/build_abl.py)
-#define RM_SEL_STAT(IDX, VAL) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_stats[IDX], (unsigned long long)(VAL)); } while (0)
-#else
-#define RM_SEL_STAT(IDX, VAL) do {} while (0)
-#endif
-
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -367,7 +360,6 @@ __device__ __forceinline__ void lane_select(S *sc, int *it, int &cnt, const int 
             if (h1 - l1 > 1) { if (a1 == tg1) { l1 = m1; h1 = m1 + 1; } else if (a1 > tg1) l1 = m1; else h1 = m1; }
             if (h2 - l2 > 1) { if (a2 == tg2) { l2 = m2; h2 = m2 + 1; } else if (a2 > tg2) l2 = m2; else h2 = m2; }
             if (h3 - l3 > 1) { if (a3 == tg3) { l3 = m3; h3 = m3 + 1; } else if (a3 > tg3) l3 = m3; else h3 = m3; }
-            RM_SEL_STAT(1, 1);
             sdone = sdone || (h1 - l1 <= 1 && h2 - l2 <= 1 && h3 - l3 <= 1);
             if (sp >= 7) sdone = true;              // (seven halvings of the value range: the probes only say where the first pass looks)
         }
@@ -391,7 +383,6 @@ __device__ __forceinline__ void lane_select(S *sc, int *it, int &cnt, const int 
             k1 = lo + (q ? q : (Key)1); k2 = lo + (q ? 2 * q : (Key)1); k3 = lo + (q ? 3 * q : (Key)1);
         }
         int c1, c2, c3;
-        RM_SEL_STAT(0, 1);
         lane_count3<S>(sc, cend, ord_unkey(k1), ord_unkey(k2), ord_unkey(k3), c1, c2, c3);
         c1 = L::usum(c1); c2 = L::usum(c2); c3 = L::usum(c3);
         if (!done) {
@@ -409,7 +400,6 @@ __device__ __forceinline__ void lane_select(S *sc, int *it, int &cnt, const int 
     const bool below = active && lo == lo0 && !unbounded;
     bool own_short = false;
     if (wave_any(below)) {
-        RM_SEL_STAT(3, 1);
         int c0 = 0;
         for (int i = 0; i < cend; i++) { const S x = L::load(sc + (size_t)i * L::SS); c0 += x >= T; }
         c0 = L::usum(c0);
@@ -420,7 +410,6 @@ __device__ __forceinline__ void lane_select(S *sc, int *it, int &cnt, const int 
     const bool ties = active && !own_short && cT > K + slack;
     int item_max = IDX_EMPTY;
     if (wave_any(ties)) {
-        RM_SEL_STAT(2, 1);
         const S above = ord_unkey(lo + 1);
         int ngt = 0;
         for (int i = 0; i < cend; i++) { const S x = L::load(sc + (size_t)i * L::SS); ngt += x >= above; }

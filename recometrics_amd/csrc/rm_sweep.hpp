@@ -25,8 +25,6 @@
 //                  behind gets the higher issue priority (s_setprio), so that all reach the end of the range together.
 //   grid           two levels (rm_launch.hpp): whole rounds of blocks with n_splits item ranges, then the cheapest user
 //                  blocks cut into tail_splits smaller ranges that fill the last round.
-//   diagnostics    the RM_ABL_* macros compile single stages out (wrong results, timing only): they are how the cost
-//                  breakdown in DESIGN.md was measured and are never defined in a product build.
 #pragma once
 #include "rm_device.hpp"
 #include "rm_list.hpp"
@@ -89,25 +87,6 @@ __device__ __forceinline__ void auc_pass(const float (&v)[16], unsigned pos_addr
     // root alone, 0 = every level reads its pivot from LDS (A/B: profiles/r4_ab_c2.txt)
     constexpr int TOP = J >= 2 ? RM_TOP_LEVELS : 0;
     unsigned long long mk0, mk1, mk2;                          // lane masks in SGPR pairs, in rotation
-#ifdef RM_ABL_LUT
-    // timing model of a table-driven start (wrong results): 3 (4 at depth 6) vector instructions and one byte read per score
-    // stand in for all but the last ABL_LEVELS levels
-    constexpr int ABL_LEVELS = J >= 6 ? 3 : (J >= 4 ? 2 : J);
-    if (J >= 3) {
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            float x; unsigned qa, f;
-            asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(x) : "v"(v[r]), "v"(piv_lo), "v"(piv_hi));
-            if (J >= 6) asm volatile("v_min_f32 %0, %1, %2" : "=v"(x) : "v"(x), "v"(piv_root));
-            asm volatile("v_cvt_pk_u8_f32 %0, %1, 0, %2" : "=v"(qa) : "v"(x), "v"(pos_addr));
-            asm volatile("ds_read_u8 %0, %1" : "=v"(f) : "v"(qa));
-            at[r] = f;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        #pragma unroll
-        for (int r = 0; r < 16; r++) asm volatile("v_lshl_add_u32 %0, %1, 7, %2" : "=v"(at[r]) : "v"(at[r] & 7u), "v"(pos_addr));
-    } else
-#endif
     if (TOP == 2) {
         constexpr unsigned Q = 128u << (J >= 2 ? J - 2 : 0);   // a quarter of the table
         const unsigned a1 = pos_addr | Q, a2 = pos_addr | (2 * Q), a3 = pos_addr | (3 * Q);
@@ -139,19 +118,10 @@ __device__ __forceinline__ void auc_pass(const float (&v)[16], unsigned pos_addr
         #pragma unroll
         for (int r = 0; r < 16; r++) at[r] = pos_addr;
     }
-#ifdef RM_ABL_LUT
-    constexpr int FIRST_ST = J >= 3 ? (1 << (ABL_LEVELS - 1)) : (J - TOP > 0 ? (1 << (J - TOP - 1)) : 0);
-#else
     constexpr int FIRST_ST = J - TOP > 0 ? (1 << (J - TOP - 1)) : 0;
-#endif
     #pragma unroll
     for (int st = FIRST_ST; st >= 1; st >>= 1) {
         float pv[16];
-#ifdef RM_ABL_NOLDS_SEARCH
-        // timing only (wrong results): the pivots come from a register move instead of LDS -- what the reads' latency costs
-        #pragma unroll
-        for (int r = 0; r < 16; r++) asm volatile("v_mov_b32 %0, %1" : "=v"(pv[r]) : "v"(at[r]));
-#else
         #pragma unroll
         for (int r = 0; r < 16; r++) pv[r] = *(LdsF32Ptr)(at[r] + (st - 1) * 128);
         #pragma unroll
@@ -167,7 +137,6 @@ __device__ __forceinline__ void auc_pass(const float (&v)[16], unsigned pos_addr
             }
         }
     }
-#endif
     // exact score tie with a positive (row `base` is the first positive not below s; the table has one +inf pad
     // row, so the read is always in range): the total order is (score desc, item asc), i.e. the candidate also
     // outranks the equal-scored positives with a LARGER item id.  Rare; positives' item ids stay in HBM.  Detection: the
@@ -193,11 +162,7 @@ __device__ __forceinline__ void auc_pass(const float (&v)[16], unsigned pos_addr
     const float m0 = hw_absmin3(df[0], df[1], df[2]), m1 = hw_absmin3(df[3], df[4], df[5]), m2 = hw_absmin3(df[6], df[7], df[8]);
     const float m3 = hw_absmin3(df[9], df[10], df[11]), m4 = hw_absmin3(df[12], df[13], df[14]);
     const float dmin = hw_absmin3(hw_absmin3(m0, m1, m2), hw_absmin3(m3, m4, df[15]), df[15]);
-#ifdef RM_ABL_NOTIE
-    if (false) {
-#else
     if (wave_any(dmin == 0.f)) {
-#endif
         // (the tile's first item made opaque INSIDE the rare branch: left visible, the sixteen item ids of the walk are loop-invariant
         // code the compiler hoists in front of the switch over the table depths -- 24 v_or per tile on the common path, 6 % of the
         // sweep's vector instructions at BASELINE C2, for a branch one tile in forty takes)
@@ -229,16 +194,6 @@ __device__ __forceinline__ void auc_pass(const float (&v)[16], unsigned pos_addr
         asm volatile("ds_add_u32 %0, %1 offset:%2" :: "v"(at[r]), "v"(one), "n"(HIST_DELTA) : "memory");
 }
 
-#ifdef RM_STATS
-#ifdef RM_STATS_TIME_ONLY
-#define RM_STAT(i, x) do {} while (0)
-#else
-#define RM_STAT(i, x) do { if (lane == 0) atomicAdd(&g_stats[i], (unsigned long long)(x)); } while (0)
-#endif
-#else
-#define RM_STAT(i, x) do {} while (0)
-#endif
-
 // LMODE (rm_device.hpp) is a template parameter, not a run-time switch: the three list schemes together do not fit the
 // register budget of the 128-factor kernel without spilling.
 
@@ -259,9 +214,6 @@ void k_sweep(SweepArgs a)
     static_assert(SPEC >= 0 && SPEC <= 2 && !(SPEC && DUMP), "unknown specialisation");
     const bool f_bits = SPEC == 1 ? true : (SPEC == 2 ? false : a.train_bits != nullptr);
     const bool f_nan = SPEC ? false : a.check_nan != 0, f_noise = SPEC ? false : a.noise_E != nullptr, f_ext = SPEC ? false : a.ext_topk != 0;
-#ifdef RM_STATS
-    const unsigned long long prof_t0 = __builtin_readcyclecounter();
-#endif
     constexpr int NWAVES = 4 * NSUB, THREADS = 64 * NWAVES;
     constexpr bool LLDS = LMODE == LM_LDS;
     constexpr bool buffered = LMODE == LM_HBM_APPEND;
@@ -319,11 +271,7 @@ void k_sweep(SweepArgs a)
     // ---- per-lane user state ----
     const int user = slot_ok ? a.slot_user[slot] : -1;
     const bool primary = slot_ok && a.slot_chunk[slot] == 0;
-#ifdef RM_ABL_TOPK_NOHIT
-    float thr = pos_inf_f();
-#else
     float thr = primary ? neg_inf_f() : nan_sentinel_f();        // NaN threshold: "v >= thr" never true
-#endif
     float vmax = neg_inf_f(), vmin = pos_inf_f();
     bool track_min = true;                                      // wave-uniform (see the validity scan of the epilogue)
     unsigned long long nanmask = 0;
@@ -418,10 +366,8 @@ void k_sweep(SweepArgs a)
         merged = true;
         const int pc = __shfl_xor(pcnt, 32);                      // the partner lane's count (same user, other item rows)
         const int lim = h == 0 ? (pcnt > pc ? pcnt : pc) : 0;
-        RM_STAT(5, 1);
         list_acquire();
         for (int i = 0; wave_any(i < lim); i++) {
-            RM_STAT(6, 1);
             if (h == 0) {
                 if (i < pcnt) offer_key(Pp[i * WAVE]);
                 if (i < pc) offer_key(Pp[i * WAVE + 32]);
@@ -475,11 +421,7 @@ void k_sweep(SweepArgs a)
     #pragma unroll
     for (int j = 0; j < STAGE_PIECES; j++) stage_voff[j] = (unsigned)(((gi + 4 * j) * 2 * TILE + h * TILE + sub * 32 + ul) * 16);
     auto stage = [&](int unit, int buf) {                     // unit = tile * NC + chunk: contiguous in the packed image
-#ifdef RM_ABL_SAME_TILE
-        const char *src = (const char *)a.Bp + (size_t)(unit & 7) * (BUF_F4 * 16);
-#else
         const char *src = (const char *)a.Bp + (size_t)unit * (BUF_F4 * 16);
-#endif
         // Issued through inline asm on purpose: with the builtin the compiler assumes every later LDS read may alias
         // the DMA's LDS write and puts s_waitcnt vmcnt(0) in front of the MFMA operand reads, which serialises the
         // prefetch with the step it was meant to overlap.  The wait that matters is the explicit one before the
@@ -497,7 +439,7 @@ void k_sweep(SweepArgs a)
 
     // ---- MFMA: 32 items (registers) x 32 users (lanes), k in index order ----
     // EARLY ARRIVAL (kernels with resident user factors: one unit per tile): see do_mfma
-#if !defined(RM_FULL_BARRIER) && !defined(RM_ABL_NO_BARRIER)
+#ifndef RM_FULL_BARRIER
     constexpr bool EARLY_ARRIVE = AF_RESIDENT && NG >= 4 && NG % 2 == 0;      // (an odd group count arrives behind its last matrix instruction)
 #else
     constexpr bool EARLY_ARRIVE = false;
@@ -577,9 +519,6 @@ void k_sweep(SweepArgs a)
     // ---- epilogue of one 32-item x 32-user tile ----
     // last key this lane published / observed (lanes that own no list never follow the shared bound: all ones, so that the test
     // below is ONE compare whose lane mask the scalar unit can look at)
-#ifdef RM_STATS
-    unsigned long long st_sel = 0, st_bar = 0, st_app = 0; unsigned st_nsel = 0;
-#endif
     unsigned thr_pub = primary ? 0u : 0xffffffffu;
     // SELECT WHILE WAITING: a selection is ~100 us of memory traffic during which the three other waves of the sub-tile's barrier
     // domain run into the next barrier and wait -- each wave's three selections per item range cost the domain twelve stalls
@@ -602,17 +541,11 @@ void k_sweep(SweepArgs a)
     unsigned lb_trig_now = sub == 0 ? lb_trigger : (sub == 1 ? (unsigned)(lane_cap - lane_cap / 4) << 9 : lb_half);
     lb_trig_now = lb_trig_now < lb_trigger ? lb_trig_now : lb_trigger;
     auto lane_bounds = [&]() {
-#ifdef RM_STATS
-        const unsigned long long lb_t0 = __builtin_readcyclecounter();
-#endif
         // (no entry of the user exceeds the larger of its two lanes' running maxima -- unless the tie noise moved it)
         const float hi_hint = f_noise ? pos_inf_f() : LaneSel<float>::umax(vmax);
         const LaneSelResult<float> sr = lane_select_call<float>((float *)lb_scores + 2 * lane, (int *)lb_scores + 2 * lane + 1, (int)(lb_off >> 9), K, primary, thr, hi_hint, n);
         const float t_new = sr.thr; const unsigned kk = sr.kth_key;
         lb_off = ((unsigned)sr.cnt << 9) | ((unsigned)lane * 8u);
-#ifdef RM_STATS
-        st_nsel++; st_sel += __builtin_readcyclecounter() - lb_t0;
-#endif
         if (kk) {
             thr = t_new;
             if (h == 0 && kk > thr_pub) atomicMax(a.thr_shared + slot, kk);
@@ -642,11 +575,7 @@ void k_sweep(SweepArgs a)
         }
         // (1) train-item / out-of-range masking (reference :491-497) + NaN detection (:517-518).  The NaN scan is
         // skipped when the host proved that no partial sum can overflow or be non-finite (k * max|A| * max|B| bound).
-#ifdef RM_ABL_NO_MASK
-        const bool slow = false;
-#else
         const bool slow = !f_bits && (wave_any(nt < sb + 32) || (sb + 32 > n));
-#endif
         if (f_bits) {                                             // masked in the accumulators already (do_mfma)
             if (f_nan) {
                 const int mb = (int)tile_bits;
@@ -721,7 +650,6 @@ void k_sweep(SweepArgs a)
             for (int q4 = 0; q4 < 4; q4++) qmax[q4] = hw_max3(v[4 * q4], v[4 * q4 + 1], hw_max(v[4 * q4 + 2], v[4 * q4 + 3]));
             tmax = hw_max3(qmax[0], qmax[1], hw_max(qmax[2], qmax[3]));
         }
-#ifndef RM_ABL_NO_TOPK
         // (3) streaming top-K: anything at or above the user's current K-th best is offered to the list (:537-540).
         // One compare per tile on the lane's tile maximum; the per-score work happens only in the rare hit path.
         // Lanes u (h = 0) and u + 32 (h = 1) carry two item rows of the same user: the h = 0 lane owns the list and
@@ -736,10 +664,6 @@ void k_sweep(SweepArgs a)
         }
         // (a.ext_topk: k_metrics beyond the lists' reach -- every lane streams its scores and k_select_topk picks the top-K)
         const unsigned long long cm = f_ext ? 0ull : __ballot(tmax >= thr);
-        RM_STAT(0, 1); RM_STAT(1, cm != 0); RM_STAT(2, __popcll(cm));
-#ifdef RM_STATS
-        const unsigned long long ap_t0 = __builtin_readcyclecounter();
-#endif
         if (buffered) {
             // K > 32: every lane appends its own candidates to its own buffer (rm_list.hpp): per score register a compare, one
             // 8-byte store under the lane mask, an add -- a register quad without a candidate in any lane is skipped with one test
@@ -763,9 +687,6 @@ void k_sweep(SweepArgs a)
                     }
                 }
             }
-#ifdef RM_STATS
-            st_app += __builtin_readcyclecounter() - ap_t0;
-#endif
         } else
         if (cm && pend_cap) {
             unsigned ov = 0;                                    // score registers that did not fit the lane's buffer
@@ -777,7 +698,6 @@ void k_sweep(SweepArgs a)
                     // (the lane test alone: wrapped in a wave-level test it compiled into five scalar instructions in front of the
                     // same exec-mask branch)
                     const bool c = v[r] >= thr;
-                    RM_STAT(3, __ballot(c) != 0); RM_STAT(4, __popcll(__ballot(c)));
                     if (c) {
                         if (pcnt < pend_cap) { Pp[pcnt * WAVE] = pack_key(v[r], sb + mfma32_row(r, h)); pcnt++; }
                         else ov |= 1u << r;
@@ -808,7 +728,6 @@ void k_sweep(SweepArgs a)
             for (int r = 0; r < 16; r++) {
                 const unsigned long long hitm = __ballot(v[r] >= thr);
                 if (hitm) {
-                    RM_STAT(3, 1); RM_STAT(4, __popcll(hitm));
                     // the partner's score is only fetched when a lane of the upper half has a candidate
                     const float other = (hitm >> 32) ? __shfl_xor(v[r], 32) : nan_sentinel_f();
                     if (h == 0 && primary) {
@@ -833,8 +752,6 @@ void k_sweep(SweepArgs a)
                 thr_pub = kk > thr_pub ? kk : thr_pub;
             }
         }
-#endif
-#ifndef RM_ABL_NO_AUC
         // (4) AUC rank counting (replaces the full sort of :552 + the walk of :795-865)
         if (wave_streams) {
             if (stream_lane) {                                  // registers 4q .. 4q+3 are four consecutive items
@@ -854,7 +771,6 @@ void k_sweep(SweepArgs a)
                 default: break;
             }
         }
-#endif
         // K > 32: some lane is a tile away from a full buffer -> every user of the wave raises its bound (at the END of the
         // epilogue: the tile's scores are dead, their registers hold the selection's loads in flight)
         if (buffered) {
@@ -899,26 +815,16 @@ void k_sweep(SweepArgs a)
     // the shared K-th-best bound is read one tile ahead: its load is drained by the wait after the next MFMA phase,
     // never by a wait in the middle of an epilogue (which would also wait for the tile prefetch)
     auto load_thr = [&]() -> unsigned {
-#ifdef RM_ABL_NO_THRSEEN
-        return 0u;
-#else
         return (primary && !DUMP) ? __hip_atomic_load(a.thr_shared + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#endif
     };
     unsigned thr_seen = load_thr();                             // (the seeded bound counts from the first tile on)
-#ifdef RM_STATS
-    const unsigned long long prof_t1 = __builtin_readcyclecounter();
-#endif
     for (int i = 0; i < ntiles; i++) {
         unsigned thr_next = thr_seen;
         for (int c = 0; c < NC; c++) {
             const int unit = i * NC + c;
-#if !defined(RM_FULL_BARRIER) && !defined(RM_ABL_NO_BARRIER)
+#ifndef RM_FULL_BARRIER
             if (unit > 0) {                                                       // wait half of the split barrier
                 const unsigned target = SYNC_WAVES * (unsigned)unit;
-#ifdef RM_STATS
-                const unsigned long long bw_t0 = __builtin_readcyclecounter();
-#endif
                 while (__hip_atomic_load(arrive, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) {
                     __builtin_amdgcn_s_sleep(1);
                     if (buffered && !DUMP) {                        // a partner is selecting: this wave's turn too (see lane_bounds)
@@ -926,11 +832,7 @@ void k_sweep(SweepArgs a)
                         if (ep != sel_seen) { sel_seen = ep; if (wave_any(lb_off >= lb_half)) { lane_bounds(); lb_trig_now = lb_trigger; } }
                     }
                 }
-#ifdef RM_STATS
-                st_bar += __builtin_readcyclecounter() - bw_t0;
-#endif
             }
-#ifndef RM_ABL_NO_PRIO
             // The sub-tile domains progress independently, and the instruction arbiter serves the oldest wave first: left
             // alone, sub-tile 0 finishes its range ~20 % ahead of sub-tile 2 and the block ends on one wave per SIMD.
             // Every fourth unit a wave compares its domain's arrival counter with the others' and sets its issue priority:
@@ -947,29 +849,20 @@ void k_sweep(SweepArgs a)
                 else __builtin_amdgcn_s_setprio(1);
             }
 #endif
-#endif
-#ifndef RM_ABL_NO_STAGE
             if (unit + 1 < nunits) stage(t0 * NC + unit + 1, (unit + 1) & 1);   // that buffer was last read one unit ago
-#endif
             if (c == 0) thr_next = load_thr();
             // the NEXT tile's word of the dense train row (the accumulators start from it): in flight during the MFMA phase,
             // drained by the wait at the arrive point
             unsigned bits_next = 0u;
             if (c == NC - 1 && tb_row && i + 1 < ntiles) { tb_idx += NSUB; bits_next = a.train_bits[tb_idx]; }      // (shifted once it has landed, below)
-#ifndef RM_ABL_NO_MFMA
             do_mfma(acc, unit & 1, c, tile_bits);
-#endif
-#if !defined(RM_FULL_BARRIER) && !defined(RM_ABL_NO_BARRIER)
-#ifndef RM_ABL_NO_ARRIVE_WAIT
+#ifndef RM_FULL_BARRIER
             __builtin_amdgcn_s_waitcnt(WAIT_VMCNT0);                              // arrive half: the next unit's DMA share has landed
-#endif
             // (a bare ds_add: the builtin goes through the compiler's wave-aggregation of atomics, a dozen instructions per tile;
             // the wave's LDS operations are issued in order, so the arrival cannot overtake its operand reads)
             if (!EARLY_ARRIVE && lane == 0) asm volatile("ds_add_u32 %0, %1" :: "v"((unsigned)(__UINTPTR_TYPE__)arrive), "v"(1u) : "memory");
 #endif
-#ifndef RM_ABL_NO_EPI
             if (c == NC - 1) do_epi(acc, t0 + i, thr_seen, tile_bits);
-#endif
             if (c == NC - 1) tile_bits = bits_next >> (4 * h);
 #if defined(RM_FULL_BARRIER)
             __builtin_amdgcn_s_waitcnt(WAIT_VMCNT0);                              // the DMA of the next unit has landed
@@ -979,19 +872,8 @@ void k_sweep(SweepArgs a)
         thr_seen = thr_next;
     }
     if (DUMP) return;
-#ifdef RM_STATS
-    const unsigned long long prof_t2 = __builtin_readcyclecounter();
-#endif
     if (pend_cap) merge_pending();
-#ifdef RM_STATS
-    if (lane == 0 && gi == 0 && sub == 1) atomicAdd(&g_stats[14], prof_t2 - prof_t1);
-    if (lane == 0 && gi == 0 && sub == 2) atomicAdd(&g_stats[15], prof_t2 - prof_t1);
-    if (lane == 0 && gi == 3 && sub == 0) atomicAdd(&g_stats[8], prof_t2 - prof_t1);
-#endif
     if (LLDS) __syncthreads();                                  // every wave of the group has merged into the shared list
-#ifdef RM_STATS
-    if (threadIdx.x == 0) atomicAdd(&g_stats[9], __builtin_readcyclecounter() - prof_t2);
-#endif
 
     // ---- write this wave's partial: top-K list, validity stats, AUC sum; flush the LDS histogram ----
     // (the kernel arguments of this part -- six pointers and a handful of counts -- are read AGAIN, from the kernarg segment: loaded at
@@ -1073,14 +955,6 @@ void k_sweep(SweepArgs a)
         }
     }
     }
-#ifdef RM_STATS
-    if (lane == 0) { atomicAdd(&g_stats[5], (unsigned long long)st_nsel); atomicAdd(&g_stats[6], st_sel); atomicAdd(&g_stats[7], st_bar); atomicAdd(&g_stats[4], st_app); }
-    if (threadIdx.x == 0) {
-        const unsigned long long prof_t3 = __builtin_readcyclecounter();
-        atomicAdd(&g_stats[10], prof_t1 - prof_t0); atomicAdd(&g_stats[11], prof_t2 - prof_t1); atomicAdd(&g_stats[12], prof_t3 - prof_t2);
-        atomicAdd(&g_stats[13], (unsigned long long)ntiles);
-    }
-#endif
 }
 
 } // namespace rm

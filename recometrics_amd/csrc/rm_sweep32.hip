@@ -24,11 +24,3 @@ int launch_sweep32(bool auc, bool dump, int lmode, int nsub, int NG, dim3 grid, 
 
 } // namespace rm
 
-#ifdef RM_STATS
-extern "C" int rm_debug_stats(unsigned long long *out, int reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(rm::g_stats), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(rm::g_stats), z, sizeof(z)); }
-    return 0;
-}
-#endif

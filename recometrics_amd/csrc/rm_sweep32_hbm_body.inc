@@ -18,11 +18,3 @@ int RM_CAT(launch_sweep32_hbm_s, RM_SPEC)(bool auc, int lmode, int NG, dim3 grid
 
 } // namespace rm
 
-#if defined(RM_STATS) && RM_SPEC == 1
-extern "C" int rm_debug_stats_hbm(unsigned long long *out, int reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(rm::g_stats), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(rm::g_stats), z, sizeof(z)); }
-    return 0;
-}
-#endif

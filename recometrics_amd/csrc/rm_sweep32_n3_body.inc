@@ -15,12 +15,3 @@ int RM_CAT(launch_sweep32_n3_s, RM_SPEC)(bool auc, int NG, dim3 grid, size_t lds
 
 } // namespace rm
 
-#ifdef RM_STATS
-// (instrumented timing builds only, scratch/build_abl.py: the cycle counters of whichever specialisation was built with RM_STATS)
-extern "C" int rm_debug_stats_n3(unsigned long long *out, int reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(rm::g_stats), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(rm::g_stats), z, sizeof(z)); }
-    return 0;
-}
-#endif

@@ -28,12 +28,3 @@ dt, sw, pr, fi, tm = measure(torch, dist, binding, p, steps, 1, 1, None)
 tf = 2.0 * n * k * m / (sw * 1e-3) / 1e12
 peak = 157.3 if dtype == np.float32 else 78.6
 print(json.dumps({"workload": wl, "users": m, "users_per_s": m * steps / dt, "sweep_ms": sw, "prep_ms": pr, "fin_ms": fi, "TF": tf, "frac": tf / peak, "tm": tm}))
-if os.environ.get("RM_PRINT_STATS"):
-    import ctypes
-    lib = binding.load()
-    lib = ctypes.CDLL(os.environ["RECOMETRICS_HIP_LIB"])
-    buf = (ctypes.c_ulonglong * 16)()
-    getattr(lib, os.environ.get("RM_STATS_FN", "rm_debug_stats"))(buf, 1)
-    runs = steps + 1
-    names = ["full_passes", "sample_passes", "tie_events", "below_events", "append_cycles", "merges_or_selections", "merge_iters_or_selection_cycles", "barrier_wait_cycles", "cyc_loop_g3s0", "cyc_wait_sync", "cyc_prologue", "cyc_loop", "cyc_epilogue", "tiles", "cyc_loop_sub1", "cyc_loop_sub2"]
-    print(json.dumps({nm: buf[i] / runs for i, nm in enumerate(names)}))
