@@ -266,13 +266,15 @@ __global__ void k_export_rank(int m, int K, const Entry<S> *merged, int *topk_id
 }
 
 __global__ void k_export_pos_rank(long long nnz, int m, const int *test_p, const int *flags, const int *pos_order,
-                                  const long long *rank_sorted, long long *pos_rank, int have_ranks)
+                                  const long long *rank_sorted, long long *pos_rank, int have_ranks, const int *status)
 {
     // one thread per user row (rows are short).  Users that were never ranked (skipped, or NDCG-only) have no entry in
-    // pos_order -- whatever the workspace held before -- and report rank 0.
+    // pos_order -- whatever the workspace held before -- and report rank 0.  So does a user that k_finalize found invalid
+    // (status 1: every candidate score the same, an infinite one): k_finalize clears its rows of rank_sorted, but the ranks of a
+    // STREAMED user are still being counted on the side stream while it runs (auc_defer_slot0) and landed on top of the zeros.
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= m || (flags[u] & UF_SKIP)) return;
-    const bool ranked = have_ranks && (flags[u] & UF_ACTIVE) && !(flags[u] & UF_ONLY_NDCG);
+    const bool ranked = have_ranks && (flags[u] & UF_ACTIVE) && !(flags[u] & UF_ONLY_NDCG) && !(status && status[u] == 1);
     for (int e = test_p[u]; e < test_p[u + 1]; e++) pos_rank[e] = ranked ? rank_sorted[test_p[u] + pos_order[e]] : 0;
 }
 
@@ -1332,7 +1334,7 @@ struct Pipeline {
             hipLaunchKernelGGL(k_export_rank<T>, dim3(cdiv((long long)m * K, 256)), dim3(256), 0, stream, m, K, merged, c.topk_idx, c.topk_score, flags);
         if (c.pos_rank)           // (per user, never a memset of the whole array: a batch must not clear what other batches wrote)
             hipLaunchKernelGGL(k_export_pos_rank, dim3(cdiv(m, 128)), dim3(128), 0, stream, c.nnz_test, m, c.test_p, flags, pos_order, rank_sorted, c.pos_rank,
-                               (want_auc && n_slots > 0) ? 1 : 0);
+                               (want_auc && n_slots > 0) ? 1 : 0, c.status);
         RM_TRACE_POINT("run: finalisation enqueued");
         HIP_CHECK(hipEventRecord(cx.ev[3], stream));
         HIP_CHECK(hipEventRecord(cx.done, stream));

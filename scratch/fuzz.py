@@ -5,9 +5,9 @@ import numpy as np
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
 from recometrics_amd import _binding as hip
-from recometrics_amd.synth import make_problem
+from recometrics_amd.synth import STRUCTURED_KINDS, make_problem, make_structured
 from oracle.oracle import Oracle
-from test_hip_parity import hip_calc
+from _parity import hip_calc
 from _util import same_bits
 
 hip.load(); oracle = Oracle()
@@ -28,7 +28,12 @@ for it in range(cases):
     if set(metrics) <= {"hit", "rr"}: metrics = metrics + ("p",)                      # deviation D1
     kw = dict(cumulative=bool(rng.random() < 0.3), cold=bool(rng.random() < 0.7), noise=bool(rng.random() < 0.45), metrics=metrics,
               min_items_pool=int(rng.choice([1, 2, 10])), min_pos_test=int(rng.choice([1, 1, 3])), seed=int(rng.choice([1, 7, 2 ** 35 + 3])))
-    pr = make_problem(m, n, k, dtype, mean_c=mean_c, seed=int(rng.integers(1 << 30)))
+    # a third of the draws take ordered / structured scores (synth.make_structured) instead of i.i.d. factors.  `runs` and the
+    # clusters hold exact ties: restatement and device order them by item id alike (this tool never asks the compiled reference)
+    kind = str(rng.choice(STRUCTURED_KINDS)) if rng.random() < 0.34 else "iid"
+    if kind == "outliers" and k < 2: kind = "ascending"
+    if kind == "iid": pr = make_problem(m, n, k, dtype, mean_c=mean_c, seed=int(rng.integers(1 << 30)))
+    else: pr = make_structured(kind, m, n, k, dtype, mean_c=mean_c, seed=int(rng.integers(1 << 30)), variant=str(rng.choice(["spikes", "clusters"])))
     if rng.random() < 0.3:                           # test items that are also train items (never candidates: reference :491-497)
         trp, tri = pr["train"]; tep_, tei_ = pr["test"][:2]
         rows = []
@@ -45,7 +50,7 @@ for it in range(cases):
         dup = rng.random(n) < 0.2
         pr["B"][dup] = pr["B"][rng.integers(0, n, int(dup.sum()))]
     if os.environ.get("FUZZ_VERBOSE"):
-        print("CASE", it, dict(dtype=dtype.__name__, m=m, n=n, k=k, K=K, mean_c=mean_c, **kw), flush=True)
+        print("CASE", it, dict(kind=kind, dtype=dtype.__name__, m=m, n=n, k=k, K=K, mean_c=mean_c, **kw), flush=True)
     try:
         want = oracle.calc(pr["A"], pr["B"], pr["train"], pr["test"], K, dtype=dtype, nthreads=8, **kw)
         got = hip_calc(hip, pr["A"], pr["B"], pr["train"], pr["test"], K, dtype=dtype, **kw)
@@ -76,6 +81,6 @@ for it in range(cases):
         msg = ["exception %r" % (e,)]
     if msg:
         bad += 1
-        print("FAIL", dict(dtype=dtype.__name__, m=m, n=n, k=k, K=K, mean_c=mean_c, **kw), msg, flush=True)
+        print("FAIL", dict(kind=kind, dtype=dtype.__name__, m=m, n=n, k=k, K=K, mean_c=mean_c, **kw), msg, flush=True)
 print("fuzz: %d cases, %d failed, %.1f s" % (cases, bad, time.time() - t0))
 sys.exit(1 if bad else 0)

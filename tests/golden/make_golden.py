@@ -5,7 +5,8 @@ Run in the build container only (needs /root/reference; it is compiled by oracle
 oracle/_ref/librecometrics_ref.so -- canonical build).  The fixtures are
 data: inputs and the reference's outputs.  No reference source is stored.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            # every family
+    python tests/golden/make_golden.py g10_       # only the files whose names start so
 
 Families:
   g1_ndcg_literal   literal cases of the reference's tests/testthat/test-ndcg.R:37-71,:107-124
@@ -16,6 +17,8 @@ Families:
   g6_random_*       random dense blocks, fp32 and fp64, all metrics, single + cumulative, noise off/on
   g7_cold_off       consider_cold_start = False
   g8_dyadic         23-bit dyadic factors (dot products exact in any order)
+  g10_ordered       synth.make_structured: scores ascending / descending in the item id, planted positives (fp32 and fp64), runs of
+                    exact ties (fp64, noise on: the noise orders them), all metrics, single + cumulative, noise off/on
 """
 import json
 import os
@@ -26,10 +29,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from oracle.oracle import METRICS, Reference  # noqa: E402
-from recometrics_amd.synth import make_problem  # noqa: E402
+from oracle.oracle import Oracle  # noqa: E402
+from oracle.ties import tie_pairs_per_user  # noqa: E402
+from recometrics_amd.synth import make_problem, make_structured  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 REF = Reference()
+ONLY = sys.argv[1] if len(sys.argv) > 1 else ""
 
 
 def csr_from_rows(rows, n, vals=None, dtype=np.float64):
@@ -49,6 +55,8 @@ def csr_from_rows(rows, n, vals=None, dtype=np.float64):
 
 def run_case(name, A, B, train, test, variants, dtype):
     """variants: list of dicts of calc kwargs; stores one output set per variant."""
+    if not name.startswith(ONLY):
+        return
     A = np.asarray(A, dtype=dtype)
     B = np.asarray(B, dtype=dtype)
     store = {"A": A, "B": B, "train_p": train[0], "train_i": train[1],
@@ -173,6 +181,25 @@ def main():
     pr = make_problem(m, n, k, f32, mean_c=25, seed=14)
     run_case("g8_dyadic_f32", A, B, pr["train"], pr["test"],
              [dict(k=10, noise=False), dict(k=10, noise=False, cumulative=True, metrics=("p", "ap", "ndcg", "rr"))], f32)
+
+    # ---- g10: ordered and structured scores (synth.make_structured) ---------------------------------
+    # The fixtures are compared bit for bit, ROC-AUC included, and exact ties are ordered by libstdc++'s sort in the reference: a
+    # case must not hold a user with an exact tie on a positive (oracle/ties.py) -- the seed moves on until it has none.  `runs` is
+    # nothing but ties: recorded with the noise on only, on a ramp small enough (2^-8) for Uniform(-1e-12, 1e-12) to separate them.
+    orc = Oracle()
+    m, n = 40, 2000
+    both = [dict(k=10, cumulative=c, noise=nz, seed=7) for c in (False, True) for nz in (False, True)]
+    for kind, k, dtype, variants, extra in (("ascending", 1, f32, both, {}), ("ascending", 12, f64, both, {}),
+                                            ("descending", 12, f32, both, {}), ("descending", 1, f64, both, {}),
+                                            ("planted", 16, f32, both, {}), ("planted", 16, f64, both, {}),
+                                            ("runs", 12, f64, [v for v in both if v["noise"]], {"span": 2.0 ** -8})):
+        for seed in range(1000, 1050):
+            pr = make_structured(kind, m, n, k, dtype, mean_c=40, seed=seed, **extra)
+            if kind == "runs" or not tie_pairs_per_user(orc.scores(pr["A"], pr["B"], dtype=dtype), pr["train"], pr["test"]).any():
+                break
+        else:
+            raise RuntimeError("no tie-free seed for " + kind)
+        run_case("g10_%s_k%d_%s" % (kind, k, "f32" if dtype == f32 else "f64"), pr["A"], pr["B"], pr["train"], pr["test"], variants, dtype)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,334 @@
+"""GPU parity on ORDERED and STRUCTURED scores (synth.make_structured), not only on i.i.d. factors.
+
+With make_factors a user's scores are i.i.d. in item order: a streaming top-K sees a new best ~ K ln(n / K) times in n items.  The
+sweep's data structures care about order where the reference (std::sort) does not: the sample seed takes its bound from the FIRST
+items of the catalogue, the lane buffers are sized for sixteen appends per lane and tile (ascending scores: every lane, every tile),
+lane_select bisects in value space first (outliers, clusters, runs of one value), and the lists / pending buffers / shared bound
+see an insert on every score or none after the first tile.  tests/test_structured_cpu.py shows that the inputs are what they say.
+
+That these tests can fail was shown once with a library whose k_seed_from_sample skips its walk of the sparse train row (it then
+counts train items among the sample's candidates: a bound that is too high, never an access out of range): seven cases here failed
+on incomplete top-K lists -- all `descending`, where the train row reaches into the first K items: fp64 at K = 50 / 100 / 300 (default,
+LANE_CAP_MIN, SPLITS, SAMPLE_SEED=4096), fp32 with NO_TRAIN_BITS at K = 100, and the descending twin of the fp64 order test -- and
+none of the 361 cases of test_hip_parity.py did.
+"""
+import functools
+import statistics
+
+import numpy as np
+import pytest
+
+from _parity import NT, _check_against_oracle, hip_calc
+from _util import assert_close, assert_same_bits, same_bits
+from oracle.ties import tie_pairs_per_user
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+F32, F64 = np.float32, np.float64
+M, N, MEAN_C = 150, 27000, 260
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from recometrics_amd import _binding
+    _binding.load()
+    assert _binding.device_count() > 0, "no HIP device visible"
+    return _binding
+
+
+def _tie_on_a_positive_near_the_top(pr, dtype, depth=1000):
+    from oracle.oracle import Oracle
+    sc = Oracle().scores(pr["A"], pr["B"], dtype=dtype)
+    trp, tri = pr["train"]
+    tep, tei = pr["test"][:2]
+    for u in np.flatnonzero(tie_pairs_per_user(sc, pr["train"], pr["test"])):
+        cand = np.ones(sc.shape[1], bool)
+        cand[tri[trp[u]:trp[u + 1]]] = False
+        s = sc[u][cand]
+        for p in tei[tep[u]:tep[u + 1]]:
+            if cand[p] and (s == sc[u, p]).sum() > 1 and (s > sc[u, p]).sum() < depth:
+                return True
+    return False
+
+
+@functools.lru_cache(maxsize=12)
+def _problem(kind, k, dtype, m=M, n=N, mean_c=MEAN_C, variant="spikes", span=4.0):
+    from recometrics_amd.synth import make_structured
+    for seed in range(1 + k, 20000, 1000):
+        pr = make_structured(kind, m, n, k, dtype, mean_c=mean_c, seed=seed, variant=variant, span=span)
+        # planted puts the positives at the top of the ranking, where ONE exact tie between a positive and another candidate moves
+        # AP@K and PR-AUC by more than the checker's 1e-5 against the compiled reference (it orders equal scores by libstdc++'s
+        # sort, deviation D4; seed 129 at 128 factors: user 50, rank 171, 1.1e-5 between restatement and reference on the CPU).
+        # The checker excuses tied users in the last bit only, so the case takes the first seed without such a tie in the first
+        # 1,000 ranks -- decided on the oracle's scores, before the device is asked anything.
+        if kind != "planted" or not _tie_on_a_positive_near_the_top(pr, dtype):
+            break
+    if m == M and mean_c == MEAN_C:           # rows in the LDS tables, streamed rows, and rows beyond 256 test items
+        nte = np.diff(pr["test"][0])
+        assert (nte <= 63).any() and (nte > 63).any() and (nte > 256).any()
+    return pr
+
+
+# ---- (a) every kind through the whole checker -----------------------------------------------------------------------------------
+# k = 1 is the folded item_biases call (every user shares one score vector); planted and trend with one factor ARE the ramp / the
+# popularity column alone and are left to the kinds that say so
+_KIND_SHAPES = [("ascending", F32, 1), ("ascending", F32, 40), ("ascending", F32, 128), ("ascending", F64, 1), ("ascending", F64, 24),
+                ("descending", F32, 1), ("descending", F32, 40), ("descending", F32, 128), ("descending", F64, 24),
+                ("trend", F32, 40), ("trend", F32, 128), ("trend", F64, 24),
+                ("planted", F32, 40), ("planted", F32, 128), ("planted", F64, 24)]
+
+
+@pytest.mark.parametrize("K", [10, 20, 100, 300])
+@pytest.mark.parametrize("kind,dtype,k", _KIND_SHAPES, ids=["%s-%s-k%d" % (a, np.dtype(b).name, c) for a, b, c in _KIND_SHAPES])
+def test_every_kind_through_the_whole_checker(hip, oracle, kind, dtype, k, K):
+    """status, ordered top-K index lists, top-K scores bit for bit, the rank of every test item, all metrics single + cumulative
+    against the restatement and the compiled reference.  K = 10 / 20: replace-the-minimum lists in LDS (fp32); 100: lane buffers +
+    k_collect_topk; 300: every user streamed, k_select_topk; fp64: lane buffers at every K."""
+    _check_against_oracle(hip, oracle, _problem(kind, k, dtype), K, dtype=dtype)
+
+
+@pytest.mark.parametrize("K", [10, 100])
+@pytest.mark.parametrize("kind,dtype,k", [("ascending", F32, 40), ("ascending", F64, 24), ("trend", F32, 40), ("trend", F64, 24), ("ascending", F32, 1)])
+def test_ordered_scores_under_the_tie_noise(hip, oracle, kind, dtype, k, K):
+    """break_ties_with_noise: the sample seed is off (its scores carry no noise) and the sweep adds the noise rows -- another path"""
+    _check_against_oracle(hip, oracle, _problem(kind, k, dtype), K, dtype=dtype, noise=True, seed=11)
+
+
+_LISTS_OFF = {"RM_DEBUG_LANE_MIN_K": "1000000"}
+_SWITCHES = [
+    # env, dtype, K, kinds                                                            -- which kernel / structure it reaches
+    ({"RM_DEBUG_LANE_CAP_MIN": "1"}, F32, 33, "adt"),                                 # smallest lane buffers: a selection per tile (ascending)
+    ({"RM_DEBUG_LANE_CAP_MIN": "1"}, F32, 100, "adt"),
+    ({"RM_DEBUG_LANE_CAP_MIN": "1"}, F64, 50, "adt"),                                 # fp64 sweep: four lanes per user, 8 appends per tile
+    ({"RM_DEBUG_LANE_CAP_MIN": "1", "RM_DEBUG_SPLITS": "3,2,5"}, F32, 100, "at"),     # + item ranges: the shared bound, k_collect_topk's sources
+    ({"RM_DEBUG_LANE_MIN_K": "1"}, F32, 1, "ad"),                                     # lane buffers at every k_metrics (smallest buffers of all)
+    ({"RM_DEBUG_LANE_MIN_K": "1"}, F32, 3, "a"),
+    ({"RM_DEBUG_LANE_MIN_K": "1"}, F32, 8, "at"),
+    ({"RM_DEBUG_LANE_MIN_K": "1"}, F32, 21, "adt"),
+    (_LISTS_OFF, F32, 32, "adt"),                                                     # replace-the-minimum lists at their largest K (fp32)
+    (_LISTS_OFF, F64, 12, "adt"),                                                     # fp64 LDS lists + pending buffers
+    (_LISTS_OFF, F64, 50, "at"),                                                      # fp64 HBM lists
+    ({"RM_DEBUG_HBM_LISTS": "1"}, F32, 20, "adt"),                                    # fp32 lists in HBM + pending buffers
+    (dict(_LISTS_OFF, RM_DEBUG_HBM_LISTS="1"), F64, 12, "a"),
+    ({"RM_DEBUG_NO_PENDING": "1"}, F32, 10, "at"),                                    # LDS lists, inserts straight into the list
+    ({"RM_DEBUG_HBM_LISTS": "1", "RM_DEBUG_NO_PENDING": "1"}, F32, 20, "at"),
+    ({"RM_DEBUG_NSUB2": "1"}, F32, 10, "at"),                                         # the two-sub-tile block (<= 64 factors)
+    ({"RM_DEBUG_SPLITS": "5"}, F32, 10, "adt"),                                       # five item ranges: with descending scores the first holds the whole top-K
+    ({"RM_DEBUG_SPLITS": "3,2,5"}, F32, 20, "at"),                                    # two-level grid
+    ({"RM_DEBUG_SPLITS": "3,2,5"}, F64, 50, "ad"),
+    ({"RM_DEBUG_SAMPLE_SEED": "64", "RM_DEBUG_LANE_MIN_K": "1"}, F32, 21, "adt"),      # k_seed_from_sample at every sample size, lane buffers ...
+    ({"RM_DEBUG_SAMPLE_SEED": "1024"}, F32, 100, "adt"),
+    ({"RM_DEBUG_SAMPLE_SEED": "4096"}, F32, 100, "ad"),
+    ({"RM_DEBUG_SAMPLE_SEED": "4096"}, F64, 50, "adt"),
+    ({"RM_DEBUG_SAMPLE_SEED": "64"}, F32, 12, "adt"),                                 # ... and the lists' DUMP launch
+    ({"RM_DEBUG_NO_SEED": "1"}, F32, 100, "adt"),                                     # no bound but the sweep's own
+    ({"RM_DEBUG_NO_SEED": "1"}, F32, 10, "ad"),
+    ({"RM_DEBUG_NO_TRAIN_BITS": "1"}, F32, 10, "adt"),                                # the CSR cursor instead of the dense train rows
+    ({"RM_DEBUG_NO_TRAIN_BITS": "1"}, F32, 100, "ad"),                                # + the sample's own walk of the sparse train rows
+    ({"RM_DEBUG_EXT_TOPK": "1"}, F32, 10, "at"),                                      # top-K picked from stored score rows
+    ({"RM_DEBUG_EXT_TOPK": "1"}, F64, 100, "ad"),
+]
+_SWITCH_CASES = [(env, dtype, K, {"a": "ascending", "d": "descending", "t": "trend"}[c]) for env, dtype, K, kinds in _SWITCHES for c in kinds]
+
+
+@pytest.mark.parametrize("env,dtype,K,kind", _SWITCH_CASES,
+                         ids=["%s-%s-K%d-%s" % (",".join("%s=%s" % (a[9:], b) for a, b in e.items()), np.dtype(d).name, K, kind) for e, d, K, kind in _SWITCH_CASES])
+def test_ordered_scores_under_the_switches_that_choose_the_data_structure(hip, oracle, env, dtype, K, kind, monkeypatch):
+    """ascending (an insert on every score), descending (none after the first tile: the sample's bound is the final one) and trend
+    through every top-K structure the sweep has; the table above says which one a row reaches.  The product of switches is pruned to
+    the rows that reach distinct code, and a kind is left out of a row where it meets nothing the other rows do not."""
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    _check_against_oracle(hip, oracle, _problem(kind, 40 if dtype == F32 else 24, dtype), K, dtype=dtype)
+
+
+@pytest.mark.parametrize("K", [20, 300])
+@pytest.mark.parametrize("kind", ["trend", "ascending"])
+def test_ordered_scores_on_a_large_catalogue(hip, oracle, kind, K):
+    """64 users x 380,000 items x 128 factors: item ranges, the shared bound overtaking every range but the last, k_collect_topk
+    with every range's buffers full"""
+    pr = _problem(kind, 128, F32, m=64, n=380_000, mean_c=100)
+    _check_against_oracle(hip, oracle, pr, K)
+    assert hip.timings()["item_splits"] > 1, hip.timings()
+
+
+@pytest.mark.parametrize("K", [10, 48, 300])
+@pytest.mark.parametrize("dtype,k,noise", [(F32, 40, False), (F32, 1, False), (F64, 24, True)])
+def test_runs_of_exact_ties_met_in_ascending_order(hip, oracle, dtype, k, noise, K):
+    """a fifth of the item rows repeat their predecessor's: exact ties at and around every bound, met in ascending order.  fp32
+    (and noise off) against the restatement only -- the reference orders exact ties by libstdc++'s sort (deviation D4); fp64 with the
+    tie noise on against the reference as well: on a ramp of 2^-8 its Uniform(-1e-12, 1e-12) separates every pair."""
+    pr = _problem("runs", k, dtype, span=2.0 ** -8)
+    assert (pr["B"][1:] == pr["B"][:-1]).all(axis=1).mean() > 0.15
+    _check_against_oracle(hip, oracle, pr, K, dtype=dtype, noise=noise, seed=3, reference=noise)
+
+
+@pytest.mark.parametrize("env", [{}, {"RM_DEBUG_LANE_CAP_MIN": "1"}])
+@pytest.mark.parametrize("K", [10, 48, 300])
+@pytest.mark.parametrize("dtype,k", [(F32, 40), (F64, 24)])
+@pytest.mark.parametrize("apart", [False, True])
+def test_every_item_row_the_same(hip, oracle, dtype, k, K, env, apart, monkeypatch):
+    """27,000 exact ties per user.  apart=False: every row the same -- the reference declares a user whose best and worst scores are
+    equal invalid (src/recometrics.hpp:525, :547, :561): NaN metrics, status 1, empty lists and rank 0 for every test item, streamed
+    users included (rm_rank_* reported the ranks its side stream had counted for them: fixed with this test).  apart=True: the last eight
+    items score lower, so the users are valid and the order of the other 26,992 is the item ids' alone: the top-K is the
+    first K candidates, every selection ends in the tie cut.  Exact ties without noise: the restatement only for fp32 and for the
+    ranked case (deviation D4)."""
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    pr = dict(_problem("ascending", k, dtype))
+    row = pr["B"][N // 2]
+    assert row[0] > 0
+    pr["B"] = np.ascontiguousarray(np.broadcast_to(row, pr["B"].shape))
+    if apart:
+        pr["B"][N - 8:] = -row
+    _check_against_oracle(hip, oracle, pr, K, dtype=dtype, reference=(dtype == F64 and not apart))
+    trp, tri = pr["train"]
+    got = hip.rank(np.ascontiguousarray(pr["A"], dtype), pr["B"], trp, tri, pr["test"][0], pr["test"][1], K)
+    assert (got["status"] == (0 if apart else 1)).all()
+    if not apart:
+        assert (got["topk_idx"] == -1).all() and (got["pos_rank"] == 0).all()
+    for u in (0, 1, M - 1) if apart else ():
+        cand = np.setdiff1d(np.arange(K + trp[u + 1] - trp[u] + 1), tri[trp[u]:trp[u + 1]])[:K]
+        assert (got["topk_idx"][u] == cand).all()
+
+
+@pytest.mark.parametrize("env", [{}, {"RM_DEBUG_LANE_CAP_MIN": "1"}])
+@pytest.mark.parametrize("K", [33, 100])
+@pytest.mark.parametrize("variant,dtype,k", [("spikes", F32, 40), ("clusters", F32, 40), ("spikes", F64, 24), ("clusters", F64, 24)])
+def test_outliers_and_clusters(hip, oracle, variant, dtype, k, K, env, monkeypatch):
+    """a flat bulk within +-1e-3 under a handful of scores at +-1e3 ... 1e6, and two clusters with nothing in between: the quartiles
+    of [lo, hi] hold no entry or all of them, lane_select's bisection must go on in key space"""
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    # (clusters in fp32: 13,500 scores within 1e-3 of a_u ~ 2 are ~8,000 distinct floats -- exact ties from the first rank on, 57 of
+    # 64 users differ between restatement and reference on the CPU (test_structured_cpu.py): the restatement only, as for `runs`)
+    _check_against_oracle(hip, oracle, _problem("outliers", k, dtype, variant=variant), K, dtype=dtype,
+                          reference=not (variant == "clusters" and dtype == F32))
+
+
+# ---- (b) order must not matter ---------------------------------------------------------------------------------------------------
+def _twins(pr):
+    from recometrics_amd.synth import permute_items
+    n = pr["B"].shape[0]
+    perms = {"ascending": np.arange(n), "shuffled": np.random.default_rng(99).permutation(n), "descending": np.arange(n)[::-1].copy()}
+    return {name: (perm, pr if name == "ascending" else permute_items(pr, perm)) for name, perm in perms.items()}
+
+
+def _order_must_not_matter(hip, pr, K, dtype, max_tie_share=0.01):
+    """A score depends on the (user, item) pair only: relabelling the items changes nothing but the order in which the sweep meets
+    them.  `pr` (a trend problem: ascending under noise) against its shuffled and descending twins."""
+    m = pr["A"].shape[0]
+    A = np.ascontiguousarray(pr["A"], dtype)
+    tw = _twins(pr)
+    ranks, metrics = {}, {}
+    for name, (perm, p) in tw.items():
+        ranks[name] = hip.rank(A, np.ascontiguousarray(p["B"], dtype), p["train"][0], p["train"][1], p["test"][0], p["test"][1], K + 1)
+        metrics[name] = hip_calc(hip, p["A"], p["B"], p["train"], p["test"], K, dtype=dtype)
+        assert (ranks[name]["status"] == ranks["ascending"]["status"]).all()
+    base = ranks["ascending"]
+    ok = base["status"] == 0                                 # ranked (1: the user is skipped, its lists are not written)
+    assert ok.mean() > 0.9
+    distinct = (np.diff(base["topk_score"], axis=1) != 0).all(axis=1)
+    assert distinct.mean() > 0.98
+    excused = np.zeros(m, bool)
+    for name in ("shuffled", "descending"):
+        perm = tw[name][0]
+        # the multiset of the K + 1 best scores does not depend on the labels -- ties included
+        assert_same_bits(ranks[name]["topk_score"][ok], base["topk_score"][ok], "top-K scores, %s order" % name)
+        sel = ok & distinct
+        assert (ranks[name]["topk_idx"][sel, :K] == perm[base["topk_idx"][sel, :K]]).all(), "top-K items, %s order" % name
+        differing = np.zeros(m, bool)
+        assert set(metrics[name]) == set(metrics["ascending"]) and len(metrics[name]) == 10
+        for key, arr in metrics[name].items():
+            assert arr.shape == metrics["ascending"][key].shape
+            differing |= ~same_bits(arr, metrics["ascending"][key])
+        who = np.flatnonzero(differing)
+        for lo in range(0, who.size, 256):                   # every user that differs in a bit has an exact tie on a positive
+            part = who[lo:lo + 256]
+            sc = hip.debug_scores(A[part], np.ascontiguousarray(pr["B"], dtype))
+            pairs = tie_pairs_per_user(sc, pr["train"], pr["test"], part)
+            assert (pairs > 0).all(), "users %s change with the item order (%s) without an exact tie on a positive" % (part[pairs == 0][:8].tolist(), name)
+        excused |= differing
+    share = excused.mean()
+    print("order: %d users, K = %d, %s: %d excused by an exact tie on a positive (%.3f %%)" % (m, K, np.dtype(dtype).name, excused.sum(), 100 * share))
+    assert share <= max_tie_share, "too many users excused by ties: change the data, not the cap"
+
+
+@pytest.mark.parametrize("m,dtype,K,mean_c", [(8192, F32, 10, 30), (8192, F32, 100, 30), (2048, F64, 50, 144)])
+def test_order_must_not_matter(hip, m, dtype, K, mean_c):
+    """26,744 items x 64 factors.  fp32: a positive shares its score with another candidate with probability ~ 0.3 n 2^-24 = 5e-4, so
+    the rows are kept short (mean_c = 30: ~9 test items, 0.4 % of the users tied) to stay below the cap of 1 % excused users; fp64
+    has no ties and keeps BASELINE C2's row lengths."""
+    from recometrics_amd.synth import make_structured
+    pr = make_structured("trend", m, 26744, 64, dtype, mean_c=mean_c, seed=102)
+    _order_must_not_matter(hip, pr, K, dtype)
+
+
+def test_order_must_not_matter_at_baseline_c2s_full_user_count(hip):
+    """138,493 users x 26,744 x 64, K = 10, all ten metrics, noise off, through the host-pointer entry; make_interactions_fast with
+    short rows (mean_c = 20: ~6 test items; the lognormal tail still has a few hundred streamed users) for the same reason as above"""
+    from recometrics_amd.synth import make_interactions_fast, make_structured
+    pr = make_structured("trend", 138_493, 26744, 64, F32, mean_c=20, seed=102, interactions=make_interactions_fast)
+    assert (np.diff(pr["test"][0]) > 63).sum() > 100
+    _order_must_not_matter(hip, pr, 10, F32)
+
+
+# ---- (c) the call a user types ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("noise", [False, None])
+@pytest.mark.parametrize("bias_dtype", [F32, F64])
+@pytest.mark.parametrize("order", ["ascending", "descending"])
+def test_item_biases_sorted_by_popularity(hip, oracle, order, bias_dtype, noise):
+    """calc_reco_metrics(X_train, X_test, None, None, item_biases=sorted popularity, k=10, all_metrics=True): one factor, every user
+    shares one strictly monotone score vector; noise off and the default (on).  The API promotes the biases to float64."""
+    from scipy.sparse import csr_array
+    from _parity import _reference
+    from recometrics_amd import calc_reco_metrics
+    from recometrics_amd.synth import make_interactions, make_structured
+    m, n = 2000, 26744
+    ramp = make_structured("ascending", 2, n, 1, F64, mean_c=2, seed=3)["B"][:, 0]
+    pop = (ramp ** 3).astype(bias_dtype)                     # a flat middle, long tails; distinct in float32 too
+    assert (np.diff(pop) > 0).all()
+    if order == "descending":
+        pop = pop[::-1].copy()
+    trp, tri, tep, tei, tev = make_interactions(m, n, 144, F64, 21)
+    Xtr = csr_array((np.ones(tri.shape[0]), tri, trp), shape=(m, n))
+    Xte = csr_array((tev, tei, tep), shape=(m, n))
+    kw = {} if noise is None else {"break_ties_with_noise": noise}
+    d = calc_reco_metrics(Xtr, Xte, None, None, item_biases=pop, k=10, all_metrics=True, as_df=False, **kw)
+    args = (np.ones((m, 1)), pop.astype(F64).reshape(-1, 1), (trp, tri), (tep, tei, tev), 10)
+    okw = dict(dtype=F64, noise=noise is None, seed=1, nthreads=NT)
+    want = oracle.calc(*args, **okw)
+    assert d["K"] == 10 and set(d) == set(want) | {"K"} and len(want) == 10
+    for key in want:
+        assert d[key].dtype == F64
+        assert_close(d[key], want[key], TOL, "item biases %s: %s" % (order, key))
+        if key != "ROC_AUC":
+            assert_same_bits(d[key], want[key], "item biases %s: %s (bitwise)" % (order, key))
+    ref = _reference()
+    if ref is not None:                                       # (tie-free: strictly monotone float64 scores)
+        real = ref.calc(*args, **okw)
+        for key in real:
+            assert_close(d[key], real[key], TOL, "item biases %s vs the compiled reference: %s" % (order, key))
+            if key != "ROC_AUC":
+                assert_same_bits(d[key], real[key], "item biases %s vs the compiled reference: %s (bitwise)" % (order, key))
+
+
+# ---- (d) what order costs: reported, not asserted ----------------------------------------------------------------------------------
+def test_report_what_item_order_costs(hip):
+    """sweep_ms (median of 7 calls after a warm-up call) of one trend problem -- 8,192 users x 26,744 items x 64 factors, fp32, all ten
+    metrics -- in shuffled, ascending and descending item order at K = 10 and K = 100.  Printed (run with -s); DESIGN.md section 2
+    records the figures.  No ratio is asserted: this is a measurement."""
+    from recometrics_amd.synth import make_structured
+    pr = make_structured("trend", 8192, 26744, 64, F32, mean_c=30, seed=102)
+    tw = _twins(pr)
+    for K in (10, 100):
+        for name in ("shuffled", "ascending", "descending"):
+            p = tw[name][1]
+            ms = []
+            for it in range(8):
+                hip_calc(hip, p["A"], p["B"], p["train"], p["test"], K)
+                ms.append(hip.timings()["sweep_ms"])
+            print("item order cost: K = %3d %-10s sweep_ms median %.3f (min %.3f max %.3f of %d calls after 1 warm-up)"
+                  % (K, name, statistics.median(ms[1:]), min(ms[1:]), max(ms[1:]), len(ms) - 1))
+            assert min(ms) > 0
