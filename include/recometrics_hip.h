@@ -124,6 +124,38 @@ int rm_rank_f64(
     int32_t min_items_pool, int32_t min_pos_test, uint64_t seed,
     int32_t *topk_idx, double *topk_score, int64_t *pos_rank, int32_t *status);
 
+/* Top-K recommendation lists for EVERY user (no counterpart in the reference: the lists its metrics are computed from).
+ * For each user u in [0, m): candidates = the items of [0, n) not listed in row u of the exclusion matrix (CSR, validated like
+ * Xtrain_csr_*: unsorted rows are sorted in a copy, duplicates tolerated; Xexcl_csr_p == NULL excludes nothing and Xexcl_csr_i
+ * is then ignored); score = the k-ordered fma chain from +0 of the metric call (bit-identical to rm_debug_scores_*); order =
+ * score descending, then item id ascending (+0 and -0 are equal scores); no tie noise.
+ * Outputs, row-major: idx[m x k_top] item ids, score[m x k_top] (may be NULL: ids only), status[m]:
+ *   0  the first min(k_top, C) places of the row hold the list (C = number of candidates), the others -1 / NaN;
+ *   1  the row excludes the whole catalogue: -1 / NaN everywhere;
+ *   2  some candidate score is NaN or +-Inf: -1 / NaN everywhere.
+ * 1 <= k_top <= n; m == 0 returns RM_OK and writes nothing.  For every user rm_rank_* (noise off) ranks, list and scores are
+ * the same bits.  rm_recommend_f32/f64: HOST pointers, through the machinery of the host-pointer metric call (user batches,
+ * rm_set_devices shards, SIGINT -> RM_ERR_INTERRUPTED with the finished batches kept, `nthreads` for the fall-back sort);
+ * results depend neither on the device list nor on the batch size.  rm_recommend_dev_f32/f64: DEVICE pointers on the current
+ * device, asynchronous on `stream` like rm_calc_metrics_dev_*; `nnz_excl` is the length of Xexcl_csr_i; k_top > 256 may answer
+ * RM_ERR_NOMEM as the metric call does (one score row per user).  rm_get_timings covers both. */
+int rm_recommend_f32(
+    const float *A, size_t lda, const float *B, size_t ldb, int32_t m, int32_t n, int32_t k,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,
+    int32_t *idx, float *score, int32_t *status, int32_t nthreads);
+int rm_recommend_f64(
+    const double *A, size_t lda, const double *B, size_t ldb, int32_t m, int32_t n, int32_t k,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,
+    int32_t *idx, double *score, int32_t *status, int32_t nthreads);
+int rm_recommend_dev_f32(
+    const float *A, size_t lda, const float *B, size_t ldb, int32_t m, int32_t n, int32_t k,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,
+    int32_t *idx, float *score, int32_t *status, void *stream);
+int rm_recommend_dev_f64(
+    const double *A, size_t lda, const double *B, size_t ldb, int32_t m, int32_t n, int32_t k,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,
+    int32_t *idx, double *score, int32_t *status, void *stream);
+
 /* Dense score matrix out[m x n] (host) computed by the sweep's own MFMA contraction -- test hook that pins the
  * "bit-identical to the k-ordered fma chain" claim (reference src/recometrics.hpp:99-112). */
 int rm_debug_scores_f32(const float *A, size_t lda, const float *B, size_t ldb,

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _binding
 
-__all__ = ["calc_reco_metrics", "split_reco_train_test"]
+__all__ = ["calc_reco_metrics", "recommend_topk", "split_reco_train_test"]
 __version__ = "0.1.0"
 
 # (keyword of calc_reco_metrics, name in the C-ABI order, key of the result dict) -- reference __init__.py:590-613
@@ -278,3 +278,68 @@ def calc_reco_metrics(
         out["K"] = k
         return out
     return _as_frame(out, k, bool(cumulative), bool(rename_k))
+
+
+def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, return_scores=True):
+    """The ``k`` best items for every user, by the scores and the tie rule the metrics of :func:`calc_reco_metrics` are computed
+    under (without tie noise): score descending, then item id ascending.  The reference has no such call.
+
+    ``A`` [users, factors] and ``B`` [items, factors] as in :func:`calc_reco_metrics` (float32 only when both are float32;
+    ``A=None, B=None`` with ``item_biases`` ranks by the biases alone; ``item_biases`` next to factors is added to the scores).
+    ``X_train``: optional sparse user-item matrix of the items to leave out per user (any SciPy format; never modified), ``None``
+    leaves nothing out.  ``users``: optional integer array -- lists for these rows of ``A`` / ``X_train`` only, in this order.
+
+    Returns ``(ids, scores, status)``: ``ids`` [len(users) or users, k] int32, ``scores`` of the same shape (``None`` with
+    ``return_scores=False``), ``status`` int32 per row: 0 = the first ``min(k, candidates)`` places hold the list and the others
+    -1 / NaN, 1 = every item is excluded, 2 = some candidate score is NaN or infinite (both: -1 / NaN everywhere).
+    """
+    if hasattr(item_biases, "to_numpy"):
+        item_biases = item_biases.to_numpy()
+    _fail_if((A is None) != (B is None), "'A' and 'B' must either be passed together or passed as 'None' together.")
+    if A is None:
+        _fail_if(item_biases is None, "Must pass item biases if not passing factors.")
+        _fail_if(X_train is None and users is None, "Must pass 'X_train' or 'users' if not passing factors (the number of users is not known).")
+        B = np.ascontiguousarray(item_biases, dtype=np.float64).reshape(-1, 1)
+        n_rows = X_train.shape[0] if X_train is not None else int(np.max(np.asarray(users), initial=-1)) + 1
+        A = np.ones((n_rows, 1), dtype=np.float64)
+        item_biases = None
+    assert isinstance(A, np.ndarray) and isinstance(B, np.ndarray)
+    _fail_if(A.ndim != 2, "'A' must be a 2-dimensional array.")
+    _fail_if(B.ndim != 2, "'B' must be a 2-dimensional array.")
+    _fail_if(A.shape[1] != B.shape[1], "'A' and 'B' must have the same number of columns.")
+    _fail_if(0 in (A.shape[1], B.shape[0]), "Input matrices cannot be empty.")
+    n_users, n_items = A.shape[0], B.shape[0]
+    _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
+    _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    k = int(k)
+    _fail_if(k < 1, "'k' must be positive.")
+    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+    if X_train is not None:
+        from scipy.sparse import issparse
+        _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
+        _fail_if(X_train.shape[1] != n_items, "Number of items in 'B' and 'X_train' does not match.")
+        _fail_if(X_train.shape[0] != n_users, "Number of users in 'A' and 'X_train' does not match.")
+    if users is not None:
+        users = np.asarray(users)
+        _fail_if(users.ndim != 1 or (users.size and users.dtype.kind not in "iu"), "'users' must be a 1-d integer array.")
+        users = users.astype(np.int64, copy=False)
+        _fail_if(users.size and (users.min() < 0 or users.max() >= n_users), "'users' has entries outside the rows of 'A'.")
+    dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
+    if item_biases is not None:
+        A, B = _fold_item_biases(A, B, item_biases, n_items, dtype)
+
+    # ---- everything above raises before the library is touched ----
+    if users is not None:
+        A = A[users]
+        if X_train is not None:
+            X_train = _csr_int32(X_train)[users]
+    excl_p = excl_i = None
+    if X_train is not None:
+        X_train = _csr_int32(X_train)
+        excl_p, excl_i = np.ascontiguousarray(X_train.indptr), np.ascontiguousarray(X_train.indices)
+    m = A.shape[0]
+    if m == 0:
+        return (np.empty((0, k), np.int32), np.empty((0, k), dtype) if return_scores else None, np.empty(0, np.int32))
+    A, lda = _row_major_with_ld(A.astype(dtype, copy=False))
+    B, ldb = _row_major_with_ld(B.astype(dtype, copy=False))
+    return _binding.recommend(A, lda, B, ldb, excl_p, excl_i, k, bool(return_scores))

@@ -17,7 +17,8 @@ _lib = None
 METRIC_ORDER = ("p", "tp", "r", "ap", "tap", "ndcg", "hit", "rr", "roc", "pr")
 EXPORTS = (
     "rm_calc_metrics_f32", "rm_calc_metrics_f64", "rm_calc_metrics_dev_f32", "rm_calc_metrics_dev_f64",
-    "rm_rank_f32", "rm_rank_f64", "rm_debug_scores_f32", "rm_debug_scores_f64", "rm_has_openmp",
+    "rm_rank_f32", "rm_rank_f64", "rm_recommend_f32", "rm_recommend_f64", "rm_recommend_dev_f32", "rm_recommend_dev_f64",
+    "rm_debug_scores_f32", "rm_debug_scores_f64", "rm_has_openmp",
     "rm_last_error", "rm_device_count", "rm_set_device", "rm_set_devices", "rm_get_devices", "rm_request_interrupt",
     "rm_get_timings", "rm_release_workspace", "rm_debug_reload_switches",
     "rm_split_f32", "rm_split_f64", "rm_split_size", "rm_split_copy", "rm_split_free", "rm_split_last_error",
@@ -47,7 +48,12 @@ def load():
     host = [vp, sz, vp, sz, i32, i32, i32, vp, vp, vp, vp, vp, i32, ci, ci] + [vp] * 10 + [ci, i32, i32, i32, u64]
     dev = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, vp, vp, vp, i64, i32, ci, ci] + [vp] * 10 + [ci, i32, i32, u64, vp]
     rank_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, vp, vp, i32, ci, ci, i32, i32, u64, vp, vp, vp, vp]
+    reco_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32]
+    reco_dev_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp]
     for suf in ("f32", "f64"):
+        getattr(lib, "rm_recommend_" + suf).argtypes = reco_sig
+        getattr(lib, "rm_recommend_dev_" + suf).argtypes = reco_dev_sig
+        getattr(lib, "rm_recommend_" + suf).restype = getattr(lib, "rm_recommend_dev_" + suf).restype = ci
         getattr(lib, "rm_calc_metrics_" + suf).argtypes = host
         getattr(lib, "rm_calc_metrics_dev_" + suf).argtypes = dev
         getattr(lib, "rm_rank_" + suf).argtypes = rank_sig
@@ -276,6 +282,38 @@ def rank(A, B, train_p, train_i, test_p, test_i, k_metrics, break_ties_with_nois
     if rc:
         _raise(lib, rc)
     return {"topk_idx": idx, "topk_score": sc, "pos_rank": pr[:test_i.shape[0]], "status": st}
+
+
+def recommend(A, lda, B, ldb, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
+    """Host-array entry of the recommendation lists (rm_recommend_*): A [m, k] / B [n, k] row-major with leading dimensions
+    lda / ldb, `excl_p` / `excl_i` the int32 CSR of the items to leave out per user (`excl_p` None: nothing is left out).
+    Returns (ids [m, k_top] int32, scores [m, k_top] or None, status [m] int32); -1 / NaN where a row holds no entry."""
+    lib = load()
+    dtype = A.dtype.type
+    m, k = A.shape
+    n = B.shape[0]
+    idx = np.empty((m, k_top), dtype=np.int32)
+    sc = np.empty((m, k_top), dtype=dtype) if return_scores else None
+    st = np.empty(m, dtype=np.int32)
+    fn = getattr(lib, "rm_recommend_" + _suffix(dtype))
+    rc = fn(_p(A), lda, _p(B), ldb, m, n, k, None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p), _p(excl_i), k_top,
+            _p(idx), _p(sc), _p(st), int(nthreads))
+    if rc:
+        _raise(lib, rc)
+    return idx, sc, st
+
+
+def recommend_device(dtype, A, lda, B, ldb, m, n, k, excl_p, excl_i, nnz_excl, k_top, idx, score, status, stream=0):
+    """Device-pointer entry (rm_recommend_dev_*): every array argument is an integer device address (0 == NULL: `excl_p` = nothing
+    is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
+    lib = load()
+    fn = getattr(lib, "rm_recommend_dev_" + _suffix(dtype))
+
+    def vp(x):
+        return C.c_void_p(int(x)) if x else None
+    rc = fn(vp(A), lda, vp(B), ldb, m, n, k, vp(excl_p), vp(excl_i), nnz_excl, k_top, vp(idx), vp(score), vp(status), vp(stream))
+    if rc:
+        _raise(lib, rc)
 
 
 def debug_scores(A, B):

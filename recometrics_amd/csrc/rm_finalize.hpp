@@ -1241,4 +1241,112 @@ __global__ void k_finalize(FinalArgs<T, S> a)
     }
 }
 
+// ---- recommendation lists (rm_recommend_*): the finalisation of a call without a test matrix ----------------------------------
+// Every user of the call passes through here and 4 K (+ sizeof(S) K) bytes per user are written, straight into the caller's arrays.
+// One thread per USER (not per slot as k_finalize: there is no group table to read, and consecutive users own consecutive output
+// rows): a block's 128 users own ONE contiguous piece of idx / score, 128 K entries long.
+//   * lists still in parts (LDS / HBM replace-the-minimum lists): each thread merges its user's partial lists exactly as k_finalize
+//     does (cursors in LDS columns), RECO_CHUNK places at a time into an LDS tile [user][place]; behind a barrier the block writes
+//     the tile out with consecutive threads on consecutive addresses -- runs of min(K, RECO_CHUNK) entries per user, whole lines
+//     when K <= RECO_CHUNK -- instead of 128 threads storing at a stride of K entries;
+//   * lists already ordered by user (`merged`: k_collect_topk / k_select_topk): a flat copy of the block's piece, cut at each user's
+//     own length.
+// status: 0 = the first min(K, C) places hold the list; 1 = no candidate (the user has no slot); 2 = some candidate score is NaN or
+// +-Inf (the parts' vmax / vmin / has_nan: exact whenever the host could not prove every score finite -- SweepArgs::check_nan --
+// and never raised otherwise).  Places without an entry hold -1 / NaN.
+template <class S> struct RecoArgs {
+    int m, n, K, n_part;
+    const int *flags, *uslot_base, *slot_index, *train_p;
+    const Entry<S> *pl; const PartialStat<S> *pst;
+    const Entry<S> *merged;      // non-null: [m][K] ordered lists by user, written by k_collect_topk / k_select_topk
+    int *idx; S *score; int *status;      // the caller's arrays; score may be null
+};
+constexpr int RECO_THREADS = 128, RECO_CHUNK = 16, RECO_LD = RECO_CHUNK + 1;      // (tile rows of 17 words: a thread per row, no bank conflict)
+template <class S> inline size_t reco_lds_bytes(int n_part, bool merged_ready)
+{
+    return merged_ready ? 0 : (sizeof(S) + 4) * (size_t)RECO_THREADS * RECO_LD + 4 * (size_t)n_part * RECO_THREADS;
+}
+
+template <class S>
+__global__ __launch_bounds__(RECO_THREADS) void k_finalize_reco(RecoArgs<S> a)
+{
+    extern __shared__ __attribute__((aligned(16))) char reco_smem[];
+    __shared__ int len_s[RECO_THREADS];                             // places of each user's row that hold an entry
+    const int tid = threadIdx.x;
+    const long long u0 = (long long)blockIdx.x * RECO_THREADS;
+    const int users_here = (int)(a.m - u0 < RECO_THREADS ? a.m - u0 : RECO_THREADS);
+    const int u = (int)u0 + tid;
+    const int K = a.K, NP = a.n_part;
+    const bool active = tid < users_here && (a.flags[u] & UF_ACTIVE);
+    int s0 = 0, W = 0, status = 1;
+    if (active) {
+        s0 = a.slot_index[a.uslot_base[u]];
+        const int C = a.n - (a.train_p[u + 1] - a.train_p[u]);
+        S vmax = -(S)INFINITY, vmin = (S)INFINITY; bool any_nan = false;
+        for (int q = 0; q < NP; q++) {
+            const PartialStat<S> ps = a.pst[(size_t)s0 * NP + q];
+            vmax = ps.vmax > vmax ? ps.vmax : vmax;
+            vmin = ps.vmin < vmin ? ps.vmin : vmin;
+            any_nan |= ps.has_nan != 0;
+        }
+        status = (any_nan || vmax == (S)INFINITY || vmin == -(S)INFINITY) ? 2 : 0;
+        W = status ? 0 : (K < C ? K : C);
+    }
+    if (tid < users_here) a.status[u] = status;
+    const size_t out0 = (size_t)u0 * K;
+    if (a.merged) {
+        len_s[tid] = W;
+        __syncthreads();
+        const long long total = (long long)users_here * K;
+        for (long long e = tid; e < total; e += RECO_THREADS) {
+            const int ul = (int)(e / K), p = (int)(e - (long long)ul * K);
+            Entry<S> be; be.s = (S)qnan<float>(); be.idx = -1;
+            if (p < len_s[ul]) be = a.merged[out0 + e];
+            a.idx[out0 + e] = be.idx;
+            if (a.score) a.score[out0 + e] = be.s;
+        }
+        return;
+    }
+    S *tile_s = (S *)reco_smem;                                                                       // [RECO_THREADS][RECO_LD]
+    int *tile_i = (int *)(reco_smem + sizeof(S) * RECO_THREADS * RECO_LD);                            // [RECO_THREADS][RECO_LD]
+    unsigned short *head_base = (unsigned short *)(tile_i + RECO_THREADS * RECO_LD);                  // [n_part][RECO_THREADS] cursors, then the parts that hold entries
+    unsigned short *head = head_base + tid, *alive = head_base + (size_t)NP * RECO_THREADS + tid;
+    const Entry<S> *PL = a.pl + (size_t)s0 * NP * K;
+    int n_alive = 0;
+    if (W > 0) {
+        for (int q = 0; q < NP; q++) {                              // (a part without entries is marked by its first one: rm_sweep.hpp)
+            const bool empty = PL[(size_t)q * K].idx == IDX_EMPTY;
+            head[q * RECO_THREADS] = empty ? (unsigned short)K : (unsigned short)0;
+            if (!empty) alive[(n_alive++) * RECO_THREADS] = (unsigned short)q;
+        }
+    }
+    for (int c0 = 0; c0 < K; c0 += RECO_CHUNK) {
+        const int kc = K - c0 < RECO_CHUNK ? K - c0 : RECO_CHUNK;
+        for (int i = 0; i < kc; i++) {
+            Entry<S> be; be.s = (S)qnan<float>(); be.idx = -1;
+            if (c0 + i < W) {
+                int best = -1;
+                for (int t = 0; t < n_alive; t++) {
+                    const int q = alive[t * RECO_THREADS];
+                    const int hq = head[q * RECO_THREADS];
+                    if (hq >= K) continue;
+                    const Entry<S> e = PL[(size_t)q * K + hq];
+                    if (best < 0 || ent_before(e, be)) { best = q; be = e; }
+                }
+                if (best >= 0) head[best * RECO_THREADS]++;
+                if (best < 0 || be.idx == IDX_EMPTY) { be.s = (S)qnan<float>(); be.idx = -1; }
+            }
+            tile_s[tid * RECO_LD + i] = be.s; tile_i[tid * RECO_LD + i] = be.idx;
+        }
+        __syncthreads();
+        for (int e = tid; e < users_here * kc; e += RECO_THREADS) {
+            const int ul = e / kc, p = e - ul * kc;
+            const size_t at = out0 + (size_t)ul * K + c0 + p;
+            a.idx[at] = tile_i[ul * RECO_LD + p];
+            if (a.score) a.score[at] = tile_s[ul * RECO_LD + p];
+        }
+        __syncthreads();
+    }
+}
+
 } // namespace rm

@@ -244,6 +244,9 @@ template <class T> struct Call {          // one calc_metrics call; every pointe
     // dense train rows: decided once per call (-1 = not yet: run() asks dense_rows_fit itself) -- every pass of a call gets the
     // answer the first one got, whatever the passes in between have allocated
     int dense_fit = -1;
+    // recommendation lists (rm_recommend_*): no test matrix (`test_p` is null), no metric; every user with a candidate gets its ordered
+    // list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
+    bool reco = false;
 };
 // internal status: some CSR row is not sorted (the entry points sort a copy of the rows and run again; never returned to a caller)
 constexpr int RM_INTERNAL_UNSORTED = 1000;
@@ -767,7 +770,8 @@ struct Pipeline {
         // reference recometrics.hpp:390-393
         min_items_pool = std::max(std::max(c.min_items_pool, K), 2);
         min_pos_test = std::min(c.min_pos_test, 1);
-        for (int i = 0; i < 10; i++) if (c.out[i]) req |= (1 << i);
+        if (c.reco) { min_items_pool = 1; min_pos_test = 0; }          // (lists for whoever has a candidate: k_classify's `reco`)
+        for (int i = 0; i < 10; i++) if (c.out[i] && !c.reco) req |= (1 << i);
         want_auc = req & (RQ_ROC | RQ_PR);
         NG = P::supported_ng(k);
         if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
@@ -793,7 +797,7 @@ struct Pipeline {
         heavy_users = (int *)ws.get("heavy_users", sizeof(int) * (size_t)m);
         ca = ClassifyArgs{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
                           flags, user_nslots, heavy_users, plan};
-        ca.only = c.only_users;
+        ca.only = c.only_users; ca.reco = c.reco ? 1 : 0;
         ca.heavy_npos = K > FIN_TOPV ? FIN_TOPV : HEAVY_NPOS;
         // the caller's CSR arrays are validated in front of everything that indexes by them (an out-of-range column index in
         // k_train_bits would be a memory fault; on the CPU reference it is a segfault): the index pointers by k_classify itself, the
@@ -840,8 +844,8 @@ struct Pipeline {
         // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
         // depends on K alone: it stays in the workspace, and only a longer one (or a moved buffer) is uploaded again -- the copy
         // comes from pageable memory, which blocks the host and waits for the stream
-        log2tab = (double *)ws.get("log2tab", sizeof(double) * (size_t)K);
-        if (cx.log2_ptr != (const void *)log2tab || cx.log2_K < K) {
+        if (!c.reco) log2tab = (double *)ws.get("log2tab", sizeof(double) * (size_t)K);
+        if (!c.reco && (cx.log2_ptr != (const void *)log2tab || cx.log2_K < K)) {
             std::vector<double> lt((size_t)K);
             for (int i = 0; i < K; i++) lt[i] = std::log2(i + 2);
             HIP_CHECK(hipMemcpy(log2tab, lt.data(), sizeof(double) * (size_t)K, hipMemcpyHostToDevice));       // (synchronous: `lt` is on the stack)
@@ -1007,7 +1011,8 @@ struct Pipeline {
     // ---- prep: the finalisation's arguments, operand packing, dense train rows, positives tables, seeds ----
     void prep()
     {
-        merged = (Entry<T> *)ws.get("merged", sizeof(Entry<T>) * (size_t)m * K);
+        // (recommendation lists: only k_collect_topk / k_select_topk go through `merged`; the lists in parts are merged into the caller's arrays)
+        if (!c.reco || want_lane || ext_topk) merged = (Entry<T> *)ws.get("merged", sizeof(Entry<T>) * (size_t)m * K);
         if (c.pos_rank) rank_sorted = (long long *)ws.get("rank_sorted", sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1));
         if (rank_sorted) HIP_CHECK(hipMemsetAsync(rank_sorted, 0, sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1), stream));
         // the argument block of the finalisation kernels is filled in as the pieces come into being
@@ -1247,6 +1252,49 @@ struct Pipeline {
         hipLaunchKernelGGL((k_finalize<T, T>), dim3(cdiv(s1 - s0, FIN_THREADS)), dim3(FIN_THREADS), fin_lds, stream, fa);
     }
 
+    // the ordered top-K of every user into `merged`, where the lists did not stay in parts: out of the sweep's lane buffers
+    // (k_collect_topk), or picked from the stored score rows (k_select_topk, k_metrics beyond the lists)
+    void collect_lists()
+    {
+        if (!collect) return;
+        // k_metrics beyond the LDS lists: the users' ordered top-K out of the sweep's lane buffers, straight into `merged` (behind
+        // k_merge_positives, whose part of `pl` -- the streamed users' own test items -- is one of the inputs)
+        fa.collected = 1;
+        const char *gl = (const char *)glists;
+        if (collect_capw(K, collect_g.lane_cap) == 512)
+            hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 512>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
+        else if (collect_capw(K, collect_g.lane_cap) == 1024)
+            hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 1024>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
+        else
+            hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 4096>), dim3(collect_grid(n_slots)), dim3(64), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
+    }
+    void select_lists()
+    {
+        if (!(n_slots > 0 && ext_topk)) return;
+        int sel_ld = 2;
+        while (sel_ld < K) sel_ld <<= 1;
+        fa.ext_topk = 1; fa.sel_ld = sel_ld;
+        fa.sel_hi = (unsigned long long *)ws.get("sel_hi", sizeof(unsigned long long) * (size_t)n_slots * sel_ld);
+        fa.sel_lo = (unsigned *)ws.get("sel_lo", sizeof(unsigned) * (size_t)n_slots * sel_ld);
+        hipLaunchKernelGGL((k_select_topk<T, T>), dim3(n_slots), dim3(SELECT_THREADS), 0, stream, fa);
+    }
+
+    // ---- finalize (recommendation lists): the lists and a status per user straight into the caller's arrays ----
+    void finalize_reco()
+    {
+        fa.n_part = g.n_part; fa.pl = pl; fa.pst = pst;
+        fa.stream_slot0 = stream_slot0; fa.stream_scores = stream_scores; fa.stream_ld = stream_ld;
+        collect_lists();
+        select_lists();
+        const bool merged_ready = n_slots > 0 && (collect || ext_topk);
+        RecoArgs<T> ra{m, n, K, g.n_part, flags, uslot_base, slot_index, c.train_p, pl, pst, merged_ready ? merged : nullptr,
+                       c.topk_idx, c.topk_score, c.status};
+        const size_t lds = reco_lds_bytes<T>(g.n_part, merged_ready);
+        if (lds > 48 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *)k_finalize_reco<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_finalize_reco<T>, dim3(cdiv(m, RECO_THREADS)), dim3(RECO_THREADS), lds, stream, ra);
+        HIP_CHECK(hipGetLastError());
+    }
+
     // ---- finalize: merge, streamed ranks and AUC, top-K collection / selection, the metrics ----
     void finalize()
     {
@@ -1283,26 +1331,8 @@ struct Pipeline {
             HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[3], 0));
             side.pending--;
         }
-        if (collect) {
-            // k_metrics beyond the LDS lists: the users' ordered top-K out of the sweep's lane buffers, straight into `merged` (behind
-            // k_merge_positives, whose part of `pl` -- the streamed users' own test items -- is one of the inputs)
-            fa.collected = 1;
-            const char *gl = (const char *)glists;
-            if (collect_capw(K, collect_g.lane_cap) == 512)
-                hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 512>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
-            else if (collect_capw(K, collect_g.lane_cap) == 1024)
-                hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 1024>), dim3(collect_grid(cdiv(n_slots, 4))), dim3(256), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
-            else
-                hipLaunchKernelGGL((k_collect_topk<T, T, ThrT, 4096>), dim3(collect_grid(n_slots)), dim3(64), 0, stream, fa, collect_g, gl, lane_cnt, (const ThrT *)thr_shared);
-        }
-        if (n_slots > 0 && ext_topk) {
-            int sel_ld = 2;
-            while (sel_ld < K) sel_ld <<= 1;
-            fa.ext_topk = 1; fa.sel_ld = sel_ld;
-            fa.sel_hi = (unsigned long long *)ws.get("sel_hi", sizeof(unsigned long long) * (size_t)n_slots * sel_ld);
-            fa.sel_lo = (unsigned *)ws.get("sel_lo", sizeof(unsigned) * (size_t)n_slots * sel_ld);
-            hipLaunchKernelGGL((k_select_topk<T, T>), dim3(n_slots), dim3(SELECT_THREADS), 0, stream, fa);
-        }
+        collect_lists();
+        select_lists();
         if (n_slots > 0) {
             if (want_auc) {
                 if (n_stream > 0 && !ranks_beside) { rank_streamed_rows(0, n_stream, stream); if (auc_launch) auc_streamed_rows(0, n_stream, stream); }
@@ -1330,7 +1360,7 @@ struct Pipeline {
     // ---- export: the ranking outputs of rm_rank_*, the context's events ----
     void export_ranks()
     {
-        if (c.topk_idx)
+        if (c.topk_idx && !c.reco)
             hipLaunchKernelGGL(k_export_rank<T>, dim3(cdiv((long long)m * K, 256)), dim3(256), 0, stream, m, K, merged, c.topk_idx, c.topk_score, flags);
         if (c.pos_rank)           // (per user, never a memset of the whole array: a batch must not clear what other batches wrote)
             hipLaunchKernelGGL(k_export_pos_rank, dim3(cdiv(m, 128)), dim3(128), 0, stream, c.nnz_test, m, c.test_p, flags, pos_order, rank_sorted, c.pos_rank,
@@ -1355,7 +1385,7 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
     p.g = sweep_geometry<T>(c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
     p.prep();
     p.sweep();
-    p.finalize();
+    if (c.reco) p.finalize_reco(); else p.finalize();
     p.export_ranks();
 }
 
@@ -1649,6 +1679,9 @@ template <class T> struct HostCall {              // one host-pointer call (refe
     int *topk_idx; T *topk_score; long long *pos_rank; int *status;
     unsigned long long seed;
     int nthreads = 0;                                 // host threads of the fall-back sort of unsorted CSR rows (0 = all)
+    // rm_recommend_*: `tep` is a row of zeros the entry made up (host-side bookkeeping only: nothing of a test matrix reaches the
+    // device), `topk_idx` / `topk_score` (optional) / `status` are the caller's idx / score / status, `pos_rank` is null
+    bool reco = false;
 };
 
 // item factors of a sharded call: uploaded from the host by shard 0, copied device-to-device (xGMI) by the others
@@ -1811,7 +1844,7 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     const long long nnz_tr = (long long)h.trp[u1] - tr0, nnz_te = (long long)h.tep[u1] - te0;
     T *dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
     int *dtrp = (int *)ws.get("in_trp", sizeof(int) * (size_t)(m + 1));
-    int *dtep = (int *)ws.get("in_tep", sizeof(int) * (size_t)(m + 1));
+    int *dtep = h.reco ? nullptr : (int *)ws.get("in_tep", sizeof(int) * (size_t)(m + 1));
     int *dtri = (int *)ws.get("in_tri", sizeof(int) * (size_t)std::max<long long>(nnz_tr, 1));
     int *dtei = (int *)ws.get("in_tei", sizeof(int) * (size_t)std::max<long long>(nnz_te, 1));
     T *dtev = h.tev ? (T *)ws.get("in_tev", sizeof(T) * (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
@@ -1823,15 +1856,15 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
         trp = rb.data(); tep = rb.data() + m + 1;
     }
     HIP_CHECK(hipMemcpyAsync(dtrp, trp, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
-    HIP_CHECK(hipMemcpyAsync(dtep, tep, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
+    if (dtep) HIP_CHECK(hipMemcpyAsync(dtep, tep, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
     const size_t per = h.cumulative ? (size_t)K : 1;                 // values per user of the eight top-K metrics
     size_t out_w = 0;                                               // values per user over all requested metrics
     for (int i = 0; i < 10; i++) if (h.outs[i]) out_w += i >= 8 ? 1 : per;
     int *d_topk_idx = nullptr, *d_status = nullptr; T *d_topk_score = nullptr; long long *d_pos_rank = nullptr;
     if (h.topk_idx) {
         d_topk_idx = (int *)ws.get("o_topk_idx", sizeof(int) * (size_t)m * K);
-        d_topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
-        d_pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
+        if (h.topk_score) d_topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
+        if (h.pos_rank) d_pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
         d_status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
     }
     const bool forced = g_sw.batch_users > 0;                        // tests: equal batches of this size
@@ -2066,13 +2099,14 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
         Call<T> c{};
         c.A = dA + (size_t)b0 * k; c.lda = k; c.B = dB; c.ldb = k; c.m = mb; c.n = n; c.k = k;
         c.train_p = dtrp + b0; c.train_i = dtri; c.nnz_train = nnz_tr;
-        c.test_p = dtep + b0; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
+        c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
         c.K = K; c.cumulative = h.cumulative; c.noise = h.noise; c.cold = h.cold; c.min_items_pool = h.mip; c.min_pos_test = h.mpt;
+        c.reco = h.reco;
         InFlight &f = fl[which];
         f.b0 = b0; f.mb = mb; f.bo = 0; f.which = which;
         for (int i = 0; i < 10; i++) { f.boff[i] = f.bo; c.out[i] = h.outs[i] ? dblocks[which] + f.bo : nullptr; if (h.outs[i]) f.bo += (size_t)mb * (i >= 8 ? 1 : per); }
         if (h.topk_idx) {
-            c.topk_idx = d_topk_idx + (size_t)b0 * K; c.topk_score = d_topk_score + (size_t)b0 * K;
+            c.topk_idx = d_topk_idx + (size_t)b0 * K; c.topk_score = d_topk_score ? d_topk_score + (size_t)b0 * K : nullptr;
             c.pos_rank = d_pos_rank; c.status = d_status + b0;
         }
         c.items_tag = tag;
@@ -2097,9 +2131,9 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
             if (bo) HIP_CHECK(hipMemcpyAsync(hblocks[which], dblocks[which], sizeof(T) * bo, hipMemcpyDeviceToHost, bs));
             if (h.topk_idx) {
                 HIP_CHECK(hipMemcpyAsync(h.topk_idx + ((size_t)u0 + b0) * K, c.topk_idx, sizeof(int) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
-                HIP_CHECK(hipMemcpyAsync(h.topk_score + ((size_t)u0 + b0) * K, c.topk_score, sizeof(T) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
+                if (h.topk_score) HIP_CHECK(hipMemcpyAsync(h.topk_score + ((size_t)u0 + b0) * K, c.topk_score, sizeof(T) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
                 HIP_CHECK(hipMemcpyAsync(h.status + u0 + b0, c.status, sizeof(int) * (size_t)mb, hipMemcpyDeviceToHost, bs));
-                if (e1 > e0) HIP_CHECK(hipMemcpyAsync(h.pos_rank + te0 + e0, c.pos_rank + e0, sizeof(long long) * (size_t)(e1 - e0), hipMemcpyDeviceToHost, bs));
+                if (h.pos_rank && e1 > e0) HIP_CHECK(hipMemcpyAsync(h.pos_rank + te0 + e0, c.pos_rank + e0, sizeof(long long) * (size_t)(e1 - e0), hipMemcpyDeviceToHost, bs));
             }
         };
         f.copy_out();
@@ -2252,7 +2286,7 @@ void run_host(const HostCall<T> &h)
 {
     try { run_host_once<T>(h); return; }
     catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; }
-    if (h.topk_idx) throw RmError{RM_ERR_INVALID, "rm_rank_*: the CSR rows must be sorted (pos_rank is indexed by the caller's entry order)"};
+    if (h.topk_idx && !h.reco) throw RmError{RM_ERR_INVALID, "rm_rank_*: the CSR rows must be sorted (pos_rank is indexed by the caller's entry order)"};
     const size_t nnz_tr = (size_t)h.trp[h.m], nnz_te = (size_t)h.tep[h.m];
     std::vector<int> tri(h.tri, h.tri + nnz_tr), tei(h.tei, h.tei + nnz_te);
     std::vector<T> tev;
@@ -2277,7 +2311,7 @@ void run_dev(Call<T> c, hipStream_t stream, Ctx &cx)
     std::vector<int> trp(m1), tep(m1), tri(std::max<size_t>(nnz_tr, 1)), tei(std::max<size_t>(nnz_te, 1));
     std::vector<T> tev(c.test_v ? std::max<size_t>(nnz_te, 1) : 0);
     HIP_CHECK(hipMemcpyAsync(trp.data(), c.train_p, sizeof(int) * m1, hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(tep.data(), c.test_p, sizeof(int) * m1, hipMemcpyDeviceToHost, stream));
+    if (c.test_p) HIP_CHECK(hipMemcpyAsync(tep.data(), c.test_p, sizeof(int) * m1, hipMemcpyDeviceToHost, stream));      // (none: recommendation lists -- `tep` stays zero)
     if (nnz_tr) HIP_CHECK(hipMemcpyAsync(tri.data(), c.train_i, sizeof(int) * nnz_tr, hipMemcpyDeviceToHost, stream));
     if (nnz_te) HIP_CHECK(hipMemcpyAsync(tei.data(), c.test_i, sizeof(int) * nnz_te, hipMemcpyDeviceToHost, stream));
     if (c.test_v && nnz_te) HIP_CHECK(hipMemcpyAsync(tev.data(), c.test_v, sizeof(T) * nnz_te, hipMemcpyDeviceToHost, stream));
@@ -2338,6 +2372,57 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
     dispatch_sweep(false, true, false, 2, NG, dim3(n_ublocks), P::lds_b(NG) + SYNC_BYTES, stream, sa);
     HIP_CHECK(hipMemcpyAsync(out, dump, sizeof(T) * (size_t)m * n, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// ---- recommendation lists: rm_recommend_* ---------------------------------------------------------------------------------
+// The metric call's pipeline in its `reco` mode (Call::reco: k_classify without a test matrix, the sweep without positives,
+// k_finalize_reco).  `xp == NULL`: nothing is excluded -- the index pointers become a row of zeros.
+inline void validate_recommend(const void *A, const void *B, int m, int n, int k, int K, size_t lda, size_t ldb, const void *idx, const void *status)
+{
+    if (m < 0 || n <= 0 || k <= 0) throw RmError{RM_ERR_INVALID, "m, n, k must be positive"};
+    if (!A || !B) throw RmError{RM_ERR_INVALID, "null input pointer"};
+    if (!idx || !status) throw RmError{RM_ERR_INVALID, "null output pointer"};
+    if (K < 1 || K > n) throw RmError{RM_ERR_INVALID, "k_top must lie in [1, n] (got " + std::to_string(K) + " with " + std::to_string(n) + " items)"};
+    if (lda < (size_t)k || ldb < (size_t)k) throw RmError{RM_ERR_INVALID, "leading dimension smaller than k"};
+}
+template <class T>
+void recommend_host(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, int k, const int *xp, const int *xi, int K,
+                    int *idx, T *score, int *status, int nthreads)
+{
+    if (m == 0) return;
+    validate_recommend(A, B, m, n, k, K, lda, ldb, idx, status);
+    const std::vector<int> zeros((size_t)m + 1, 0);
+    HostCall<T> h{A, lda, B, ldb, m, n, k, xp ? xp : zeros.data(), xp ? xi : nullptr, zeros.data(), nullptr, nullptr, K, false, false,
+                  {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, true, 1, 0,
+                  idx, score, nullptr, status, 0};
+    h.nthreads = nthreads > 0 ? nthreads : 0;
+    h.reco = true;
+    run_host<T>(h);
+}
+template <class T>
+void recommend_dev(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, int k, const int *xp, const int *xi, long long nnz, int K,
+                   int *idx, T *score, int *status, hipStream_t stream)
+{
+    if (m == 0) return;
+    validate_recommend(A, B, m, n, k, K, lda, ldb, idx, status);
+    if (xp && nnz > 0 && !xi) throw RmError{RM_ERR_INVALID, "null input pointer"};
+    if (nnz < 0) throw RmError{RM_ERR_INVALID, "negative length of the index array"};
+    Call<T> c{};
+    c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.m = m; c.n = n; c.k = k;
+    c.train_p = xp; c.train_i = xi; c.nnz_train = xp ? nnz : 0;
+    c.K = K; c.cold = true; c.min_items_pool = 1; c.min_pos_test = 0;
+    c.topk_idx = idx; c.topk_score = score; c.status = status; c.reco = true;
+    c.seed = 0; c.user0 = 0;
+    Ctx &cx = context(0);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
+    if (!xp) {
+        int *z = (int *)cx.ws.get("reco_zero_p", sizeof(int) * ((size_t)m + 1));
+        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // (an earlier call on another stream may still read it)
+        HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)m + 1), stream));
+        c.train_p = z; c.train_i = z;
+    }
+    run_dev<T>(c, stream, cx);
 }
 
 } // namespace
@@ -2412,6 +2497,26 @@ extern "C" int rm_rank_##SUFFIX(                                                
 
 RM_HOST_ENTRY(f32, float)
 RM_HOST_ENTRY(f64, double)
+
+#define RM_RECOMMEND_ENTRY(SUFFIX, T)                                                                                   \
+extern "C" int rm_recommend_##SUFFIX(                                                                                   \
+    const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
+    int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
+{                                                                                                                       \
+    return guarded([&] { recommend_host<T>(A, lda, B, ldb, m, n, k, Xexcl_csr_p, Xexcl_csr_i, k_top, idx, score, status, nthreads); }); \
+}                                                                                                                       \
+extern "C" int rm_recommend_dev_##SUFFIX(                                                                               \
+    const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
+    int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
+{                                                                                                                       \
+    return guarded([&] { recommend_dev<T>(A, lda, B, ldb, m, n, k, Xexcl_csr_p, Xexcl_csr_i, (long long)nnz_excl, k_top, idx, score, status, \
+                                          (hipStream_t)stream); });                                                     \
+}
+
+RM_RECOMMEND_ENTRY(f32, float)
+RM_RECOMMEND_ENTRY(f64, double)
 
 extern "C" int rm_debug_scores_f32(const float *A, size_t lda, const float *B, size_t ldb, int32_t m, int32_t n, int32_t k, float *out)
 {

@@ -25,6 +25,8 @@ struct ClassifyArgs {
     int check_ptr;               // 1 = validate the index pointers of every row here (first pass of a call over these users)
     int heavy_npos;              // test rows longer than this are listed in `heavy_users` (HEAVY_NPOS; FIN_TOPV when k_metrics is beyond k_finalize's buffer)
     long long nnz_train, nnz_test;
+    int reco;                    // 1 = recommendation lists (rm_recommend_*): there is no test matrix (`test_p` is null and never read); every
+                                 //     user with at least one candidate is active, one slot, depth class 0, UF_KLEQN when it has no more than K
 };
 
 __device__ __forceinline__ int chunk_depth(int pc)      // smallest j with 2^j - 1 >= pc   (pc in 1..63)
@@ -102,8 +104,10 @@ __global__ __launch_bounds__(1024) void k_check_csr_starts(int m, const int *tra
     if (u >= 1 && u < m) {
         const int s = train_p[u], e1 = train_p[m], e0 = train_p[0];
         if (train_p[u - 1] < s && s > e0 && s < e1) d0 = train_i[s - 1] > train_i[s];
-        const int t = test_p[u], f1 = test_p[m], f0 = test_p[0];
-        if (test_p[u - 1] < t && t > f0 && t < f1) d1 = test_i[t - 1] > test_i[t];
+        if (test_p) {
+            const int t = test_p[u], f1 = test_p[m], f0 = test_p[0];
+            if (test_p[u - 1] < t && t > f0 && t < f1) d1 = test_i[t - 1] > test_i[t];
+        }
     }
     const unsigned long long b0 = __ballot(d0), b1 = __ballot(d1);
     if ((threadIdx.x & 63) == 0) {
@@ -125,7 +129,7 @@ __global__ void k_classify(ClassifyArgs a)
     if (skip) { a.flags[u] = UF_SKIP; a.user_nslots[u] = 0; }
     int ntr = 0, npos = 0;
     if (live) {
-        const int a0 = a.train_p[u], a1 = a.train_p[u + 1], b0 = a.test_p[u], b1 = a.test_p[u + 1];
+        const int a0 = a.train_p[u], a1 = a.train_p[u + 1], b0 = a.reco ? 0 : a.test_p[u], b1 = a.reco ? 0 : a.test_p[u + 1];
         if (a.check_ptr && (a0 < 0 || a1 < a0 || (long long)a1 > a.nnz_train || b0 < 0 || b1 < b0 || (long long)b1 > a.nnz_test)) {
             atomicOr(&a.plan->csr_bad, CSR_BAD_INDPTR); a.plan->csr_where = u;
         } else { ntr = a1 - a0; npos = b1 - b0; }
@@ -133,9 +137,10 @@ __global__ void k_classify(ClassifyArgs a)
     const int cand = a.n - ntr;
     bool isnan_user = !live || npos <= 0 || (ntr + npos >= a.n && !(a.req & RQ_NDCG)) || cand < a.min_items_pool ||
                       (!a.cold && ntr == 0) || npos < a.min_pos_test;
-    const bool only_ndcg = (ntr + npos) >= a.n;
+    if (a.reco) isnan_user = !live || cand < 1;                     // whoever has a candidate is served
+    const bool only_ndcg = !a.reco && (ntr + npos) >= a.n;
     const bool kleqn = cand <= a.K;
-    if (!isnan_user && kleqn && !(a.req & (RQ_ROC | RQ_PR | RQ_AP | RQ_TAP | RQ_RR))) isnan_user = true;
+    if (!a.reco && !isnan_user && kleqn && !(a.req & (RQ_ROC | RQ_PR | RQ_AP | RQ_TAP | RQ_RR))) isnan_user = true;
     int f = 0, nsl = 0, myclass = -1, nfull = 0;
     if (isnan_user) f = UF_NAN;
     else {
@@ -277,7 +282,7 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void k_assign_slots(AssignArgs a)
     if (threadIdx.x == N_CLASSES) blk_chunks = 0;
     __syncthreads();
     const int nsl = u < a.m ? a.user_nslots[u] : 0;
-    const int npos = nsl ? a.test_p[u + 1] - a.test_p[u] : 0;
+    const int npos = (nsl && a.test_p) ? a.test_p[u + 1] - a.test_p[u] : 0;      // (no test matrix: recommendation lists)
     int ubase = 0;
     if (u < a.m) {                                                // the scan's last step, in place: every later reader sees final values
         ubase = a.uslot_base[u] + (a.tile_offset ? a.tile_offset[u >> 10] : 0);
