@@ -123,6 +123,17 @@ struct Workspace {
         bufs.clear();
     }
 };
+// The page-locked words of a context through which the counts of the fp32 tie noise come back from the device (one 64-byte
+// allocation per context, Ctx::need_noise_words)
+struct NoiseWords {
+    int first_early;         // users flagged when a first pass launches its sweep (Call::flag_count_host; for the last batch of a host
+                             // call it is the word of the RANGE's context, also when that batch runs on the peer context)
+    int first_final;         // ... and after that pass's k_finalize (run_call)
+    int sequential;          // flagged users as a sequential exact pass counts them (noise_exact_pass)
+    int range_early;         // host entry: flagged users of the range as the pass beside the last batch counts them
+    int batch_flagged;       // host entry: users the first pass of a batch on this context flagged
+};
+static_assert(sizeof(NoiseWords) <= 64, "the noise words share one 64-byte page-locked allocation");
 // One context per (device, shard slot): the cached workspace plus the events / side stream that belong to that device.
 // Slot 0 serves ordinary calls; a call sharded inside the library (rm_set_devices) uses slot i for the i-th entry of the device
 // list, so that the same physical device can appear more than once ("virtual shards").  A context is used by ONE call at a
@@ -142,7 +153,14 @@ struct Ctx {
     hipStream_t own_stream = nullptr;        // stream of a shard worker (multi-device calls)
     hipStream_t up_stream = nullptr;         // host-pointer calls: uploads of the NEXT user batch run beside the current batch's kernels
     hipEvent_t up_ev[2] = {nullptr, nullptr};
-    int *pinned_small = nullptr; hipEvent_t flags_ev = nullptr, pass_ev = nullptr;   // tie noise: flag count read-back, flags ready, exact pass done
+    NoiseWords *noise_words = nullptr; hipEvent_t flags_ev = nullptr, pass_ev = nullptr;   // tie noise: flag counts read back, flags ready, exact pass done
+    void need_noise_words()                    // (the words and the two events are created together, once per context)
+    {
+        if (noise_words) return;
+        HIP_CHECK(hipHostMalloc((void **)&noise_words, 64, hipHostMallocDefault));
+        HIP_CHECK(hipEventCreateWithFlags(&flags_ev, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&pass_ev, hipEventDisableTiming));
+    }
     void *pinned = nullptr; size_t pinned_bytes = 0;   // page-locked staging for the metric block of a batch (one D2H copy instead of ten)
     void *pinned_get(size_t bytes)
     {
@@ -248,6 +266,29 @@ template <class T> struct Call {          // one calc_metrics call; every pointe
     // list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
     bool reco = false;
 };
+// Layout of the ten metrics of a call (Call::out): the eight top-K metrics have `per` values per user (k_metrics when cumulative,
+// else one), the two AUCs one.  The requested metrics of one user, packed, are a RECORD (what k_noise_gather writes); those of
+// `users` users, metric by metric -- [metric][users x width] --, a BLOCK (what a batch of the host entry leaves the device as).
+struct MetricLayout {
+    bool want[10]; size_t per, rec_off[10], rec_w = 0;                // metric requested; offset in a record; values per record
+    template <class P> MetricLayout(P *const *outs, size_t per_) : per(per_)
+    {
+        for (int i = 0; i < 10; i++) { want[i] = outs[i] != nullptr; rec_off[i] = rec_w; if (want[i]) rec_w += width(i); }
+    }
+    size_t width(int i) const { return i >= 8 ? 1 : per; }
+    size_t block_off(int i, size_t users) const { return rec_off[i] * users; }
+    size_t block_size(size_t users) const { return rec_w * users; }
+    // the outputs of a call whose metric block of `users` users starts at `block`
+    template <class T> void point_at(T *block, size_t users, T **out) const { for (int i = 0; i < 10; i++) out[i] = want[i] ? block + block_off(i, users) : nullptr; }
+};
+// what makes a pass an EXACT pass of the fp32 tie noise: `rows` users (those marked in `only`), each with its row of noise in E
+template <class T>
+inline void set_exact_pass(Call<T> &c, const unsigned char *only, const int *noise_row, int row0, const T *E, long long ld, int rows)
+{
+    c.only_users = only; c.noise_row = noise_row; c.noise_row0 = row0; c.noise_E = E; c.noise_ld = ld; c.eval_users = rows;
+    c.noise_flag = nullptr; c.first_pass_flags = nullptr; c.flag_snapshot = nullptr;
+    c.csr_checked = true;                                            // (the first pass looked at every row)
+}
 // internal status: some CSR row is not sorted (the entry points sort a copy of the rows and run again; never returned to a caller)
 constexpr int RM_INTERNAL_UNSORTED = 1000;
 
@@ -1450,9 +1491,9 @@ int noise_exact_pass(const Call<T> &c0, const int *flag, const int *skip, int n_
     hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, flag, skip, noise_row, row_user, counter);
     int n_flagged = n_known;
     if (n_known < 0) {
-        HIP_CHECK(hipMemcpyAsync(cx.pinned_small + 2, counter, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(&cx.noise_words->sequential, counter, sizeof(int), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        n_flagged = cx.pinned_small[2];
+        n_flagged = cx.noise_words->sequential;
     }
     if (row_user_out) *row_user_out = row_user;
     for (long long r0 = 0; r0 < n_flagged; r0 += g.cap) {
@@ -1462,14 +1503,90 @@ int noise_exact_pass(const Call<T> &c0, const int *flag, const int *skip, int n_
         T *E = (T *)ws.get("noise_rows", sizeof(T) * (size_t)rows * (size_t)g.e_ld);
         noise_make_rows<T>(cx, c0, g, row_user + r0, rows, c0.train_p, c0.user0, D, E, stream);
         Call<T> c = c0;
-        c.only_users = only; c.noise_row = noise_row; c.noise_row0 = (int)r0; c.noise_E = E; c.noise_ld = g.e_ld; c.noise_flag = nullptr;
-        c.first_pass_flags = nullptr; c.flag_snapshot = nullptr;
-        c.eval_users = rows;
-        c.csr_checked = true;                                        // (the first pass looked at every row)
+        set_exact_pass<T>(c, only, noise_row, (int)r0, E, g.e_ld, rows);
         run<T>(c, stream, cx);
     }
     return n_flagged;
 }
+
+// The exact pass of the fp32 tie noise BESIDE a running sweep: the users flagged by the time a first pass launches its sweep (every
+// user with a TEST item in the noise zone) are evaluated on the NOISE_SLOT context of `cx` and its high-priority stream, into
+// buffers of that context.  What the two callers share lives here -- run_call (device entry, un-ranged batches) and the host entry
+// (beside the last batch of a range); each brings its count, its dense train rows and its output pointers, calls the steps in
+// order (open, assign, rows, run_pass) and delivers the results itself.
+template <class T> struct NoiseBeside {
+    Ctx &cx;                                                         // whose `flags_ev` the pass waits for; g_last_ctx again afterwards
+    Ctx *pc = nullptr; hipStream_t ps = nullptr;                     // the NOISE_SLOT context, its stream
+    std::unique_lock<std::mutex> lock;                               // ... and its mutex, held until this object goes
+    int *noise_row = nullptr, *row_user = nullptr; unsigned char *only = nullptr;
+    explicit NoiseBeside(Ctx &c) : cx(c) {}
+    void open(hipEvent_t other = nullptr)
+    {
+        pc = &peer_context(cx, NOISE_SLOT);
+        lock = std::unique_lock<std::mutex>(pc->mu);
+        if (!pc->own_stream) HIP_CHECK(create_stream(&pc->own_stream, pc->high_priority));
+        ps = pc->own_stream;
+        HIP_CHECK(hipStreamWaitEvent(ps, cx.flags_ev, 0));           // flags, their snapshot and the dense train rows are in place
+        if (other) HIP_CHECK(hipStreamWaitEvent(ps, other, 0));
+    }
+    // A row for every user flagged in `flags` [m].  `known` > 0: their number; else they are counted on the pass's stream and the
+    // count is read back through `*word` (one wait for that stream).  Returns the number.
+    int assign(int m, const int *flags, int known, int *word)
+    {
+        Workspace &pw = pc->ws;
+        noise_row = (int *)pw.get("noise_row", sizeof(int) * (size_t)m);
+        row_user = (int *)pw.get("noise_row_user", sizeof(int) * (size_t)(known > 0 ? known : m));
+        int *counter = (int *)pw.get("noise_counter", sizeof(int));
+        only = (unsigned char *)pw.get("noise_only", (size_t)m);
+        HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(int), ps));
+        hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, flags, (const int *)nullptr, noise_row, row_user, counter);
+        if (known > 0) return known;
+        HIP_CHECK(hipMemcpyAsync(word, counter, sizeof(int), hipMemcpyDeviceToHost, ps));
+        HIP_CHECK(hipStreamSynchronize(ps));
+        return *word;
+    }
+    // The noise rows of the `rows_n` flagged users and the fields of their exact pass in `c` (a call over all m users).  Dense train
+    // rows: the first pass's when `cx` still holds them for exactly these users, or with `own_rows` rows built here for the
+    // flagged users alone (train items only; fp32, when they fit the PEER workspace).
+    void rows(Call<T> &c, const NoiseGeom<T> &g, int rows_n, bool own_rows)
+    {
+        Workspace &pw = pc->ws;
+        const int m = c.m, n = c.n;
+        hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, noise_row, 0, rows_n, only);
+        unsigned *D = (unsigned *)pw.get("noise_draws", sizeof(unsigned) * (size_t)rows_n * (size_t)g.d_ld);
+        T *E = (T *)pw.get("noise_rows", sizeof(T) * (size_t)rows_n * (size_t)g.e_ld);
+        const long long words = dense_row_words(n);
+        unsigned *bits = nullptr;
+        if (own_rows) {
+            const bool fit = std::is_same<T, float>::value && dense_rows_fit(pw, m, n);
+            if (fit) {
+                bits = (unsigned *)pw.get("train_bits", (size_t)m * (size_t)words * 4);
+                pc->bits_tag = 0; pc->bits_ptr = nullptr;
+                launch_train_bits(ps, m, n, (int)words, c.train_p, c.train_i, (const int *)nullptr, c.test_i, bits, (const Plan *)nullptr, only);
+                c.ext_bits = bits; c.ext_words = words; c.ext_masked = false;
+            }
+            c.dense_fit = fit ? 1 : 0;
+        } else if (cx.bits_tag != 0 && cx.bits_tag == c.items_tag && cx.bits_train_p == c.train_p && cx.bits_m == m && !cx.bits_partial) {
+            c.ext_bits = (const unsigned *)cx.bits_ptr; c.ext_words = cx.bits_words; c.ext_masked = cx.bits_masked;      // the first pass's rows
+        }
+        noise_make_rows<T>(own_rows ? *pc : cx, c, g, row_user, rows_n, c.train_p, c.user0, D, E, ps, bits, words);
+        set_exact_pass<T>(c, only, noise_row, 0, E, g.e_ld, rows_n);
+    }
+    void run_pass(const Call<T> &c)
+    {
+        // (whatever fails in there -- the peer context duplicates workspace under memory pressure --, nothing of it may still be
+        // reading this context's buffers (flag snapshot, dense train rows, A / B) when the error reaches the caller)
+        try { run<T>(c, ps, *pc); }
+        catch (...) {
+            sync();
+            if (pc->side_stream) (void)hipStreamSynchronize(pc->side_stream);
+            g_last_ctx = &cx;
+            throw;
+        }
+        g_last_ctx = &cx;                                            // rm_get_timings reports the main pass, not the small exact one
+    }
+    void sync() { if (pc) (void)hipStreamSynchronize(ps); }
+};
 
 // `defer` (host-pointer calls in user batches): the fp32 noise path ends with a look at what the first pass flagged on top of the
 // users evaluated beside it -- a wait for the whole batch.  With `defer` that tail is handed back instead of run: the caller
@@ -1484,11 +1601,7 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     if (c0.items_tag == 0) c0.items_tag = g_call_counter.fetch_add(1);                   // (a device-pointer call: its passes share B)
     Workspace &ws = cx.ws;
     const int m = c0.m;
-    if (!cx.pinned_small) {
-        HIP_CHECK(hipHostMalloc((void **)&cx.pinned_small, 64, hipHostMallocDefault));
-        HIP_CHECK(hipEventCreateWithFlags(&cx.flags_ev, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&cx.pass_ev, hipEventDisableTiming));
-    }
+    cx.need_noise_words();
     if (sizeof(T) == 4 && c0.first_pass_flags) {                    // a batch of a host-pointer call: see Call::first_pass_flags
         Call<T> c1 = c0;
         c1.noise_flag = c0.first_pass_flags;
@@ -1497,28 +1610,20 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     }
     if (sizeof(T) == 4 && c0.dense_fit < 0) c0.dense_fit = dense_rows_fit(ws, m, c0.n) ? 1 : 0;
     const NoiseGeom<T> g(ws, c0.n);
-    const long long e_ld = g.e_ld, d_ld = g.d_ld, cap = g.cap;
-    auto make_rows_into = [=, &cx](const int *row_user, int rows, const int *train_p, long long user0, unsigned *D, T *E, hipStream_t st) {
-        noise_make_rows<T>(cx, c0, g, row_user, rows, train_p, user0, D, E, st);
-    };
-    auto make_rows = [=, &ws](const int *row_user, int rows, const int *train_p, long long user0, unsigned *&D, T *&E) {
-        D = (unsigned *)ws.get("noise_draws", sizeof(unsigned) * (size_t)rows * (size_t)d_ld);
-        E = (T *)ws.get("noise_rows", sizeof(T) * (size_t)rows * (size_t)e_ld);
-        make_rows_into(row_user, rows, train_p, user0, D, E, stream);
-    };
+    const MetricLayout lay(c0.out, c0.cumulative ? (size_t)c0.K : 1);
     if (sizeof(T) == 8) {
         if (!c0.csr_checked) { check_csr_now<T>(c0, stream, cx); c0.csr_checked = true; }     // (the noise rows below index by the CSR arrays)
-        const long long width = c0.cumulative ? c0.K : 1;
-        for (long long b0 = 0; b0 < m; b0 += cap) {
-            const int mb = (int)std::min<long long>(cap, m - b0);
+        for (long long b0 = 0; b0 < m; b0 += g.cap) {
+            const int mb = (int)std::min<long long>(g.cap, m - b0);
             Call<T> c = c0;
             c.A = c0.A + (size_t)b0 * c0.lda; c.m = mb; c.train_p = c0.train_p + b0; c.test_p = c0.test_p + b0; c.user0 = c0.user0 + b0;
-            for (int i = 0; i < 10; i++) if (c0.out[i]) c.out[i] = c0.out[i] + (size_t)b0 * (i >= 8 ? 1 : width);
+            for (int i = 0; i < 10; i++) if (c0.out[i]) c.out[i] = c0.out[i] + (size_t)b0 * lay.width(i);
             if (c0.topk_idx) { c.topk_idx = c0.topk_idx + (size_t)b0 * c0.K; c.topk_score = c0.topk_score + (size_t)b0 * c0.K; c.status = c0.status + b0; }
             if (c0.only_users) c.only_users = c0.only_users + b0;
-            unsigned *D; T *E;
-            make_rows(nullptr, mb, c.train_p, c.user0, D, E);
-            c.noise_E = E; c.noise_ld = e_ld; c.noise_row = nullptr; c.noise_row0 = 0;
+            unsigned *D = (unsigned *)ws.get("noise_draws", sizeof(unsigned) * (size_t)mb * (size_t)g.d_ld);
+            T *E = (T *)ws.get("noise_rows", sizeof(T) * (size_t)mb * (size_t)g.e_ld);
+            noise_make_rows<T>(cx, c0, g, nullptr, mb, c.train_p, c.user0, D, E, stream);
+            c.noise_E = E; c.noise_ld = g.e_ld; c.noise_row = nullptr; c.noise_row0 = 0;
             run<T>(c, stream, cx);
         }
         return;
@@ -1537,76 +1642,42 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     int *snap = nullptr;
     if (beside) {
         snap = (int *)ws.get("noise_flag_snap", sizeof(int) * (size_t)m);
-        *cx.pinned_small = 0;
-        c1.flag_snapshot = snap; c1.flag_count_host = cx.pinned_small; c1.flags_event = cx.flags_ev;
+        cx.noise_words->first_early = 0;
+        c1.flag_snapshot = snap; c1.flag_count_host = &cx.noise_words->first_early; c1.flags_event = cx.flags_ev;
     }
+    Plan *plan = (Plan *)ws.get("plan", sizeof(Plan));
+    int n_beside = 0;
+    NoiseBeside<T> nb(cx);
+    run<T>(c1, stream, cx);
     // The exact pass beside the first sweep: enqueued right behind the first pass, on the NOISE_SLOT context's HIGH-PRIORITY streams
     // (create_stream) -- at normal priority its kernels would only be served when the sweep, which fills every compute unit, drains.
     // (Measured and dropped: enqueueing it from inside the first pass's run(), in front of the sweep's dispatch:
     // the host-side chain of the pass, two waits, keeps the sweep off the device for 0.8 ms.)
-    Plan *plan = (Plan *)ws.get("plan", sizeof(Plan));
-    int n_beside = 0;
-    std::unique_lock<std::mutex> peer_lock;
-    ScatterArgs<T> sc_keep{};
-    auto beside_pass = [&]() {
+    if (beside) {
         HIP_CHECK(hipEventSynchronize(cx.flags_ev));                 // (early: the sweep has only just been launched)
-        const int n_early = *cx.pinned_small;
-        if (n_early > 0 && n_early <= cap) {
-            Ctx &pc = peer_context(cx, NOISE_SLOT);
-            peer_lock = std::unique_lock<std::mutex>(pc.mu);
-            if (!pc.own_stream) HIP_CHECK(create_stream(&pc.own_stream, pc.high_priority));
-            hipStream_t ps = pc.own_stream;
-            Workspace &pw = pc.ws;
-            HIP_CHECK(hipStreamWaitEvent(ps, cx.flags_ev, 0));       // flags, their snapshot and the dense train rows are in place
-            int *noise_row = (int *)pw.get("noise_row", sizeof(int) * (size_t)m);
-            int *row_user = (int *)pw.get("noise_row_user", sizeof(int) * (size_t)n_early);
-            int *counter = (int *)pw.get("noise_counter", sizeof(int));
-            unsigned char *only = (unsigned char *)pw.get("noise_only", (size_t)m);
-            HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(int), ps));
-            hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, snap, (const int *)nullptr, noise_row, row_user, counter);
-            hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, noise_row, 0, n_early, only);
-            unsigned *D = (unsigned *)pw.get("noise_draws", sizeof(unsigned) * (size_t)n_early * (size_t)d_ld);
-            T *E = (T *)pw.get("noise_rows", sizeof(T) * (size_t)n_early * (size_t)e_ld);
-            make_rows_into(row_user, n_early, c0.train_p, c0.user0, D, E, ps);
+        const int n_early = cx.noise_words->first_early;
+        if (n_early > 0 && n_early <= g.cap) {
+            nb.open();
+            nb.assign(m, snap, n_early, nullptr);
             Call<T> c = c0;
-            const long long width = c0.cumulative ? c0.K : 1;
+            nb.rows(c, g, n_early, false);
             static const char *tnames[10] = {"t_p", "t_tp", "t_r", "t_ap", "t_tap", "t_ndcg", "t_hit", "t_rr", "t_roc", "t_pr"};
             ScatterArgs<T> sc{};
             for (int i = 0; i < 10; i++) {
-                sc.width[i] = i >= 8 ? 1 : (int)width;
+                sc.width[i] = (int)lay.width(i);
                 sc.dst[i] = c0.out[i];
-                c.out[i] = c0.out[i] ? (T *)pw.get(tnames[i], sizeof(T) * (size_t)m * (size_t)sc.width[i]) : nullptr;
+                c.out[i] = c0.out[i] ? (T *)nb.pc->ws.get(tnames[i], sizeof(T) * (size_t)m * lay.width(i)) : nullptr;
                 sc.src[i] = c.out[i];
             }
-            c.only_users = only; c.noise_row = noise_row; c.noise_row0 = 0; c.noise_E = E; c.noise_ld = e_ld; c.noise_flag = nullptr;
-            c.eval_users = n_early;
-            c.csr_checked = true;
-            if (cx.bits_tag != 0 && cx.bits_tag == c0.items_tag && cx.bits_train_p == c0.train_p && cx.bits_m == m && !cx.bits_partial) {
-                c.ext_bits = (const unsigned *)cx.bits_ptr; c.ext_words = cx.bits_words; c.ext_masked = cx.bits_masked;      // the first pass's rows
-            }
-            // (whatever fails in there -- the peer context duplicates workspace under memory pressure --, nothing of it may still be
-            // reading this context's buffers (flag snapshot, dense train rows, A / B) when the error reaches the caller)
-            try { run<T>(c, ps, pc); }
-            catch (...) {
-                (void)hipStreamSynchronize(ps);
-                if (pc.side_stream) (void)hipStreamSynchronize(pc.side_stream);
-                g_last_ctx = &cx;
-                throw;
-            }
-            g_last_ctx = &cx;                                        // rm_get_timings reports the main pass, not the small exact one
-            HIP_CHECK(hipEventRecord(cx.pass_ev, ps));
-            sc_keep = sc;
+            nb.run_pass(c);
+            HIP_CHECK(hipEventRecord(cx.pass_ev, nb.ps));
+            HIP_CHECK(hipStreamWaitEvent(stream, cx.pass_ev, 0));    // behind the first pass (stream order) AND the exact one
+            hipLaunchKernelGGL(k_noise_scatter<T>, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, snap, sc);
+            HIP_CHECK(hipEventRecord(cx.done, stream));              // (the context's "last work" now ends with the scatter)
             n_beside = n_early;
         }
-    };
-    run<T>(c1, stream, cx);
-    if (beside) beside_pass();
-    if (n_beside > 0) {
-        HIP_CHECK(hipStreamWaitEvent(stream, cx.pass_ev, 0));        // behind the first pass (stream order) AND the exact one
-        hipLaunchKernelGGL(k_noise_scatter<T>, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, snap, sc_keep);
-        HIP_CHECK(hipEventRecord(cx.done, stream));                  // (the context's "last work" now ends with the scatter)
     }
-    int *n_flagged_host = cx.pinned_small + 1;
+    int *n_flagged_host = &cx.noise_words->first_final;
     HIP_CHECK(hipMemcpyAsync(n_flagged_host, &plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, stream));
     auto tail = [=, &cx]() -> bool {
         HIP_CHECK(hipStreamSynchronize(stream));
@@ -1821,106 +1892,134 @@ template <class T> struct ItemUpload {
 // rows, so nothing is double-buffered.  The first batch is small (its upload is the only one nothing hides) and the batches
 // double in size from there; they are also what the interrupt flag is looked at between (reference :488-489).  Each batch's
 // outputs go straight into the caller's arrays.  `shared` (sharded calls) says where the item factors come from.
-template <class T>
-void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t stream, SharedItems *shared, int shard, unsigned long long tag)
-{
-    std::lock_guard<std::mutex> lk(cx.mu);
-    Workspace &ws = cx.ws;
-    const int m = u1 - u0, n = h.n, k = h.k, K = h.K;
-    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0; cx.ev_recorded = false;
-    g_last_ctx = &cx;
-    ItemUpload<T> items{h, shared, shard};         // (its destructor completes the handshake with the other shards, whatever happens below)
-    if (!cx.up_stream) {
-        HIP_CHECK(hipStreamCreateWithFlags(&cx.up_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&cx.up_ev[i], hipEventDisableTiming));
-    }
-    hipStream_t up = cx.up_stream;
-    if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(up, cx.done, 0));   // the previous call on this context may still read the buffers
-    // item factors, dense rows of k
-    T *dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
-    if (m <= 0) { items.run(dB, cx.device, up); HIP_CHECK(hipStreamSynchronize(up)); return; }
-    // this range's users: factors, CSR rows with the index pointers rebased to the range
-    const long long tr0 = h.trp[u0], te0 = h.tep[u0];
-    const long long nnz_tr = (long long)h.trp[u1] - tr0, nnz_te = (long long)h.tep[u1] - te0;
-    T *dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
-    int *dtrp = (int *)ws.get("in_trp", sizeof(int) * (size_t)(m + 1));
-    int *dtep = h.reco ? nullptr : (int *)ws.get("in_tep", sizeof(int) * (size_t)(m + 1));
-    int *dtri = (int *)ws.get("in_tri", sizeof(int) * (size_t)std::max<long long>(nnz_tr, 1));
-    int *dtei = (int *)ws.get("in_tei", sizeof(int) * (size_t)std::max<long long>(nnz_te, 1));
-    T *dtev = h.tev ? (T *)ws.get("in_tev", sizeof(T) * (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
-    std::vector<int> rb;                                              // rebased index pointers (only when the range does not start at 0)
-    const int *trp = h.trp + u0, *tep = h.tep + u0;
-    if (tr0 || te0) {
-        rb.resize(2 * (size_t)(m + 1));
-        for (int i = 0; i <= m; i++) { rb[i] = h.trp[u0 + i] - (int)tr0; rb[m + 1 + i] = h.tep[u0 + i] - (int)te0; }
-        trp = rb.data(); tep = rb.data() + m + 1;
-    }
-    HIP_CHECK(hipMemcpyAsync(dtrp, trp, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
-    if (dtep) HIP_CHECK(hipMemcpyAsync(dtep, tep, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
-    const size_t per = h.cumulative ? (size_t)K : 1;                 // values per user of the eight top-K metrics
-    size_t out_w = 0;                                               // values per user over all requested metrics
-    for (int i = 0; i < 10; i++) if (h.outs[i]) out_w += i >= 8 ? 1 : per;
-    int *d_topk_idx = nullptr, *d_status = nullptr; T *d_topk_score = nullptr; long long *d_pos_rank = nullptr;
-    if (h.topk_idx) {
-        d_topk_idx = (int *)ws.get("o_topk_idx", sizeof(int) * (size_t)m * K);
-        if (h.topk_score) d_topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
-        if (h.pos_rank) d_pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
-        d_status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
-    }
-    const bool forced = g_sw.batch_users > 0;                        // tests: equal batches of this size
-    const std::vector<long long> cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K), forced);
-    const int n_batches = (int)cuts.size() - 1;
-    long long mb_max = 0;
-    for (int bi = 0; bi < n_batches; bi++) mb_max = std::max(mb_max, cuts[bi + 1] - cuts[bi]);
-    // the metric block of a batch: [metric][users of the batch x width], one device buffer, one D2H copy into page-locked
-    // staging, scattered into the caller's arrays by the host (ten pageable copies cost 35-140 us EACH in host time)
-    // Batches alternate between this context and its peer (own workspace, events and stream): batch i + 1 is planned and
-    // packed while batch i sweeps, and its sweep takes over the compute units as batch i's blocks drain.
-    Ctx *ctxs[2] = {&cx, &cx};
-    hipStream_t streams[2] = {stream, stream};
+// One member function per stage; run_host_range() below is the sequence.
+template <class T> struct HostRange {
+    // a batch in flight on one of the two contexts (`tail`: what the fp32 tie noise still has to look at once the batch is through, run_call)
+    struct InFlight { bool on = false; long long b0 = 0; int mb = 0; std::function<bool()> tail; };
+    // Members are destroyed in reverse order of declaration, and these four must go in this order: the lock of the pass beside the
+    // last batch (in `bes`), the peer context's lock, the item upload's guard (shard 0 waits there for the other shards' copies of
+    // in_B) and last the range's own context.  `items` is constructed before anything that can throw: its destructor completes the
+    // handshake with the other shards, whatever happens.
+    std::lock_guard<std::mutex> lk;
+    ItemUpload<T> items;
     std::unique_lock<std::mutex> peer_lock;
-    // (not with k_metrics > 256: a batch is then sized by the score rows ONE context may hold -- a third of the free memory --
-    // and a second context holding as much again leaves the first one's next batch short: RM_ERR_NOMEM on the third batch)
-    const bool rows_bound = K > 256 || g_sw.ext_topk;             // (the lane buffers of k_metrics > 256 are as large)
-    if (n_batches > 1 && !rows_bound && !g_sw.one_context) {
-        Ctx &pc = peer_context(cx);
-        peer_lock = std::unique_lock<std::mutex>(pc.mu);
-        if (!pc.own_stream) HIP_CHECK(hipStreamCreateWithFlags(&pc.own_stream, hipStreamNonBlocking));
-        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(pc.own_stream, cx.done, 0));       // (buffers of the range may still be read by an earlier call)
-        ctxs[1] = &pc; streams[1] = pc.own_stream;
+    NoiseBeside<T> bes;
+    bool bes_ran = false; int bes_count = 0; T *bes_hx = nullptr; int *bes_hu = nullptr;     // what the pass beside the last batch left in page-locked memory
+
+    const HostCall<T> &h; const int u0, m, n, k, K; Ctx &cx; Workspace &ws; hipStream_t stream, up = nullptr;
+    SharedItems *shared; int shard; unsigned long long tag;
+    const MetricLayout lay;                                           // (per: values per user of the eight top-K metrics)
+    // stage_inputs()
+    long long tr0 = 0, te0 = 0, nnz_tr = 0, nnz_te = 0;
+    T *dB = nullptr, *dA = nullptr, *dtev = nullptr; int *dtrp = nullptr, *dtep = nullptr, *dtri = nullptr, *dtei = nullptr;
+    std::vector<int> rb;                                              // rebased index pointers (only when the range does not start at 0)
+    const int *trp = nullptr, *tep = nullptr;
+    int *d_topk_idx = nullptr, *d_status = nullptr; T *d_topk_score = nullptr; long long *d_pos_rank = nullptr;
+    // plan_batches()
+    std::vector<long long> cuts; int n_batches = 0;
+    Ctx *ctxs[2]; hipStream_t streams[2]; bool two_ctx = false;
+    T *dblocks[2] = {nullptr, nullptr}, *hblocks[2] = {nullptr, nullptr};
+    bool range_noise = false; int *range_flag = nullptr, *range_snap = nullptr;
+    // the batches
+    long long users_copied = 0;                                       // users [0, users_copied) of the range have been handed over to the caller
+    long long flagged_total = 0;                                      // fp32 tie noise over the range: users the batches' first passes flagged
+    InFlight fl[2];
+    // RM_HOST_TRACE (timing studies only): host-side time stamps of the pipeline, printed at the end of the call
+    std::vector<std::pair<const char *, double>> stamps; std::chrono::steady_clock::time_point t_start;
+    void stamp(const char *what) { if (g_sw.host_trace) stamps.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count()); }
+
+    HostRange(const HostCall<T> &h_, int u0_, int u1, Ctx &cx_, hipStream_t stream_, SharedItems *shared_, int shard_, unsigned long long tag_)
+        : lk(cx_.mu), items{h_, shared_, shard_}, bes(cx_), h(h_), u0(u0_), m(u1 - u0_), n(h_.n), k(h_.k), K(h_.K), cx(cx_), ws(cx_.ws), stream(stream_),
+          shared(shared_), shard(shard_), tag(tag_), lay(h_.outs, h_.cumulative ? (size_t)h_.K : 1), ctxs{&cx_, &cx_}, streams{stream_, stream_}
+    {
+        cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0; cx.ev_recorded = false;
+        g_last_ctx = &cx;
     }
-    T *dblocks[2], *hblocks[2];
-    for (int i = 0; i < 2; i++) {
-        if (i == 1 && ctxs[1] == ctxs[0]) { dblocks[1] = dblocks[0]; hblocks[1] = hblocks[0]; break; }
-        dblocks[i] = (T *)ctxs[i]->ws.get("o_block", sizeof(T) * std::max<size_t>(out_w * (size_t)mb_max, 1));
-        hblocks[i] = out_w ? (T *)ctxs[i]->pinned_get(sizeof(T) * out_w * (size_t)mb_max) : nullptr;
+
+    // workspace buffers of the range, index pointers rebased to it and uploaded, ranking outputs; false = no user (the item factors' handshake only)
+    bool stage_inputs()
+    {
+        if (!cx.up_stream) {
+            HIP_CHECK(hipStreamCreateWithFlags(&cx.up_stream, hipStreamNonBlocking));
+            for (int i = 0; i < 2; i++) HIP_CHECK(hipEventCreateWithFlags(&cx.up_ev[i], hipEventDisableTiming));
+        }
+        up = cx.up_stream;
+        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(up, cx.done, 0));   // the previous call on this context may still read the buffers
+        // item factors, dense rows of k
+        dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
+        if (m <= 0) { items.run(dB, cx.device, up); HIP_CHECK(hipStreamSynchronize(up)); return false; }
+        // this range's users: factors, CSR rows with the index pointers rebased to the range
+        tr0 = h.trp[u0]; te0 = h.tep[u0];
+        nnz_tr = (long long)h.trp[u0 + m] - tr0; nnz_te = (long long)h.tep[u0 + m] - te0;
+        dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
+        dtrp = (int *)ws.get("in_trp", sizeof(int) * (size_t)(m + 1));
+        dtep = h.reco ? nullptr : (int *)ws.get("in_tep", sizeof(int) * (size_t)(m + 1));
+        dtri = (int *)ws.get("in_tri", sizeof(int) * (size_t)std::max<long long>(nnz_tr, 1));
+        dtei = (int *)ws.get("in_tei", sizeof(int) * (size_t)std::max<long long>(nnz_te, 1));
+        dtev = h.tev ? (T *)ws.get("in_tev", sizeof(T) * (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
+        trp = h.trp + u0; tep = h.tep + u0;
+        if (tr0 || te0) {
+            rb.resize(2 * (size_t)(m + 1));
+            for (int i = 0; i <= m; i++) { rb[i] = h.trp[u0 + i] - (int)tr0; rb[m + 1 + i] = h.tep[u0 + i] - (int)te0; }
+            trp = rb.data(); tep = rb.data() + m + 1;
+        }
+        HIP_CHECK(hipMemcpyAsync(dtrp, trp, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
+        if (dtep) HIP_CHECK(hipMemcpyAsync(dtep, tep, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
+        if (h.topk_idx) {
+            d_topk_idx = (int *)ws.get("o_topk_idx", sizeof(int) * (size_t)m * K);
+            if (h.topk_score) d_topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
+            if (h.pos_rank) d_pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
+            d_status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
+        }
+        return true;
     }
-    const bool two_ctx = ctxs[1] != ctxs[0];
-    // fp32 tie noise over several batches: every batch runs its first pass only and flags the users the noise can touch in its
-    // slice of `range_flag`; ONE exact pass over the flagged users of the whole range follows the last batch.  (Per batch, the
-    // exact pass costs two waits on the host -- for the flags, for its own plan -- during which the next batch is not enqueued:
-    // 14.6 ms against 10.2 without noise at BASELINE C2, profiles/r4_host_entry.txt.)  Not with the ranking outputs of rm_rank_*.
-    const bool range_noise = h.noise && std::is_same<T, float>::value && n_batches > 1 && !h.topk_idx &&
-                             !g_sw.noise_per_batch;
-    int *range_flag = nullptr, *range_snap = nullptr;
-    // ... and the users flagged by the time the LAST batch launches its sweep -- every user with a test item in the noise zone, in
-    // practice all of them -- are evaluated exactly BESIDE that sweep on a context of their own (`besides` below), as the device entry
-    // does (run_call); what remains behind the last batch is the host-side scatter of their values, and an exact pass over the few
-    // users only a batch's k_finalize flagged (a top-K score in the zone), usually none
-    const bool beside_last = range_noise;
-    if (range_noise) {
+
+    // the batches' boundaries, the second context and its lock, the metric block of a batch on either context, the flags of the tie noise
+    void plan_batches()
+    {
+        const bool forced = g_sw.batch_users > 0;                        // tests: equal batches of this size
+        cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K), forced);
+        n_batches = (int)cuts.size() - 1;
+        long long mb_max = 0;
+        for (int bi = 0; bi < n_batches; bi++) mb_max = std::max(mb_max, cuts[bi + 1] - cuts[bi]);
+        // the metric block of a batch: [metric][users of the batch x width], one device buffer, one D2H copy into page-locked
+        // staging, scattered into the caller's arrays by the host (ten pageable copies cost 35-140 us EACH in host time)
+        // Batches alternate between this context and its peer (own workspace, events and stream): batch i + 1 is planned and
+        // packed while batch i sweeps, and its sweep takes over the compute units as batch i's blocks drain.
+        // (not with k_metrics > 256: a batch is then sized by the score rows ONE context may hold -- a third of the free memory --
+        // and a second context holding as much again leaves the first one's next batch short: RM_ERR_NOMEM on the third batch)
+        const bool rows_bound = K > 256 || g_sw.ext_topk;             // (the lane buffers of k_metrics > 256 are as large)
+        if (n_batches > 1 && !rows_bound && !g_sw.one_context) {
+            Ctx &pc = peer_context(cx);
+            peer_lock = std::unique_lock<std::mutex>(pc.mu);
+            if (!pc.own_stream) HIP_CHECK(hipStreamCreateWithFlags(&pc.own_stream, hipStreamNonBlocking));
+            if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(pc.own_stream, cx.done, 0));       // (buffers of the range may still be read by an earlier call)
+            ctxs[1] = &pc; streams[1] = pc.own_stream;
+        }
+        for (int i = 0; i < 2; i++) {
+            if (i == 1 && ctxs[1] == ctxs[0]) { dblocks[1] = dblocks[0]; hblocks[1] = hblocks[0]; break; }
+            dblocks[i] = (T *)ctxs[i]->ws.get("o_block", sizeof(T) * std::max<size_t>(lay.block_size((size_t)mb_max), 1));
+            hblocks[i] = lay.rec_w ? (T *)ctxs[i]->pinned_get(sizeof(T) * lay.block_size((size_t)mb_max)) : nullptr;
+        }
+        two_ctx = ctxs[1] != ctxs[0];
+        // fp32 tie noise over several batches: every batch runs its first pass only and flags the users the noise can touch in its
+        // slice of `range_flag`; ONE exact pass over the flagged users of the whole range follows the last batch.  (Per batch, the
+        // exact pass costs two waits on the host -- for the flags, for its own plan -- during which the next batch is not enqueued:
+        // 14.6 ms against 10.2 without noise at BASELINE C2, profiles/r4_host_entry.txt.)  Not with the ranking outputs of rm_rank_*.
+        range_noise = h.noise && std::is_same<T, float>::value && n_batches > 1 && !h.topk_idx && !g_sw.noise_per_batch;
+        if (!range_noise) return;
+        // ... and the users flagged by the time the LAST batch launches its sweep -- every user with a test item in the noise zone, in
+        // practice all of them -- are evaluated exactly BESIDE that sweep on a context of their own (exact_beside_last), as the device entry
+        // does (run_call); what remains behind the last batch is the host-side scatter of their values, and an exact pass over the few
+        // users only a batch's k_finalize flagged (a top-K score in the zone), usually none
         range_flag = (int *)ws.get("noise_flag_range", sizeof(int) * (size_t)m);
         HIP_CHECK(hipMemsetAsync(range_flag, 0, sizeof(int) * (size_t)m, up));      // (in front of batch 0's rows: every batch waits for its rows' event)
-        if (beside_last) {
-            range_snap = (int *)ws.get("noise_flag_range_snap", sizeof(int) * (size_t)m);
-            if (!cx.pinned_small) {
-                HIP_CHECK(hipHostMalloc((void **)&cx.pinned_small, 64, hipHostMallocDefault));
-                HIP_CHECK(hipEventCreateWithFlags(&cx.flags_ev, hipEventDisableTiming));
-                HIP_CHECK(hipEventCreateWithFlags(&cx.pass_ev, hipEventDisableTiming));
-            }
-        }
+        range_snap = (int *)ws.get("noise_flag_range_snap", sizeof(int) * (size_t)m);
+        cx.need_noise_words();
     }
-    auto upload_users = [&](int bi) {                                 // rows [cuts[bi], cuts[bi + 1]) into their places, on `up`
+
+    void upload_users(int bi)                                         // rows [cuts[bi], cuts[bi + 1]) into their places, on `up`
+    {
         const long long b0 = cuts[bi], b1 = cuts[bi + 1];
         if (h.lda == (size_t)k) HIP_CHECK(hipMemcpyAsync(dA + (size_t)b0 * k, h.A + ((size_t)u0 + b0) * k, sizeof(T) * (size_t)(b1 - b0) * k, hipMemcpyHostToDevice, up));
         else HIP_CHECK(hipMemcpy2DAsync(dA + (size_t)b0 * k, sizeof(T) * k, h.A + ((size_t)u0 + b0) * h.lda, sizeof(T) * h.lda, sizeof(T) * k, (size_t)(b1 - b0),
@@ -1930,37 +2029,60 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
         if (e1 > e0) HIP_CHECK(hipMemcpyAsync(dtei + e0, h.tei + te0 + e0, sizeof(int) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
         if (dtev && e1 > e0) HIP_CHECK(hipMemcpyAsync(dtev + e0, h.tev + te0 + e0, sizeof(T) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
         HIP_CHECK(hipEventRecord(cx.up_ev[bi & 1], up));
-    };
-    // RM_HOST_TRACE (timing studies only): host-side time stamps of the pipeline, printed at the end of the call
-    const bool trace = g_sw.host_trace;
-    RM_TRACE_POINT("host entry: batches start");
-    std::vector<std::pair<const char *, double>> stamps;
-    const auto t_start = std::chrono::steady_clock::now();
-    auto stamp = [&](const char *what) { if (trace) stamps.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count()); };
+    }
     // shard 0 sends the item factors first (the other shards are waiting for them); the others send their own rows first
-    if (!shared || shard == 0) { items.run(dB, cx.device, up); stamp("items enqueued"); upload_users(0); }
-    else { upload_users(0); items.run(dB, cx.device, up); HIP_CHECK(hipEventRecord(cx.up_ev[0], up)); }
-    stamp("batch 0 rows enqueued");
-    // (`tail`: what the fp32 tie noise still has to look at once the batch is through, run_call; `copy_out`: the batch's device-to-host
-    // copies, enqueued behind the batch and once more when the tail rewrote outputs)
-    long long users_copied = 0;                                       // users [0, users_copied) of the range have been handed over to the caller
-    long long flagged_total = 0;                                      // fp32 tie noise over the range: users the batches' first passes flagged
-    struct InFlight { bool on = false; bool counts_flags = false; long long b0 = 0; int mb = 0; size_t boff[10]; size_t bo = 0; int which = 0;
-                      std::function<bool()> tail; std::function<void()> copy_out; } fl[2];
-    auto finish = [&](int which) {                                    // wait for the batch in flight on context `which`, hand its outputs over
+    void first_uploads()
+    {
+        RM_TRACE_POINT("host entry: batches start");
+        t_start = std::chrono::steady_clock::now();
+        if (!shared || shard == 0) { items.run(dB, cx.device, up); stamp("items enqueued"); upload_users(0); }
+        else { upload_users(0); items.run(dB, cx.device, up); HIP_CHECK(hipEventRecord(cx.up_ev[0], up)); }
+        stamp("batch 0 rows enqueued");
+    }
+    // users [b0, b0 + mb) of the range as a call on the staged arrays: everything but the outputs and the tie noise's flags
+    Call<T> batch_call(long long b0, int mb) const
+    {
+        Call<T> c{};
+        c.A = dA + (size_t)b0 * k; c.lda = k; c.B = dB; c.ldb = k; c.m = mb; c.n = n; c.k = k;
+        c.train_p = dtrp + b0; c.train_i = dtri; c.nnz_train = nnz_tr;
+        c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
+        c.K = K; c.cumulative = h.cumulative; c.noise = h.noise; c.cold = h.cold; c.min_items_pool = h.mip; c.min_pos_test = h.mpt;
+        c.reco = h.reco;
+        c.items_tag = tag; c.seed = h.seed; c.user0 = (long long)u0 + b0;
+        return c;
+    }
+    // the device-to-host copies of the batch in flight on context `which`, enqueued behind the batch and once more when its tail
+    // rewrote outputs
+    void copy_out(int which)
+    {
+        const long long b0 = fl[which].b0; const int mb = fl[which].mb;
+        Ctx &bc = *ctxs[which]; hipStream_t bs = streams[which];
+        const Plan *plan = (const Plan *)bc.ws.get("plan", sizeof(Plan));
+        // (`range_noise`: run_call ran on this context with the noise on, so the context has its words)
+        if (range_noise) HIP_CHECK(hipMemcpyAsync(&bc.noise_words->batch_flagged, &plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, bs));
+        if (lay.rec_w) HIP_CHECK(hipMemcpyAsync(hblocks[which], dblocks[which], sizeof(T) * lay.block_size((size_t)mb), hipMemcpyDeviceToHost, bs));
+        if (h.topk_idx) {
+            const long long e0 = tep[b0], e1 = tep[b0 + mb];          // this batch's test entries (range-relative)
+            HIP_CHECK(hipMemcpyAsync(h.topk_idx + ((size_t)u0 + b0) * K, d_topk_idx + (size_t)b0 * K, sizeof(int) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
+            if (h.topk_score) HIP_CHECK(hipMemcpyAsync(h.topk_score + ((size_t)u0 + b0) * K, d_topk_score + (size_t)b0 * K, sizeof(T) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
+            HIP_CHECK(hipMemcpyAsync(h.status + u0 + b0, d_status + b0, sizeof(int) * (size_t)mb, hipMemcpyDeviceToHost, bs));
+            if (h.pos_rank && e1 > e0) HIP_CHECK(hipMemcpyAsync(h.pos_rank + te0 + e0, d_pos_rank + e0, sizeof(long long) * (size_t)(e1 - e0), hipMemcpyDeviceToHost, bs));
+        }
+    }
+
+    void finish(int which)                                            // wait for the batch in flight on context `which`, hand its outputs over
+    {
         InFlight &f = fl[which];
         if (!f.on) return;
         f.on = false;
-        if (f.tail) { const bool again = f.tail(); f.tail = nullptr; if (again) f.copy_out(); }
+        if (f.tail) { const bool again = f.tail(); f.tail = nullptr; if (again) copy_out(which); }
         HIP_CHECK(hipStreamSynchronize(streams[which]));
         stamp("batch done");
-        for (int i = 0; i < 10; i++) {
-            const size_t w = i >= 8 ? 1 : per;
-            if (h.outs[i]) std::memcpy(h.outs[i] + ((size_t)u0 + f.b0) * w, hblocks[which] + f.boff[i], sizeof(T) * (size_t)f.mb * w);
-        }
+        for (int i = 0; i < 10; i++)
+            if (lay.want[i]) std::memcpy(h.outs[i] + ((size_t)u0 + f.b0) * lay.width(i), hblocks[which] + lay.block_off(i, (size_t)f.mb), sizeof(T) * (size_t)f.mb * lay.width(i));
         stamp("outputs scattered");
         users_copied = std::max<long long>(users_copied, f.b0 + f.mb);
-        if (f.counts_flags) flagged_total += ctxs[which]->pinned_small[5];
+        if (range_noise) flagged_total += ctxs[which]->noise_words->batch_flagged;
         if (n_batches > 1) {                                          // more than one batch: add up the stage timings
             Ctx &c = *ctxs[which];
             float ta = 0, tb = 0, tc = 0, td = 0;
@@ -1969,45 +2091,69 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
             cx.acc[0] += ta; cx.acc[1] += tb; cx.acc[2] += tc; cx.acc[3] += td;
             c.ev_recorded = false; cx.ev_recorded = false;
         }
-    };
-    // ---- fp32 tie noise over the whole range (see `range_noise` above) ----
-    auto range_call = [&]() {                                         // every user of the range, outputs not set
-        Call<T> c{};
-        c.A = dA; c.lda = k; c.B = dB; c.ldb = k; c.m = m; c.n = n; c.k = k;
-        c.train_p = dtrp; c.train_i = dtri; c.nnz_train = nnz_tr;
-        c.test_p = dtep; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
-        c.K = K; c.cumulative = h.cumulative; c.noise = true; c.cold = h.cold; c.min_items_pool = h.mip; c.min_pos_test = h.mpt;
-        c.items_tag = tag; c.seed = h.seed; c.user0 = (long long)u0;
-        c.csr_checked = true;                                         // (every batch has looked at its rows)
-        return c;
-    };
-    size_t x_off[10], x_bo = 0;                                       // layout of an exact pass's metric block: [metric][users of the range x width]
-    for (int i = 0; i < 10; i++) { x_off[i] = x_bo; if (h.outs[i]) x_bo += (size_t)m * (i >= 8 ? 1 : per); }
-    // an exact pass's results leave the device packed: one record of `out_w` values per evaluated user (k_noise_gather)
-    size_t rec_off[10], rec_w = 0;
-    for (int i = 0; i < 10; i++) { rec_off[i] = rec_w; if (h.outs[i]) rec_w += i >= 8 ? 1 : per; }
-    auto gather_exact = [&](Ctx &gc, const T *dx, const int *row_user, int count, hipStream_t st, T *&hx, int *&hu) {
-        GatherArgs<T> ga{};
-        for (int i = 0; i < 10; i++) { ga.src[i] = h.outs[i] ? dx + x_off[i] : nullptr; ga.width[i] = i >= 8 ? 1 : (int)per; ga.off[i] = (int)rec_off[i]; }
-        ga.out_w = (int)rec_w;
-        T *dg = (T *)gc.ws.get("o_exact_packed", sizeof(T) * rec_w * (size_t)count);
-        hipLaunchKernelGGL(k_noise_gather<T>, dim3(cdiv(count, 256)), dim3(256), 0, st, count, row_user, ga, dg);
-        hx = (T *)gc.pinned_get(sizeof(T) * rec_w * (size_t)count + sizeof(int) * (size_t)count);
-        hu = (int *)(hx + rec_w * (size_t)count);
-        HIP_CHECK(hipMemcpyAsync(hx, dg, sizeof(T) * rec_w * (size_t)count, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(hu, row_user, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
-    };
-    auto scatter_exact = [&](const T *hx, const int *hu, int count) {  // the flagged users' records -> the caller's arrays
-        for (int f = 0; f < count; f++) {
-            const T *rec = hx + (size_t)f * rec_w;
-            for (int i = 0; i < 10; i++) {
-                if (!h.outs[i]) continue;
-                const size_t w = i >= 8 ? 1 : per;
-                std::memcpy(h.outs[i] + ((size_t)u0 + hu[f]) * w, rec + rec_off[i], sizeof(T) * w);
-            }
+    }
+
+    void enqueue_batch(int bi)
+    {
+        const long long b0 = cuts[bi];
+        const int mb = (int)(cuts[bi + 1] - b0);
+        const int which = two_ctx ? (bi & 1) : 0;
+        InFlight &f = fl[which];
+        finish(which);                                               // (the batch two back: its context and staging are free again)
+        HIP_CHECK(hipStreamWaitEvent(streams[which], cx.up_ev[bi & 1], 0));
+        Call<T> c = batch_call(b0, mb);
+        f.b0 = b0; f.mb = mb;
+        lay.point_at(dblocks[which], (size_t)mb, c.out);
+        if (h.topk_idx) {
+            c.topk_idx = d_topk_idx + (size_t)b0 * K; c.topk_score = d_topk_score ? d_topk_score + (size_t)b0 * K : nullptr;
+            c.pos_rank = d_pos_rank; c.status = d_status + b0;
         }
-    };
-    struct Beside { bool ran = false; int count = 0; T *hx = nullptr; int *hu = nullptr; Ctx *pc = nullptr; hipStream_t stream = nullptr; std::unique_lock<std::mutex> lock; } bes;
+        if (range_noise) c.first_pass_flags = range_flag + b0;
+        const bool snap_here = range_noise && bi == n_batches - 1;
+        if (snap_here) {
+            c.flag_snapshot = range_snap + b0; c.flag_count_host = &cx.noise_words->first_early; c.flags_event = cx.flags_ev;
+        }
+        // enqueued (one short plan read-back inside; with more than one batch the tie noise's last look at the batch is deferred to
+        // finish(): the next batch is enqueued first)
+        run_call<T>(c, streams[which], *ctxs[which], n_batches > 1 ? &f.tail : nullptr);
+        f.on = true;
+        stamp("batch enqueued");
+        copy_out(which);
+        // the next batch's rows travel while this batch's sweep runs (the copies below block the host, not the device)
+        if (bi + 1 < n_batches && !g_interrupt) upload_users(bi + 1);
+        stamp("next rows enqueued");
+        if (snap_here && !g_interrupt) {
+            exact_beside_last(b0, (two_ctx && bi > 0) ? ctxs[(bi - 1) & 1]->ev[1] : (hipEvent_t)nullptr);
+            stamp("exact pass beside the last batch enqueued");
+        }
+        if (!two_ctx) finish(which);
+    }
+    // (the batch before the last one first: its outputs are copied to the caller while the last batch is still on the device)
+    void finish_all() { const int older = two_ctx ? ((n_batches - 2) & 1) : 0; finish(older); finish(older ^ 1); g_last_ctx = &cx; }
+
+    // ---- fp32 tie noise over the whole range (see `range_noise` in plan_batches) ----
+    // every user of the range; the metric block of an exact pass, [metric][users of the range x width], in workspace `w`
+    Call<T> range_call() const { Call<T> c = batch_call(0, m); c.csr_checked = true; return c; }      // (every batch has looked at its rows)
+    void exact_block(Call<T> &c, Workspace &w) const { lay.point_at((T *)w.get("o_exact", sizeof(T) * std::max<size_t>(lay.block_size((size_t)m), 1)), (size_t)m, c.out); }
+    // an exact pass's results leave the device packed: one record of `lay.rec_w` values per evaluated user (k_noise_gather)
+    void gather_exact(Ctx &gc, const Call<T> &c, const int *row_user, int count, hipStream_t st, T *&hx, int *&hu)
+    {
+        GatherArgs<T> ga{};
+        for (int i = 0; i < 10; i++) { ga.src[i] = c.out[i]; ga.width[i] = (int)lay.width(i); ga.off[i] = (int)lay.rec_off[i]; }
+        ga.out_w = (int)lay.rec_w;
+        T *dg = (T *)gc.ws.get("o_exact_packed", sizeof(T) * lay.rec_w * (size_t)count);
+        hipLaunchKernelGGL(k_noise_gather<T>, dim3(cdiv(count, 256)), dim3(256), 0, st, count, row_user, ga, dg);
+        hx = (T *)gc.pinned_get(sizeof(T) * lay.rec_w * (size_t)count + sizeof(int) * (size_t)count);
+        hu = (int *)(hx + lay.rec_w * (size_t)count);
+        HIP_CHECK(hipMemcpyAsync(hx, dg, sizeof(T) * lay.rec_w * (size_t)count, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hu, row_user, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, st));
+    }
+    void scatter_exact(const T *hx, const int *hu, int count)         // the flagged users' records -> the caller's arrays
+    {
+        for (int f = 0; f < count; f++)
+            for (int i = 0; i < 10; i++)
+                if (lay.want[i]) std::memcpy(h.outs[i] + ((size_t)u0 + hu[f]) * lay.width(i), hx + (size_t)f * lay.rec_w + lay.rec_off[i], sizeof(T) * lay.width(i));
+    }
     // the exact pass beside the last batch's sweep, on the NOISE_SLOT context and its stream: flags as they stand once the last batch
     // has scored its positives, noise rows for those users (from dense train rows built for them alone), the pipeline for them,
     // and the copy of their metric block to page-locked memory -- all of it enqueued behind `flags_ev`, none of it waited for here
@@ -2015,180 +2161,95 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     // It runs on the NOISE_SLOT context's high-priority streams (create_stream): at normal priority, kernels that reach the device after
     // a sweep which fills every compute unit only start when it drains -- the pass began when the last batch ended and cost its full
     // 0.9 ms (profiles/r5_host_entry.txt).
-    auto beside_start = [&](long long b0_last, hipEvent_t other) {
-        if (!out_w) return;
-        Ctx &pc = peer_context(cx, NOISE_SLOT);
-        bes.lock = std::unique_lock<std::mutex>(pc.mu);
-        bes.pc = &pc;
-        if (!pc.own_stream) HIP_CHECK(create_stream(&pc.own_stream, pc.high_priority));
-        hipStream_t ps = pc.own_stream;
-        bes.stream = ps;
-        Workspace &pw = pc.ws;
-        HIP_CHECK(hipStreamWaitEvent(ps, cx.flags_ev, 0));
-        // (the batch before the last runs on the other context's stream: its positives -- the early flags -- are in place once its
+    void exact_beside_last(long long b0_last, hipEvent_t other)
+    {
+        if (!lay.rec_w) return;
+        // (`other`: the batch before the last runs on the other context's stream: its positives -- the early flags -- are in place once its
         // own sweep has been launched, the event run() records as ev[1]; what its k_finalize flags later is the late pass's)
-        if (other) HIP_CHECK(hipStreamWaitEvent(ps, other, 0));
+        bes.open(other);
         // (the earlier batches' flags as they stand: a flag their k_finalize sets later is the sequential pass's, below)
-        if (b0_last > 0) HIP_CHECK(hipMemcpyAsync(range_snap, range_flag, sizeof(int) * (size_t)b0_last, hipMemcpyDeviceToDevice, ps));
-        int *noise_row = (int *)pw.get("noise_row", sizeof(int) * (size_t)m);
-        int *row_user = (int *)pw.get("noise_row_user", sizeof(int) * (size_t)m);
-        int *counter = (int *)pw.get("noise_counter", sizeof(int));
-        unsigned char *only = (unsigned char *)pw.get("noise_only", (size_t)m);
-        HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(int), ps));
-        hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, range_snap, (const int *)nullptr, noise_row, row_user, counter);
-        HIP_CHECK(hipMemcpyAsync(cx.pinned_small + 3, counter, sizeof(int), hipMemcpyDeviceToHost, ps));
-        HIP_CHECK(hipStreamSynchronize(ps));                          // (the last batch's positives are scored; its sweep has just been launched)
-        const int n_early = cx.pinned_small[3];
-        const NoiseGeom<T> g(pw, n);
+        if (b0_last > 0) HIP_CHECK(hipMemcpyAsync(range_snap, range_flag, sizeof(int) * (size_t)b0_last, hipMemcpyDeviceToDevice, bes.ps));
+        // (the wait in there: the last batch's positives are scored; its sweep has just been launched)
+        const int n_early = bes.assign(m, range_snap, -1, &cx.noise_words->range_early);
+        const NoiseGeom<T> g(bes.pc->ws, n);
         if (n_early <= 0 || n_early > g.cap) return;                  // nobody, or more rows than the budget holds at once: the sequential pass
-        hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, noise_row, 0, n_early, only);
-        unsigned *D = (unsigned *)pw.get("noise_draws", sizeof(unsigned) * (size_t)n_early * (size_t)g.d_ld);
-        T *E = (T *)pw.get("noise_rows", sizeof(T) * (size_t)n_early * (size_t)g.e_ld);
         Call<T> c = range_call();
-        const long long words = dense_row_words(n);
-        const bool fit = std::is_same<T, float>::value && dense_rows_fit(pw, m, n);
-        unsigned *bits = nullptr;
-        if (fit) {                                                    // rows of the flagged users alone, train items only
-            bits = (unsigned *)pw.get("train_bits", (size_t)m * (size_t)words * 4);
-            pc.bits_tag = 0; pc.bits_ptr = nullptr;
-            launch_train_bits(ps, m, n, (int)words, dtrp, dtri, (const int *)nullptr, dtei, bits, (const Plan *)nullptr, only);
-            c.ext_bits = bits; c.ext_words = words; c.ext_masked = false;
-        }
-        c.dense_fit = fit ? 1 : 0;
-        noise_make_rows<T>(pc, c, g, row_user, n_early, dtrp, (long long)u0, D, E, ps, bits, words);
-        c.only_users = only; c.noise_row = noise_row; c.noise_row0 = 0; c.noise_E = E; c.noise_ld = g.e_ld; c.eval_users = n_early;
-        T *dx = (T *)pw.get("o_exact", sizeof(T) * std::max<size_t>(x_bo, 1));
-        for (int i = 0; i < 10; i++) c.out[i] = h.outs[i] ? dx + x_off[i] : nullptr;
-        try { run<T>(c, ps, pc); }
-        catch (...) {
-            (void)hipStreamSynchronize(ps);
-            if (pc.side_stream) (void)hipStreamSynchronize(pc.side_stream);
-            g_last_ctx = &cx;
-            throw;
-        }
-        g_last_ctx = &cx;
-        gather_exact(pc, dx, row_user, n_early, ps, bes.hx, bes.hu);
-        bes.ran = true; bes.count = n_early;
-    };
-    // (ADVICE r4) a call that stops between its first passes and the exact one -- interrupt, failure -- must not leave the first
-    // pass's un-noised values of the flagged users in the caller's arrays looking like results: they become NaN
-    auto nan_flagged = [&]() {
-        if (!range_noise || !out_w || users_copied <= 0) return;
-        std::vector<int> hf((size_t)users_copied);
-        if (hipMemcpy(hf.data(), range_flag, sizeof(int) * (size_t)users_copied, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return; }
-        const T nanv = std::numeric_limits<T>::quiet_NaN();
-        for (long long u = 0; u < users_copied; u++) {
-            if (!hf[(size_t)u]) continue;
-            for (int i = 0; i < 10; i++) {
-                if (!h.outs[i]) continue;
-                const size_t w = i >= 8 ? 1 : per;
-                for (size_t j = 0; j < w; j++) h.outs[i][((size_t)u0 + (size_t)u) * w + j] = nanv;
-            }
-        }
-    };
-    try {
-    for (int bi = 0; bi < n_batches; bi++) {
-        const long long b0 = cuts[bi];
-        const int b1 = (int)cuts[bi + 1], mb = b1 - (int)b0;
-        if (g_interrupt) break;                                      // reference :488-489: the remaining users are skipped
-        const int which = two_ctx ? (bi & 1) : 0;
-        Ctx &bc = *ctxs[which];
-        hipStream_t bs = streams[which];
-        finish(which);                                               // (the batch two back: its context and staging are free again)
-        HIP_CHECK(hipStreamWaitEvent(bs, cx.up_ev[bi & 1], 0));
-        Call<T> c{};
-        c.A = dA + (size_t)b0 * k; c.lda = k; c.B = dB; c.ldb = k; c.m = mb; c.n = n; c.k = k;
-        c.train_p = dtrp + b0; c.train_i = dtri; c.nnz_train = nnz_tr;
-        c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
-        c.K = K; c.cumulative = h.cumulative; c.noise = h.noise; c.cold = h.cold; c.min_items_pool = h.mip; c.min_pos_test = h.mpt;
-        c.reco = h.reco;
-        InFlight &f = fl[which];
-        f.b0 = b0; f.mb = mb; f.bo = 0; f.which = which;
-        for (int i = 0; i < 10; i++) { f.boff[i] = f.bo; c.out[i] = h.outs[i] ? dblocks[which] + f.bo : nullptr; if (h.outs[i]) f.bo += (size_t)mb * (i >= 8 ? 1 : per); }
-        if (h.topk_idx) {
-            c.topk_idx = d_topk_idx + (size_t)b0 * K; c.topk_score = d_topk_score ? d_topk_score + (size_t)b0 * K : nullptr;
-            c.pos_rank = d_pos_rank; c.status = d_status + b0;
-        }
-        c.items_tag = tag;
-        c.seed = h.seed; c.user0 = (long long)u0 + b0;
-        if (range_noise) c.first_pass_flags = range_flag + b0;
-        const bool snap_here = beside_last && bi == n_batches - 1;
-        if (snap_here) {
-            c.flag_snapshot = range_snap + b0; c.flag_count_host = cx.pinned_small; c.flags_event = cx.flags_ev;
-        }
-        // enqueued (one short plan read-back inside; with more than one batch the tie noise's last look at the batch is deferred to
-        // finish(): the next batch is enqueued first)
-        run_call<T>(c, bs, bc, n_batches > 1 ? &f.tail : nullptr);
-        f.on = true;
-        stamp("batch enqueued");
-        const size_t bo = f.bo;
-        const long long e0 = tep[b0], e1 = tep[b1];                 // this batch's test entries (range-relative)
-        Plan *batch_plan = (Plan *)bc.ws.get("plan", sizeof(Plan));
-        int *flagged_here = (range_noise && bc.pinned_small) ? bc.pinned_small + 5 : nullptr;
-        f.counts_flags = flagged_here != nullptr;
-        f.copy_out = [=, &h]() {
-            if (flagged_here) HIP_CHECK(hipMemcpyAsync(flagged_here, &batch_plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, bs));
-            if (bo) HIP_CHECK(hipMemcpyAsync(hblocks[which], dblocks[which], sizeof(T) * bo, hipMemcpyDeviceToHost, bs));
-            if (h.topk_idx) {
-                HIP_CHECK(hipMemcpyAsync(h.topk_idx + ((size_t)u0 + b0) * K, c.topk_idx, sizeof(int) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
-                if (h.topk_score) HIP_CHECK(hipMemcpyAsync(h.topk_score + ((size_t)u0 + b0) * K, c.topk_score, sizeof(T) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
-                HIP_CHECK(hipMemcpyAsync(h.status + u0 + b0, c.status, sizeof(int) * (size_t)mb, hipMemcpyDeviceToHost, bs));
-                if (h.pos_rank && e1 > e0) HIP_CHECK(hipMemcpyAsync(h.pos_rank + te0 + e0, c.pos_rank + e0, sizeof(long long) * (size_t)(e1 - e0), hipMemcpyDeviceToHost, bs));
-            }
-        };
-        f.copy_out();
-        // the next batch's rows travel while this batch's sweep runs (the copies below block the host, not the device)
-        if (bi + 1 < n_batches && !g_interrupt) upload_users(bi + 1);
-        stamp("next rows enqueued");
-        if (snap_here && !g_interrupt) {
-            beside_start(b0, (two_ctx && bi > 0) ? ctxs[(bi - 1) & 1]->ev[1] : (hipEvent_t)nullptr);
-            stamp("exact pass beside the last batch enqueued");
-        }
-        if (!two_ctx) finish(which);
+        bes.rows(c, g, n_early, true);                                // rows of the flagged users alone, train items only
+        exact_block(c, bes.pc->ws);
+        bes.run_pass(c);
+        gather_exact(*bes.pc, c, bes.row_user, n_early, bes.ps, bes_hx, bes_hu);
+        bes_ran = true; bes_count = n_early;
     }
-    // (the batch before the last one first: its outputs are copied to the caller while the last batch is still on the device)
-    { const int older = two_ctx ? ((n_batches - 2) & 1) : 0; finish(older); finish(older ^ 1); }
-    g_last_ctx = &cx;
-    // (ONE look at the flag decides both: whether the exact passes run, and whether the flagged users' values are withdrawn -- an
-    // interrupt that arrives while the passes finish must not turn their finished, correct values into NaN)
-    const bool interrupted = g_interrupt;
-    if (range_noise && !interrupted && out_w) {
-        if (bes.ran) {                                                // (its results left the device while the last batch was sweeping)
-            HIP_CHECK(hipStreamSynchronize(bes.stream));
-            scatter_exact(bes.hx, bes.hu, bes.count);
+    // behind the last batch: the values of the pass beside it, and the exact pass over the users of the range that the first passes
+    // flagged and that pass has not seen (all of them without it)
+    void exact_late(bool wanted)
+    {
+        if (!(range_noise && wanted && lay.rec_w)) { bes.sync(); return; }
+        if (bes_ran) {                                                // (its results left the device while the last batch was sweeping)
+            HIP_CHECK(hipStreamSynchronize(bes.ps));
+            scatter_exact(bes_hx, bes_hu, bes_count);
             stamp("exact pass (beside) scattered");
         }
-        // the exact pass over the users of the range that the first passes flagged and the pass beside the last batch has not seen
-        // (all of them without it): into a metric block of its own, from which the host takes the flagged users' values
+        // into a metric block of its own, from which the host takes the flagged users' values
         Call<T> c = range_call();
-        T *dx = (T *)ws.get("o_exact", sizeof(T) * std::max<size_t>(x_bo, 1));
-        for (int i = 0; i < 10; i++) c.out[i] = h.outs[i] ? dx + x_off[i] : nullptr;
+        exact_block(c, ws);
         // (every batch reports how many users its first pass flagged: when the pass beside the last batch has seen them all --
         // the usual case -- nothing is left to look for)
-        const long long late = flagged_total - (bes.ran ? bes.count : 0);
-        if (late > 0) {
-            const int *row_user = nullptr;
-            const int n_flagged = noise_exact_pass<T>(c, range_flag, bes.ran ? (const int *)range_snap : (const int *)nullptr, -1, stream, cx, &row_user);
-            stamp("exact pass enqueued");
-            if (n_flagged > 0) {
-                T *hx = nullptr; int *hu = nullptr;
-                gather_exact(cx, dx, row_user, n_flagged, stream, hx, hu);
-                HIP_CHECK(hipStreamSynchronize(stream));
-                scatter_exact(hx, hu, n_flagged);
-                stamp("exact pass scattered");
-            }
+        const long long late = flagged_total - (bes_ran ? bes_count : 0);
+        if (late <= 0) return;
+        const int *row_user = nullptr;
+        const int n_flagged = noise_exact_pass<T>(c, range_flag, bes_ran ? (const int *)range_snap : (const int *)nullptr, -1, stream, cx, &row_user);
+        stamp("exact pass enqueued");
+        if (n_flagged <= 0) return;
+        T *hx = nullptr; int *hu = nullptr;
+        gather_exact(cx, c, row_user, n_flagged, stream, hx, hu);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        scatter_exact(hx, hu, n_flagged);
+        stamp("exact pass scattered");
+    }
+    // (ADVICE r4) a call that stops between its first passes and the exact one -- interrupt, failure -- must not leave the first
+    // pass's un-noised values of the flagged users in the caller's arrays looking like results: they become NaN
+    void withdraw_flagged()
+    {
+        if (!range_noise || !lay.rec_w || users_copied <= 0) return;
+        std::vector<int> hf((size_t)users_copied);
+        if (hipMemcpy(hf.data(), range_flag, sizeof(int) * (size_t)users_copied, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return; }
+        for (long long u = 0; u < users_copied; u++) {
+            if (!hf[(size_t)u]) continue;
+            for (int i = 0; i < 10; i++)
+                if (lay.want[i]) std::fill_n(h.outs[i] + ((size_t)u0 + (size_t)u) * lay.width(i), lay.width(i), std::numeric_limits<T>::quiet_NaN());
         }
-    } else if (bes.pc) (void)hipStreamSynchronize(bes.stream);
-    if (interrupted) nan_flagged();
-    } catch (...) {
-        for (int i = 0; i < 2; i++) (void)hipStreamSynchronize(streams[i]);      // nothing may still write into staging that goes away
+    }
+    void drain()                                                      // a failure: nothing may still write into staging that goes away
+    {
+        for (int i = 0; i < 2; i++) (void)hipStreamSynchronize(streams[i]);
         (void)hipStreamSynchronize(up);
-        if (bes.pc) (void)hipStreamSynchronize(bes.stream);
-        nan_flagged();
+        bes.sync();
+        withdraw_flagged();
+    }
+};
+
+template <class T>
+void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t stream, SharedItems *shared, int shard, unsigned long long tag)
+{
+    HostRange<T> r(h, u0, u1, cx, stream, shared, shard, tag);
+    if (!r.stage_inputs()) return;
+    r.plan_batches();
+    r.first_uploads();
+    try {
+        for (int bi = 0; bi < r.n_batches && !g_interrupt; bi++) r.enqueue_batch(bi);      // reference :488-489: the remaining users are skipped
+        r.finish_all();
+        // (ONE look at the flag decides both: whether the exact passes run, and whether the flagged users' values are withdrawn -- an
+        // interrupt that arrives while the passes finish must not turn their finished, correct values into NaN)
+        const bool interrupted = g_interrupt;
+        r.exact_late(!interrupted);
+        if (interrupted) r.withdraw_flagged();
+    } catch (...) {
+        r.drain();
         throw;
     }
-    HIP_CHECK(hipStreamSynchronize(up));                              // `rb` and the caller's arrays go out of use (also after an interrupt)
-    if (trace) print_host_trace(n_batches, stamps);
+    HIP_CHECK(hipStreamSynchronize(r.up));                            // `rb` and the caller's arrays go out of use (also after an interrupt)
+    if (g_sw.host_trace) print_host_trace(r.n_batches, r.stamps);
 }
 
 // (m == 0 is not an error: the reference's loop over users, src/recometrics.hpp:428-437, simply does not run; the entry
