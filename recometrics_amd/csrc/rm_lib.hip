@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -98,31 +99,72 @@ RunTrace g_run_trace;
 #define RM_TRACE_POINT(what) do { if (g_sw.host_trace) g_run_trace.point(what); } while (0)
 
 // ---- cached device workspace (per device), so that repeated calls do not pay hipMalloc ----
+// Every ALLOCATION of a buffer carries a stamp from a process-wide counter: what is remembered about a buffer's contents (PackedItems,
+// DenseRows, DiscountTable) is void once the buffer is allocated anew -- grown, or released and asked for again -- at whatever address.
+std::atomic<unsigned long long> g_ws_stamp{1};
 struct Workspace {
-    std::map<std::string, std::pair<void *, size_t>> bufs;
+    struct Buf { void *ptr = nullptr; size_t bytes = 0; unsigned long long stamp = 0; };
+    std::map<std::string, Buf> bufs;
     void *get(const std::string &name, size_t bytes)
     {
         bytes = std::max<size_t>(bytes, 256);
-        auto &b = bufs[name];
-        if (b.second < bytes) {
-            if (b.first) { (void)hipFree(b.first); g_ws_bytes -= (long long)b.second; b.first = nullptr; b.second = 0; }
+        Buf &b = bufs[name];
+        if (b.bytes < bytes) {
+            if (b.ptr) { (void)hipFree(b.ptr); g_ws_bytes -= (long long)b.bytes; b = Buf{}; }
             const size_t cap = bytes + bytes / 8;
             const long long sim = debug_free_cap();
             if (sim >= 0 && g_ws_bytes.load() + (long long)cap > sim)
                 throw RmError{RM_ERR_NOMEM, "hipMalloc(" + name + ", " + std::to_string(cap) + " B): beyond RM_DEBUG_FREE_MB"};
-            hipError_t e = hipMalloc(&b.first, cap);
-            if (e != hipSuccess) { b.first = nullptr; throw RmError{RM_ERR_NOMEM, "hipMalloc(" + name + ", " + std::to_string(cap) + " B): " + hipGetErrorString(e)}; }
-            b.second = cap;
+            hipError_t e = hipMalloc(&b.ptr, cap);
+            if (e != hipSuccess) { b.ptr = nullptr; throw RmError{RM_ERR_NOMEM, "hipMalloc(" + name + ", " + std::to_string(cap) + " B): " + hipGetErrorString(e)}; }
+            b.bytes = cap; b.stamp = g_ws_stamp.fetch_add(1);
             g_ws_bytes += (long long)cap;
         }
-        return b.first;
+        return b.ptr;
     }
+    // the buffer as it stands (never asked for, or released: null and stamp 0, which no valid record carries)
+    Buf peek(const char *name) const { auto it = bufs.find(name); return it == bufs.end() ? Buf{} : it->second; }
     void release()
     {
-        for (auto &kv : bufs) if (kv.second.first) { (void)hipFree(kv.second.first); g_ws_bytes -= (long long)kv.second.second; }
+        for (auto &kv : bufs) if (kv.second.ptr) { (void)hipFree(kv.second.ptr); g_ws_bytes -= (long long)kv.second.bytes; }
         bufs.clear();
     }
 };
+// What a workspace buffer was last filled with, for the callers that may find it filled already.  A record is valid only for the
+// allocation it was made in (Workspace::Buf::stamp); each question a caller asks is a member.
+struct PackedItems {                         // "Bp": the packed item image, shared by the passes / batches of one call (Call::items_tag)
+    unsigned long long stamp = 0, tag = 0; int tile = 0, ng = 0;
+    unsigned long long amax_b = 0; int nonfinite_b = 0;      // max |B| and its non-finite count as that call's plan found them
+    bool of_call(unsigned long long t) const { return t != 0 && t == tag; }      // (the bound on |B| holds for the call; `holds`: so does the image, at this geometry)
+    bool holds(const Workspace &ws, unsigned long long t, int tile_items, int NG) const { return of_call(t) && stamp == ws.peek("Bp").stamp && tile == tile_items && ng == NG; }
+    void set(const Workspace &ws, unsigned long long t, int tile_items, int NG) { stamp = ws.peek("Bp").stamp; tag = t; tile = tile_items; ng = NG; }
+    void invalidate() { stamp = 0; tag = 0; }
+};
+struct DenseRows {                           // "train_bits": the dense train rows (set_train_bits)
+    unsigned long long stamp = 0; long long words = 0; int m = 0;
+    bool masked = false, partial = false;                      // the test items marked too; a subset of the users only (Call::only_users)
+    unsigned long long tag = 0; const int *train_p = nullptr;  // built by which call (Call::items_tag), over which rows
+    bool valid(const Workspace &ws) const { return stamp != 0 && stamp == ws.peek("train_bits").stamp; }
+    // rows of this buffer for `m_` users, `words_` words, masked as asked, built for all users (a later pass of the same call)
+    bool fits(const Workspace &ws, int m_, long long words_, bool masked_) const { return valid(ws) && !partial && words == words_ && m == m_ && masked == masked_; }
+    // rows built by call `t` over `train_p_` for `m_` users, not partial (the tie noise's exact pass beside that call's sweep)
+    bool built_by(const Workspace &ws, unsigned long long t, const int *train_p_, int m_) const { return valid(ws) && t != 0 && t == tag && train_p == train_p_ && m == m_ && !partial; }
+    const unsigned *rows(const Workspace &ws) const { return (const unsigned *)ws.peek("train_bits").ptr; }
+    void set(const Workspace &ws, long long words_, int m_, bool masked_, bool partial_, unsigned long long t, const int *train_p_)
+    { stamp = ws.peek("train_bits").stamp; words = words_; m = m_; masked = masked_; partial = partial_; tag = t; train_p = train_p_; }
+    void invalidate() { stamp = 0; tag = 0; }
+};
+struct DiscountTable {                       // "log2tab": log2(i + 2), the DCG discounts
+    unsigned long long stamp = 0; int K = 0;
+    bool holds(const Workspace &ws, int K_) const { return stamp != 0 && stamp == ws.peek("log2tab").stamp && K >= K_; }
+    void set(const Workspace &ws, int K_) { stamp = ws.peek("log2tab").stamp; K = K_; }
+};
+// The roles of the events that order a context's two streams beside the call's against it: who records each and who waits is the
+// table in DESIGN.md section 1.  One event per role; `Beside` (below) is the only code that touches them.
+enum SideMark { SIDE_FORK, SIDE_JOIN, SIDE_PLAN_FORK, SIDE_CHECKS_DONE, SIDE_ROWS_AND_PACKS, SIDE_ROWS_FOR_POS, SIDE_TOP_VALUES,
+                SIDE_SWEEP_FORK, SIDE_SWEEP_DEEP_DONE, SIDE_MERGED, SIDE_MARKS };
+enum PosMark { POS_PLAN_FORK, POS_MAXIMA_DONE, POS_SCORES_AFTER_COPY, POS_SCORES_DONE, POS_TABLES_INIT, POS_STREAMED_PLACED, POS_MARKS };
+enum PassEvent { EV_START, EV_PREP_END /* = sweep launched: HostRange::exact_beside_last waits for it */, EV_SWEEP_END, EV_END, EV_COUNT };   // timing (Ctx::stage_ms)
 // The page-locked words of a context through which the counts of the fp32 tie noise come back from the device (one 64-byte
 // allocation per context, Ctx::need_noise_words)
 struct NoiseWords {
@@ -144,11 +186,10 @@ struct Ctx {
     int device = 0, slot = 0;
     std::mutex mu;
     Workspace ws;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[EV_COUNT] = {nullptr, nullptr, nullptr, nullptr};
     bool ev_valid = false, ev_recorded = false;
-    hipStream_t side_stream = nullptr;      // second sweep launch of a depth-split call runs beside the first
-    hipStream_t pos_stream = nullptr; hipEvent_t pos_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // the streamed users' positives beside the table users' (run())
-    hipEvent_t side_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipStream_t side_stream = nullptr; std::array<hipEvent_t, SIDE_MARKS> side_marks{};     // the two streams beside a call's (Beside), one event per role
+    hipStream_t pos_stream = nullptr; std::array<hipEvent_t, POS_MARKS> pos_marks{};
     hipEvent_t done = nullptr;               // end of the device work of the most recent call on this context
     hipStream_t own_stream = nullptr;        // stream of a shard worker (multi-device calls)
     hipStream_t up_stream = nullptr;         // host-pointer calls: uploads of the NEXT user batch run beside the current batch's kernels
@@ -174,16 +215,14 @@ struct Ctx {
     double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int timed_slots = 0, total_slots = 0;     // slots (user lanes) of the sweep launch the "sweep" timing brackets / of the call
     double acc[4] = {0, 0, 0, 0};            // prep / sweep / finalize / total ms of the batches already read back (host entry)
-    // what the packed item image (workspace buffer "Bp") currently holds, for batches of one host call that share B
-    unsigned long long packed_tag = 0; int packed_tile = 0, packed_ng = 0; const void *packed_ptr = nullptr;
-    const void *bits_ptr = nullptr; long long bits_words = 0; int bits_m = 0;      // dense train rows as last built (set_train_bits)
-    unsigned long long bits_tag = 0; const int *bits_train_p = nullptr;             // ... by which call (Call::items_tag) and for which rows
-    bool bits_masked = false;                                                       // ... with the test items marked too
-    bool bits_partial = false;                                                      // ... for a subset of the users only (Call::only_users)
+    PackedItems packed; DenseRows dense; DiscountTable discounts;    // what "Bp", "train_bits" and "log2tab" of `ws` hold
     bool high_priority = false;          // streams of this context are created with the highest priority (the exact passes of the tie noise)
     Plan *pinned_plan = nullptr;                                                    // page-locked landing place of the plan read-back
-    const void *log2_ptr = nullptr; int log2_K = 0;                                 // the DCG discount table the workspace holds (run())
-    unsigned long long packed_amax_b = 0; int packed_nonfinite_b = 0;
+    void stage_ms(float ms[4]) const       // prep / sweep / finalize / total of the most recent pass, from its four events (which have completed)
+    {
+        const int from[4] = {EV_START, EV_PREP_END, EV_SWEEP_END, EV_START}, to[4] = {EV_PREP_END, EV_SWEEP_END, EV_END, EV_END};
+        for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&ms[i], ev[from[i]], ev[to[i]]);
+    }
 };
 // A stream of a context.  The NOISE_SLOT contexts ask for the highest priority the device offers: their work -- the exact pass of the
 // tie noise over a few thousand users -- is enqueued BESIDE a sweep that fills every compute unit, and at normal priority its kernels
@@ -422,7 +461,7 @@ inline long long free_plus_owned(const Workspace &ws, std::initializer_list<cons
     const long long sim = debug_free_cap();
     if (sim >= 0) fr = (size_t)std::max<long long>(0, std::min<long long>((long long)fr, sim - g_ws_bytes.load()));
     long long owned = 0;
-    for (const char *nm : names) { auto it = ws.bufs.find(nm); if (it != ws.bufs.end()) owned += (long long)it->second.second; }
+    for (const char *nm : names) { auto it = ws.bufs.find(nm); if (it != ws.bufs.end()) owned += (long long)it->second.bytes; }
     return (long long)fr + owned;
 }
 inline long long stream_budget_bytes(const Workspace &ws)
@@ -491,18 +530,14 @@ template <class C> inline void set_train_bits(SweepArgs &sa, Ctx &cx, const C &c
     const long long words = dense_row_words(n);
     const size_t bytes = (size_t)m * (size_t)words * 4;
     sa.train_bits = nullptr; sa.train_words = 0;
-    if (!fit) { cx.bits_tag = 0; return; }
+    if (!fit) { cx.dense.invalidate(); return; }
     unsigned *bits = (unsigned *)ws.get("train_bits", bytes);
     // (the exact second pass of the tie noise evaluates a subset of the same users: the rows of the first pass are still there)
-    const bool ready = (early && early_masked == mask_test) ||
-                       (c.same_train_rows && !cx.bits_partial && cx.bits_ptr == (const void *)bits && cx.bits_words == words && cx.bits_m == m && cx.bits_masked == mask_test);
-    if (!ready) {
+    const bool ready = (early && early_masked == mask_test) || (c.same_train_rows && cx.dense.fits(ws, m, words, mask_test));
+    if (!ready)
         launch_train_bits(stream, m, n, (int)words, c.train_p, c.train_i, (mask_test || ent_masked) ? c.test_p : nullptr, c.test_i, bits,
                           (const Plan *)ws.get("plan", sizeof(Plan)), c.only_users, ent_masked, mask_test);
-        cx.bits_partial = c.only_users != nullptr;
-    }
-    cx.bits_ptr = (const void *)bits; cx.bits_words = words; cx.bits_m = m; cx.bits_masked = mask_test;
-    cx.bits_tag = c.items_tag; cx.bits_train_p = c.train_p;
+    cx.dense.set(ws, words, m, mask_test, ready ? cx.dense.partial : c.only_users != nullptr, c.items_tag, c.train_p);
     sa.train_bits = bits; sa.train_words = (int)words;
 }
 template <class C> inline void set_train_bits(Sweep64Args &, Ctx &, const C &, int, int, bool, hipStream_t, bool, bool = false, bool = false, unsigned char * = nullptr) {}
@@ -580,7 +615,7 @@ void throw_csr_defects(const Plan &hp, const Call<T> &c, Ctx &cx)
 {
     const bool unsorted = hp.csr_desc_all[0] != hp.csr_desc_legit[0] || hp.csr_desc_all[1] != hp.csr_desc_legit[1];
     if (!hp.csr_bad && !unsorted) return;
-    cx.bits_tag = 0; cx.bits_ptr = nullptr;                        // (dense train rows launched beside the plan were not built)
+    cx.dense.invalidate();                                         // (dense train rows launched beside the plan were not built)
     if (hp.csr_bad & CSR_BAD_INDPTR)
         throw RmError{RM_ERR_INVALID, "CSR index pointers of row " + std::to_string((long long)c.user0 + hp.csr_where) + " are negative, decreasing or beyond the index array"};
     if (hp.csr_bad & CSR_BAD_INDEX)
@@ -621,13 +656,22 @@ void check_csr_now(const Call<T> &c, hipStream_t stream, Ctx &cx)
 // ---------------------------------------------------------------------------------------------------------------------
 // device pipeline (T = float: v_mfma_f32_32x32x2_f32 sweep; T = double: v_mfma_f64_16x16x4_f64 sweep)
 // ---------------------------------------------------------------------------------------------------------------------
-// A stream of the context beside the call's (the side stream, the positives' stream), created on first use with its events.
-// `pending` counts the pieces of work forked onto it that the call's stream has not been told to wait for yet: an error between
-// a fork and its join must not leave the stream reading the call's buffers behind the caller's back, so the destructor waits.
+// A stream of the context beside the call's (the side stream, the positives' stream), created on first use with its events, and the
+// order between the two (roles: SideMark / PosMark):
+//   cut(role) / behind(role)  the call's stream records a point; the stream beside waits for it and is handed out (fork = both);
+//   on()                      ... handed out again, with nothing new to wait for;
+//   mark(role) / await(role, into)  the stream beside records what it was given so far; `into` -- the call's stream, or a third one --
+//                             waits for that (join = mark + await by the call's stream).
+// A handle is good until the next mark: work enqueued behind a mark asks for the stream again.  Every hand-out counts, a mark
+// remembers the count, and the call's stream has JOINED what it awaited (or the host waited for: sync) and, the stream being in order,
+// all before it.  An error between a hand-out and its join must not leave the stream reading the call's buffers behind the caller's
+// back: the destructor waits when something is outstanding.  Switched off (RM_DEBUG_NO_SIDE) every hand-out is the call's stream.
 struct Beside {
-    hipStream_t &st; hipEvent_t *ev; int n_ev; bool high_priority; int pending = 0;
-    Beside(hipStream_t &s, hipEvent_t *e, int n, bool hp) : st(s), ev(e), n_ev(n), high_priority(hp) {}
-    ~Beside() { if (pending > 0 && st) (void)hipStreamSynchronize(st); }
+    hipStream_t &st; hipEvent_t *const ev; const int n_ev; const hipStream_t call; const bool high_priority; bool enabled;
+    long long handed = 0, joined = 0, at[SIDE_MARKS] = {};      // at[role]: 0 = no mark the call's stream has yet to await
+    static_assert((int)POS_MARKS <= (int)SIDE_MARKS, "at[] holds the roles of either stream");
+    Beside(hipStream_t &s, hipEvent_t *e, int n, hipStream_t call_, bool hp, bool on_) : st(s), ev(e), n_ev(n), call(call_), high_priority(hp), enabled(on_) {}
+    ~Beside() { if (handed > joined && st) (void)hipStreamSynchronize(st); }
     hipStream_t get()
     {
         if (!st) {
@@ -636,8 +680,16 @@ struct Beside {
         }
         return st;
     }
-    hipStream_t fork(hipStream_t from) { hipStream_t s = get(); HIP_CHECK(hipEventRecord(ev[0], from)); HIP_CHECK(hipStreamWaitEvent(s, ev[0], 0)); pending++; return s; }
-    void join(hipStream_t into) { HIP_CHECK(hipEventRecord(ev[1], st)); HIP_CHECK(hipStreamWaitEvent(into, ev[1], 0)); pending = 0; }
+    hipStream_t on() { if (!enabled) return call; handed++; return get(); }
+    void cut(int role) { if (enabled) { get(); HIP_CHECK(hipEventRecord(ev[role], call)); } }
+    hipStream_t behind(int role) { if (!enabled) return call; HIP_CHECK(hipStreamWaitEvent(st, ev[role], 0)); handed++; return st; }
+    hipStream_t fork(int role) { cut(role); return behind(role); }
+    void mark(int role) { if (enabled) { HIP_CHECK(hipEventRecord(ev[role], st)); at[role] = handed; } }
+    void joined_at(int role) { joined = std::max(joined, at[role]); at[role] = 0; }
+    void await(int role, hipStream_t into) { if (enabled) { HIP_CHECK(hipStreamWaitEvent(into, ev[role], 0)); if (into == call) joined_at(role); } }
+    void join(int role) { mark(role); await(role, call); }
+    bool marked(int role) const { return at[role] != 0; }              // marked, and the call's stream has not been told to wait yet
+    void sync() { if (enabled && st) { HIP_CHECK(hipStreamSynchronize(st)); joined = handed; } }      // the HOST waits (the second plan)
 };
 
 // LDS of a sweep block of depth j (each group's positives table is aligned to its own size, 2^j rows of GU scores: worst-case
@@ -772,8 +824,8 @@ struct Pipeline {
     static constexpr int GU = P::GU;
     const Call<T> &c; hipStream_t stream; Ctx &cx; Workspace &ws;
     const int m, n, k, K;
-    Beside side, pos;                       // kernels that do not depend on one another run beside the call's stream (run_stages)
-    bool use_side = !g_sw.no_side;
+    const bool use_side = !g_sw.no_side;    // (decides what is launched; where it only decides a stream, a record or a wait, Beside does)
+    Beside side, pos;                       // kernels that do not depend on one another run beside the call's stream
     // begin
     int min_items_pool = 0, min_pos_test = 0, req = 0, NG = 0; bool want_auc = false;
     // plan
@@ -790,20 +842,20 @@ struct Pipeline {
     // prep
     FinalArgs<T, T> fa{};
     Entry<T> *merged = nullptr; long long *rank_sorted = nullptr;
-    bool topv_pending = false;
     T *pos_score = nullptr; unsigned *hist = nullptr; int *pos_order = nullptr, *pos_item = nullptr;
     Entry<T> *pl = nullptr; PartialStat<T> *pst = nullptr;
     T *stream_scores = nullptr, *spos_score = nullptr; int *spos_item = nullptr; unsigned *shist = nullptr;
     long long stream_ld = 0;
     typename P::Args sa{};
     typename P::ListT *glists = nullptr; int *lane_cnt = nullptr; ThrT *thr_shared = nullptr;
-    bool lane_lists = false, bits_wait = false;
+    bool lane_lists = false;
     // sweep
     bool collect = false; CollectGeom collect_g{};
 
     Pipeline(const Call<T> &c_, hipStream_t s, Ctx &cx_)
         : c(c_), stream(s), cx(cx_), ws(cx_.ws), m(c_.m), n(c_.n), k(c_.k), K(c_.K),
-          side(cx_.side_stream, cx_.side_ev, 7, cx_.high_priority), pos(cx_.pos_stream, cx_.pos_ev, 5, cx_.high_priority) {}
+          side(cx_.side_stream, cx_.side_marks.data(), SIDE_MARKS, s, cx_.high_priority, use_side),
+          pos(cx_.pos_stream, cx_.pos_marks.data(), POS_MARKS, s, cx_.high_priority, use_side) {}
 
     // ---- begin: the reference's clamps, the metrics asked for, the context's events ----
     void begin()
@@ -817,14 +869,14 @@ struct Pipeline {
         NG = P::supported_ng(k);
         if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
         if (!cx.ev_valid) {
-            for (int i = 0; i < 5; i++) HIP_CHECK(hipEventCreate(&cx.ev[i]));
+            for (int i = 0; i < EV_COUNT; i++) HIP_CHECK(hipEventCreate(&cx.ev[i]));
             HIP_CHECK(hipEventCreateWithFlags(&cx.done, hipEventDisableTiming));
             cx.ev_valid = true;
         } else {
             HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // the previous call on this context may still be running on another stream
         }
         g_last_ctx = &cx;
-        HIP_CHECK(hipEventRecord(cx.ev[0], stream));
+        HIP_CHECK(hipEventRecord(cx.ev[EV_START], stream));
         RM_TRACE_POINT("run: start");
     }
 
@@ -881,16 +933,16 @@ struct Pipeline {
             tile_total = (int *)ws.get("scan_tile_total", sizeof(int) * (size_t)n_tiles);
             tile_offset = (int *)ws.get("scan_tile_offset", sizeof(int) * (size_t)n_tiles);
         }
-        items_known = c.items_tag != 0 && c.items_tag == cx.packed_tag;       // a later batch of the same host call
+        items_known = cx.packed.of_call(c.items_tag);                          // a later batch of the same host call
         // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
-        // depends on K alone: it stays in the workspace, and only a longer one (or a moved buffer) is uploaded again -- the copy
-        // comes from pageable memory, which blocks the host and waits for the stream
+        // depends on K alone: it stays in the workspace, and only a longer one (or one for a new allocation) is uploaded again -- the
+        // copy comes from pageable memory, which blocks the host and waits for the stream
         if (!c.reco) log2tab = (double *)ws.get("log2tab", sizeof(double) * (size_t)K);
-        if (!c.reco && (cx.log2_ptr != (const void *)log2tab || cx.log2_K < K)) {
+        if (!c.reco && !cx.discounts.holds(ws, K)) {
             std::vector<double> lt((size_t)K);
             for (int i = 0; i < K; i++) lt[i] = std::log2(i + 2);
             HIP_CHECK(hipMemcpy(log2tab, lt.data(), sizeof(double) * (size_t)K, hipMemcpyHostToDevice));       // (synchronous: `lt` is on the stack)
-            cx.log2_ptr = (const void *)log2tab; cx.log2_K = K;
+            cx.discounts.set(ws, K);
         }
         if (!cx.pinned_plan) HIP_CHECK(hipHostMalloc((void **)&cx.pinned_plan, sizeof(Plan), hipHostMallocDefault));
         // (one answer per call: a later pass -- the exact passes of the tie noise, on this or on a peer context with less free memory --
@@ -923,11 +975,7 @@ struct Pipeline {
             hipLaunchKernelGGL(k_classify, dim3(cdiv(m, 1024)), dim3(1024), 0, stream, ca);
             // (the two forks behind k_classify, recorded BEFORE the rest of the chain is enqueued: the host needs ~4 us per launch, and the
             // chain's kernels used to reach the device 60 us late, behind everything that was enqueued for the other streams)
-            if (use_side) {
-                side.get(); pos.get();
-                HIP_CHECK(hipEventRecord(cx.side_ev[0], stream));
-                HIP_CHECK(hipEventRecord(cx.pos_ev[0], stream));
-            }
+            side.cut(SIDE_PLAN_FORK); pos.cut(POS_PLAN_FORK);
             if (tile_total) {
                 hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(1024), 0, stream, user_nslots, uslot_base, m, tile_total);
                 hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, tile_total, tile_offset, n_tiles, &plan->n_slots, plan, GU);
@@ -945,36 +993,28 @@ struct Pipeline {
             // items (`mask_test`) is only decided behind the read-back; the guess here is the usual answer, and a wrong guess costs one
             // more launch of the kernel behind it.  On the positives' stream max |A| and max |B| and the user of every test entry.  The
             // plan carries the checks' verdicts and the maxima: its read-back waits for both streams.
-            hipStream_t aux = stream, aux2 = stream;
-            if (use_side) {
-                aux = cx.side_stream; aux2 = cx.pos_stream;
-                HIP_CHECK(hipStreamWaitEvent(aux, cx.side_ev[0], 0)); side.pending++;
-                HIP_CHECK(hipStreamWaitEvent(aux2, cx.pos_ev[0], 0)); pos.pending = 1;
-            }
+            const hipStream_t aux = side.behind(SIDE_PLAN_FORK), aux2 = pos.behind(POS_PLAN_FORK);
             if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
-            if (use_side) HIP_CHECK(hipEventRecord(cx.side_ev[2], aux));
+            side.mark(SIDE_CHECKS_DONE);
             hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
             if (!items_known) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
-            if (use_side) HIP_CHECK(hipEventRecord(cx.pos_ev[2], aux2));
+            pos.mark(POS_MAXIMA_DONE);
             // (the user of every test entry, for the positives' scores by entry: index pointers only)
-            if (attempt == 0 && flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, aux2, m, c.test_p, ent_user, plan);
+            if (attempt == 0 && flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, pos.on(), m, c.test_p, ent_user, plan);
             // (463 MB of writes at BASELINE C2; four resident blocks per CU leave half of the wave slots to the plan's kernels and the
             // read-back's copy.  With the positives' scores by entry the kernel also says which test items are train items, `ent_masked`:
             // a bit of the row it has just built.)
             if (attempt == 0 && std::is_same<T, float>::value && use_side && !c.ext_bits && dense_ok) {
                 SweepArgs probe{};
                 const bool guess = want_auc && !ext_topk && !g_sw.no_test_mask;
-                const unsigned *had = (const unsigned *)cx.bits_ptr;
-                const bool reuse = c.same_train_rows && had && !cx.bits_partial && cx.bits_words == dense_row_words(n) && cx.bits_m == m && cx.bits_masked == guess &&
-                                   had == (const unsigned *)ws.get("train_bits", (size_t)m * (size_t)dense_row_words(n) * 4);
-                if (!reuse) {
-                    set_train_bits(probe, cx, c, m, n, dense_ok, aux, guess, false, false, flat_early ? ent_masked : nullptr);
-                    HIP_CHECK(hipEventRecord(cx.side_ev[4], aux));
-                    HIP_CHECK(hipEventRecord(cx.side_ev[5], aux));
+                (void)ws.get("train_bits", (size_t)m * (size_t)dense_row_words(n) * 4);
+                if (!(c.same_train_rows && cx.dense.fits(ws, m, dense_row_words(n), guess))) {
+                    set_train_bits(probe, cx, c, m, n, dense_ok, side.on(), guess, false, false, flat_early ? ent_masked : nullptr);
+                    side.mark(SIDE_ROWS_AND_PACKS); side.mark(SIDE_ROWS_FOR_POS);
                     bits_early = true; bits_early_masked = guess; masked_from_bits = flat_early;
                 }
             }
-            if (use_side) { HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[2], 0)); HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[2], 0)); }
+            side.await(SIDE_CHECKS_DONE, stream); pos.await(POS_MAXIMA_DONE, stream);
             HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
             if (attempt == 0 && flat_early) {
                 // The scores of the test entries (k_pos_scores_flat) depend on the inputs and on the users' flags alone: they run on the
@@ -983,34 +1023,24 @@ struct Pipeline {
                 // copy: their blocks take every wave slot they find, and a plan kernel's block of 1,024 threads then waits for sixteen
                 // slots of one CU to fall free at once (measured: the read-back 0.2 ms late).  Without dense train rows k_test_masked says
                 // which test items are train items, behind the scores.
-                if (use_side) {
-                    HIP_CHECK(hipEventRecord(cx.pos_ev[3], stream));
-                    HIP_CHECK(hipStreamWaitEvent(cx.pos_stream, cx.pos_ev[3], 0));
-                }
-                hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, aux2, pf, ent_user);
+                const hipStream_t sc = pos.fork(POS_SCORES_AFTER_COPY);
+                hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pf, ent_user);
                 // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
-                if (masked_from_bits) HIP_CHECK(hipStreamWaitEvent(aux2, cx.side_ev[5], 0));
-                else hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, aux2, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
-                hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, aux2, pf, ent_masked);
-                if (use_side) HIP_CHECK(hipEventRecord(cx.pos_ev[1], cx.pos_stream));
+                if (masked_from_bits) side.await(SIDE_ROWS_FOR_POS, sc);
+                else hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
+                hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, ent_masked);
+                pos.mark(POS_SCORES_DONE);
             }
             RM_TRACE_POINT("run: plan chain + side kernels enqueued");
             HIP_CHECK(hipStreamSynchronize(stream));
             RM_TRACE_POINT("run: plan read back");
-            // (the stream has waited for the checks and the maxima: only the dense train rows of the first attempt may still be running on
-            // the side stream, only the positives' scores on theirs)
-            if (use_side && !(attempt == 0 && bits_early)) side.pending--;
-            if (use_side && !flat_early) pos.pending = 0;
             hp = *cx.pinned_plan;
             throw_csr_defects(hp, c, cx);
             // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
             if (ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0) {
                 ca.allow_stream = 0; ca.check_ptr = 0;
                 // (attempt 0's kernels on BOTH side streams read `flags` and `plan`, which the second plan rewrites: wait for them)
-                if (use_side) {
-                    HIP_CHECK(hipStreamSynchronize(cx.side_stream)); side.pending = bits_early ? 1 : 0;
-                    if (cx.pos_stream) HIP_CHECK(hipStreamSynchronize(cx.pos_stream));
-                }
+                side.sync(); pos.sync();
                 continue;
             }
             break;
@@ -1021,8 +1051,8 @@ struct Pipeline {
         n_stream = (want_auc || ext_topk) ? hp.class_count[STREAM_CLASS] : 0;
         stream_slot0 = n_stream > 0 ? hp.class_offset[STREAM_CLASS] : n_slots;
         // |any partial sum| <= k * max|A| * max|B|: if that is comfortably finite in T, no score is NaN / Inf
-        if (items_known) { hp.amax_b = cx.packed_amax_b; hp.nonfinite_b = cx.packed_nonfinite_b; }
-        else { cx.packed_amax_b = hp.amax_b; cx.packed_nonfinite_b = hp.nonfinite_b; }
+        if (items_known) { hp.amax_b = cx.packed.amax_b; hp.nonfinite_b = cx.packed.nonfinite_b; }
+        else { cx.packed.amax_b = hp.amax_b; cx.packed.nonfinite_b = hp.nonfinite_b; }
         double amax_a, amax_b;
         std::memcpy(&amax_a, &hp.amax_a, 8); std::memcpy(&amax_b, &hp.amax_b, 8);
         const double tmax = std::is_same<T, float>::value ? 3.0e38 : 1.0e308;
@@ -1043,10 +1073,8 @@ struct Pipeline {
         fa.heavy_topv = (T *)ws.get("heavy_topv", sizeof(T) * (size_t)m * (size_t)fa.heavy_ld);
         fa.heavy_nan = (unsigned char *)ws.get("heavy_nan", (size_t)m);
         fa.heavy_users = heavy_users; fa.n_heavy = hp.n_heavy;
-        hipStream_t tv_stream = stream;
-        if (use_side) tv_stream = side.fork(stream);
-        hipLaunchKernelGGL((k_top_values<T, T>), dim3(cdiv((long long)hp.n_heavy * WAVE, 256)), dim3(256), 0, tv_stream, fa);
-        if (use_side) { HIP_CHECK(hipEventRecord(cx.side_ev[3], tv_stream)); topv_pending = true; }
+        hipLaunchKernelGGL((k_top_values<T, T>), dim3(cdiv((long long)hp.n_heavy * WAVE, 256)), dim3(256), 0, side.fork(SIDE_FORK), fa);
+        side.mark(SIDE_TOP_VALUES);
     }
 
     // ---- prep: the finalisation's arguments, operand packing, dense train rows, positives tables, seeds ----
@@ -1078,27 +1106,20 @@ struct Pipeline {
         typename P::PackT *Bp = (typename P::PackT *)ws.get("Bp", 16 * (size_t)bp_units);
         typename P::PackT *Ap = (typename P::PackT *)ws.get("Ap", 16 * (size_t)ap_units);
         // the packed item image survives between the batches of one host call (same B, same geometry)
-        const bool items_packed = items_known && cx.packed_tile == tile_items && cx.packed_ng == NG && cx.packed_ptr == (const void *)Bp;
+        const bool items_packed = cx.packed.holds(ws, c.items_tag, tile_items, NG);
         // Only the sweep reads the packed images: with a side stream they are made there, behind the dense train rows and beside the
         // positives' kernels (120 us of BASELINE C2's preparation that sat in front of k_pos_scores); the sweep's launch waits for both.
         const bool packs_side = use_side && want_auc && cx.side_stream != nullptr;
-        pack_operands(c.A, c.lda, c.B, c.ldb, n, k, NG, tile_items, slot_user, n_slots, Ap, ap_units, Bp, bp_units, packs_side ? cx.side_stream : stream, !items_packed);
-        if (packs_side) {
-            HIP_CHECK(hipEventRecord(cx.side_ev[4], cx.side_stream));   // (behind the rows, when they were launched: one event for both)
-            if (!bits_early) side.pending++;
-        }
-        cx.packed_tag = c.items_tag; cx.packed_tile = tile_items; cx.packed_ng = NG; cx.packed_ptr = (const void *)Bp;
+        pack_operands(c.A, c.lda, c.B, c.ldb, n, k, NG, tile_items, slot_user, n_slots, Ap, ap_units, Bp, bp_units, packs_side ? side.on() : stream, !items_packed);
+        if (packs_side) side.mark(SIDE_ROWS_AND_PACKS);                 // (behind the rows, when they were launched: the sweep waits for both)
+        cx.packed.set(ws, c.items_tag, tile_items, NG);
         launch_top_values();
 
         // ---- dense train rows (fp32, small item counts) ----
         // (measured: on the side stream beside the positives' kernels they gain nothing -- both are bound by memory; r3_ab_c2.txt)
         // (rows launched beside the plan read-back that turn out not to be the ones wanted -- a wrong guess of `mask_test`, rows handed over
         // by another pass -- are waited for here, before anything is launched over them; the usual case waits in front of the sweep)
-        bits_wait = bits_early || packs_side;
-        if (bits_early && (bits_early_masked != g.mask_test || (g.use_ext_bits && dense_ok))) {
-            HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[4], 0));
-            side.pending--; bits_wait = false;
-        }
+        if (bits_early && (bits_early_masked != g.mask_test || (g.use_ext_bits && dense_ok))) side.await(SIDE_ROWS_AND_PACKS, stream);
         if (g.use_ext_bits && dense_ok) set_ext_bits(sa, c.ext_bits, (int)c.ext_words);
         else set_train_bits(sa, cx, c, m, n, dense_ok, stream, g.mask_test, bits_early, bits_early_masked);
 
@@ -1140,10 +1161,7 @@ struct Pipeline {
 
         // the dense train rows, launched beside the plan read-back: the sweep reads them, and so do the passes that start at
         // `flags_event` (their noise rows, their own sweeps) -- nothing in front of this point does
-        if (bits_wait) {
-            HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[4], 0));
-            side.pending--;
-        }
+        if (side.marked(SIDE_ROWS_AND_PACKS)) side.await(SIDE_ROWS_AND_PACKS, stream);
         // Sample seeds (k_seed_from_sample, rm_prep.hpp): the sweep's DUMP variant scores the first S items for every slot, a
         // wavefront per slot takes the K-th best candidate of them, and the lane buffers start with a pass rate of K / S.
         const bool sample_lists = !lane_lists && !ext_topk && sizeof(T) == 4;      // (the LDS / HBM lists: seeded as well, from a smaller sample)
@@ -1180,14 +1198,10 @@ struct Pipeline {
         const bool flat = flat_early;
         // The streamed users' positives (the all-pairs rank of long test rows: vector work) run on a stream of their own beside
         // the table users'
-        hipStream_t ps = stream;
+        // (not the side stream: that one carries the dense train rows and the operand packing, 0.3 ms the streamed users' chain
+        // used to queue behind.  The host has waited for the call's stream since: nothing to wait for over there.)
         const bool pos_beside = use_side && n_stream > 0 && stream_slot0 > 0 && !g_sw.no_pos_beside;
-        if (pos_beside) {
-            // (not the side stream: that one carries the dense train rows and the operand packing, 0.3 ms the streamed users' chain
-            // used to queue behind.  The host has waited for the call's stream since: nothing to wait for over there.)
-            ps = pos.get();
-            pos.pending = 1;
-        }
+        hipStream_t ps = pos_beside ? pos.on() : stream;
         PosArgs<T> pb = pa;
         // (with the scores by entry the positives' stream is busy with them: the tables are filled on the call's stream meanwhile)
         const hipStream_t fill = (flat && pos_beside) ? stream : ps;
@@ -1203,16 +1217,16 @@ struct Pipeline {
         const int nsc = hp.n_stream_chunks;
         hipLaunchKernelGGL(k_init_tables<T>, dim3(cdiv(rows * GU, 256)), dim3(256), 0, stream, pos_score, hist, rows * GU);
         if (flat) {
-            if (pos_beside && n_stream > 0) { HIP_CHECK(hipEventRecord(cx.pos_ev[2], stream)); HIP_CHECK(hipStreamWaitEvent(ps, cx.pos_ev[2], 0)); }
+            if (pos_beside) ps = pos.fork(POS_TABLES_INIT);
             // (the scores are the last thing on the positives' stream: whoever is not on it waits for them)
-            if (use_side) { HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[1], 0)); if (!pos_beside) pos.pending = 0; }
+            pos.await(POS_SCORES_DONE, stream);
         } else {
             if (n_stream > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(nsc, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, ps, pb, sc_user, sc_chunk, nsc);
             if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(stream_slot0, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
         }
         if (n_stream > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)nsc * WAVE, 256)), dim3(256), 0, ps, pb, sc_user, sc_chunk, nsc);
         if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)stream_slot0 * WAVE, 256)), dim3(256), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
-        if (pos_beside) { HIP_CHECK(hipEventRecord(cx.pos_ev[4], ps)); HIP_CHECK(hipStreamWaitEvent(stream, cx.pos_ev[4], 0)); pos.pending = 0; }
+        if (pos_beside) pos.join(POS_STREAMED_PLACED);
     }
 
     // ---- sweep: the flags for the tie noise's exact pass, then the sweep launch (two with a depth split) ----
@@ -1228,10 +1242,10 @@ struct Pipeline {
             }
             HIP_CHECK(hipEventRecord(c.flags_event, stream));
         }
-        HIP_CHECK(hipEventRecord(cx.ev[1], stream));
+        HIP_CHECK(hipEventRecord(cx.ev[EV_PREP_END], stream));
         double *tm = cx.timings;
         if (n_slots == 0) {
-            HIP_CHECK(hipEventRecord(cx.ev[2], stream));
+            HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
             tm[4] = 0; tm[5] = 0; tm[6] = 0; tm[7] = 0;
             return;
         }
@@ -1239,7 +1253,7 @@ struct Pipeline {
         if (g.u_split > 0) {
             // Depth split: the two launches run side by side on two streams so that neither pays a partially filled last round of its own.
             const int u_split = g.u_split, n_ublocks = g.n_ublocks;
-            hipStream_t sd = side.get();
+            side.enabled = true;                                   // (the second launch runs beside the first whatever RM_DEBUG_NO_SIDE says)
             typename P::Args sb = sa;                              // the deep blocks: lists in HBM, as computed above
             P::set_ublocks(sb, u_split, n_ublocks - u_split);
             typename P::Args sl = sa;                              // the shallow blocks: lists in LDS
@@ -1249,12 +1263,11 @@ struct Pipeline {
             sb.tail_ublocks = g.tail_ublocks - sl.tail_ublocks;
             P::set_pending(sl, g.pend_cap, 0);
             P::set_sync(sl, (int)(g.lds_l - SYNC_BYTES));
-            HIP_CHECK(hipEventRecord(cx.side_ev[0], stream));
-            HIP_CHECK(hipStreamWaitEvent(sd, cx.side_ev[0], 0));
-            dispatch_sweep(want_auc, false, false, g.nsub, NG, dim3((unsigned)((n_ublocks - u_split - sb.tail_ublocks) * g.n_splits + sb.tail_ublocks * g.tail_splits)), g.lds_total, sd, sb);
-            HIP_CHECK(hipEventRecord(cx.side_ev[1], sd));
+            dispatch_sweep(want_auc, false, false, g.nsub, NG, dim3((unsigned)((n_ublocks - u_split - sb.tail_ublocks) * g.n_splits + sb.tail_ublocks * g.tail_splits)), g.lds_total, side.fork(SIDE_SWEEP_FORK), sb);
+            side.mark(SIDE_SWEEP_DEEP_DONE);
             dispatch_sweep(want_auc, false, true, g.nsub, NG, dim3((unsigned)((u_split - sl.tail_ublocks) * g.n_splits + sl.tail_ublocks * g.tail_splits)), g.lds_l, stream, sl);
-            HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[1], 0));
+            side.await(SIDE_SWEEP_DEEP_DONE, stream);
+            side.enabled = use_side;
         } else {
             // (Measured and dropped: the blocks made of streamed users only as a second launch of the sweep variant without rank
             // counting on a side stream, followed there by k_rank_streamed, beside the main launch.  At C2 the step time did
@@ -1263,7 +1276,7 @@ struct Pipeline {
             dispatch_sweep(want_auc, false, g.list_in_lds, g.nsub, NG, dim3(n_blocks), g.lds_total, stream, sa);
         }
         RM_TRACE_POINT("run: sweep enqueued");
-        HIP_CHECK(hipEventRecord(cx.ev[2], stream));
+        HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
         if (lane_lists) {
             collect = true;
             collect_g = CollectGeom{sa.ublock0, sa.n_ublocks, g.n_splits, g.tail_ublocks, g.tail_splits, g.nsub, GU, P::lanes_per_user, sa.lane_cap, g.part_extra ? g.n_part - 1 : -1};
@@ -1356,22 +1369,16 @@ struct Pipeline {
             auc_launch = ext_topk || !(top * (long long)(sizeof(T) / 4) + hp.max_npos + 1 <= STREAM_RANK_LDS / 4);
         }
         hipStream_t rank_stream = stream;
-        if (ranks_beside) { rank_stream = side.fork(stream); rank_streamed_rows(0, n_stream, rank_stream); }
+        if (ranks_beside) { rank_stream = side.fork(SIDE_FORK); rank_streamed_rows(0, n_stream, rank_stream); }
         if (g.mask_test) {
             // (the table users' test items were put back by the sweep, rm_sweep.hpp; the streamed users' are this kernel's)
             if (n_slots > stream_slot0)
                 hipLaunchKernelGGL((k_merge_positives<T, T>), dim3(cdiv(n_slots - stream_slot0, MERGE_WAVES)), dim3(MERGE_WAVES * WAVE), 0, stream, fa, g.n_part - 1, stream_slot0);
-            if (ranks_beside && auc_launch) {                          // (it counts the streamed users' own test items: before k_auc_streamed)
-                HIP_CHECK(hipEventRecord(cx.side_ev[2], stream));
-                HIP_CHECK(hipStreamWaitEvent(rank_stream, cx.side_ev[2], 0));
-            }
+            if (ranks_beside && auc_launch) rank_stream = side.fork(SIDE_MERGED);     // (it counts the streamed users' own test items: before k_auc_streamed)
         }
         if (ranks_beside && auc_launch) auc_streamed_rows(0, n_stream, rank_stream);
         hipLaunchKernelGGL((k_finalize_skipped<T, T>), dim3(cdiv(m, 256)), dim3(256), 0, stream, fa);
-        if (topv_pending) {                                           // (k_top_values, launched beside the preparation)
-            HIP_CHECK(hipStreamWaitEvent(stream, cx.side_ev[3], 0));
-            side.pending--;
-        }
+        if (side.marked(SIDE_TOP_VALUES)) side.await(SIDE_TOP_VALUES, stream);       // (k_top_values, launched beside the preparation)
         collect_lists();
         select_lists();
         if (n_slots > 0) {
@@ -1387,11 +1394,11 @@ struct Pipeline {
                 // their ranks are still being counted there, and a short kernel fills those two in behind the join
                 fa.auc_defer_slot0 = stream_slot0;
                 finalize_slots(0, n_slots, fin_lds);
-                side.join(stream);
+                side.join(SIDE_JOIN);
                 hipLaunchKernelGGL((k_finalize_auc<T, T>), dim3(cdiv(n_slots - stream_slot0, 256)), dim3(256), 0, stream, fa);
             } else if (ranks_beside) {
                 finalize_slots(0, stream_slot0, fin_lds);
-                side.join(stream);
+                side.join(SIDE_JOIN);
                 finalize_slots(stream_slot0, n_slots, fin_lds);
             } else finalize_slots(0, n_slots, fin_lds);
         }
@@ -1407,16 +1414,15 @@ struct Pipeline {
             hipLaunchKernelGGL(k_export_pos_rank, dim3(cdiv(m, 128)), dim3(128), 0, stream, c.nnz_test, m, c.test_p, flags, pos_order, rank_sorted, c.pos_rank,
                                (want_auc && n_slots > 0) ? 1 : 0, c.status);
         RM_TRACE_POINT("run: finalisation enqueued");
-        HIP_CHECK(hipEventRecord(cx.ev[3], stream));
+        HIP_CHECK(hipEventRecord(cx.ev[EV_END], stream));
         HIP_CHECK(hipEventRecord(cx.done, stream));
         cx.ev_recorded = true;
         HIP_CHECK(hipGetLastError());
     }
 };
 
-// One pass of a call: DESIGN.md section 1, stage by stage.  Side streams: the context's side stream carries the CSR index checks,
-// the early dense train rows, the operand packing, k_top_values, a depth-split call's second sweep launch and the streamed users'
-// ranks; the positives' stream carries the maxima, the positives' scores by entry and the streamed users' positives.
+// One pass of a call: DESIGN.md section 1, stage by stage; what runs on the context's side stream and on the positives' stream, and
+// which event orders it against the call's stream, is the table at the end of that section.
 template <class T>
 void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
 {
@@ -1461,13 +1467,13 @@ void noise_make_rows(Ctx &cx, const Call<T> &c0, const NoiseGeom<T> &g, const in
     hipLaunchKernelGGL(k_mt_draws, dim3(cdiv(rows, MT_WAVES)), dim3(MT_WAVES * WAVE), 0, stream, row_user, rows, c0.seed, user0,
                        train_p, n, g.per, D, g.d_ld);
     // the dense train rows of this call's own first pass (fp32, small item counts), when they cover exactly these users
-    const bool dense = cx.bits_tag != 0 && cx.bits_tag == c0.items_tag && cx.bits_train_p == train_p && cx.bits_m == m && row_user != nullptr && !cx.bits_partial;
+    const bool dense = row_user != nullptr && cx.dense.built_by(cx.ws, c0.items_tag, train_p, m);
     if (own_bits)                                                  // unmasked dense rows built for exactly these users (run_host_range)
         hipLaunchKernelGGL(k_noise_rows_bits<T>, dim3(rows), dim3(NOISE_ROWS_THREADS), sizeof(int) * (size_t)(2 * own_words + 1), stream, row_user, rows,
                            own_bits, (int)own_words, n, 0, train_p, c0.train_i, c0.test_p, c0.test_i, D, g.d_ld, E, g.e_ld);
     else if (dense)
-        hipLaunchKernelGGL(k_noise_rows_bits<T>, dim3(rows), dim3(NOISE_ROWS_THREADS), sizeof(int) * (size_t)(2 * cx.bits_words + 1), stream, row_user, rows,
-                           (const unsigned *)cx.bits_ptr, (int)cx.bits_words, n, cx.bits_masked ? 1 : 0, train_p, c0.train_i, c0.test_p, c0.test_i,
+        hipLaunchKernelGGL(k_noise_rows_bits<T>, dim3(rows), dim3(NOISE_ROWS_THREADS), sizeof(int) * (size_t)(2 * cx.dense.words + 1), stream, row_user, rows,
+                           cx.dense.rows(cx.ws), (int)cx.dense.words, n, cx.dense.masked ? 1 : 0, train_p, c0.train_i, c0.test_p, c0.test_i,
                            D, g.d_ld, E, g.e_ld);
     else
         hipLaunchKernelGGL(k_noise_rows<T>, dim3(cdiv((long long)rows * g.e_ld, 256)), dim3(256), 0, stream, row_user, rows, train_p, c0.train_i, n,
@@ -1561,13 +1567,13 @@ template <class T> struct NoiseBeside {
             const bool fit = std::is_same<T, float>::value && dense_rows_fit(pw, m, n);
             if (fit) {
                 bits = (unsigned *)pw.get("train_bits", (size_t)m * (size_t)words * 4);
-                pc->bits_tag = 0; pc->bits_ptr = nullptr;
+                pc->dense.invalidate();
                 launch_train_bits(ps, m, n, (int)words, c.train_p, c.train_i, (const int *)nullptr, c.test_i, bits, (const Plan *)nullptr, only);
                 c.ext_bits = bits; c.ext_words = words; c.ext_masked = false;
             }
             c.dense_fit = fit ? 1 : 0;
-        } else if (cx.bits_tag != 0 && cx.bits_tag == c.items_tag && cx.bits_train_p == c.train_p && cx.bits_m == m && !cx.bits_partial) {
-            c.ext_bits = (const unsigned *)cx.bits_ptr; c.ext_words = cx.bits_words; c.ext_masked = cx.bits_masked;      // the first pass's rows
+        } else if (cx.dense.built_by(cx.ws, c.items_tag, c.train_p, m)) {
+            c.ext_bits = cx.dense.rows(cx.ws); c.ext_words = cx.dense.words; c.ext_masked = cx.dense.masked;             // the first pass's rows
         }
         noise_make_rows<T>(own_rows ? *pc : cx, c, g, row_user, rows_n, c.train_p, c.user0, D, E, ps, bits, words);
         set_exact_pass<T>(c, only, noise_row, 0, E, g.e_ld, rows_n);
@@ -2085,10 +2091,9 @@ template <class T> struct HostRange {
         if (range_noise) flagged_total += ctxs[which]->noise_words->batch_flagged;
         if (n_batches > 1) {                                          // more than one batch: add up the stage timings
             Ctx &c = *ctxs[which];
-            float ta = 0, tb = 0, tc = 0, td = 0;
-            (void)hipEventElapsedTime(&ta, c.ev[0], c.ev[1]); (void)hipEventElapsedTime(&tb, c.ev[1], c.ev[2]);
-            (void)hipEventElapsedTime(&tc, c.ev[2], c.ev[3]); (void)hipEventElapsedTime(&td, c.ev[0], c.ev[3]);
-            cx.acc[0] += ta; cx.acc[1] += tb; cx.acc[2] += tc; cx.acc[3] += td;
+            float ms[4] = {0, 0, 0, 0};
+            c.stage_ms(ms);
+            for (int i = 0; i < 4; i++) cx.acc[i] += ms[i];
             c.ev_recorded = false; cx.ev_recorded = false;
         }
     }
@@ -2123,7 +2128,7 @@ template <class T> struct HostRange {
         if (bi + 1 < n_batches && !g_interrupt) upload_users(bi + 1);
         stamp("next rows enqueued");
         if (snap_here && !g_interrupt) {
-            exact_beside_last(b0, (two_ctx && bi > 0) ? ctxs[(bi - 1) & 1]->ev[1] : (hipEvent_t)nullptr);
+            exact_beside_last(b0, (two_ctx && bi > 0) ? ctxs[(bi - 1) & 1]->ev[EV_PREP_END] : (hipEvent_t)nullptr);
             stamp("exact pass beside the last batch enqueued");
         }
         if (!two_ctx) finish(which);
@@ -2165,7 +2170,7 @@ template <class T> struct HostRange {
     {
         if (!lay.rec_w) return;
         // (`other`: the batch before the last runs on the other context's stream: its positives -- the early flags -- are in place once its
-        // own sweep has been launched, the event run() records as ev[1]; what its k_finalize flags later is the late pass's)
+        // own sweep has been launched, the event run() records as EV_PREP_END; what its k_finalize flags later is the late pass's)
         bes.open(other);
         // (the earlier batches' flags as they stand: a flag their k_finalize sets later is the sequential pass's, below)
         if (b0_last > 0) HIP_CHECK(hipMemcpyAsync(range_snap, range_flag, sizeof(int) * (size_t)b0_last, hipMemcpyDeviceToDevice, bes.ps));
@@ -2403,7 +2408,7 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
     Ctx &cx = context(0);
     std::lock_guard<std::mutex> lk(cx.mu);
     Workspace &ws = cx.ws;
-    cx.packed_tag = 0;                                       // the packed item image is overwritten below
+    cx.packed.invalidate();                                  // the packed item image is overwritten below
     hipStream_t stream = nullptr;
     T *dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
     T *dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
@@ -2636,15 +2641,12 @@ extern "C" int rm_get_timings(double *out, int n)
 {
     Ctx *cx = g_last_ctx;
     if (!out || n <= 0 || !cx || !cx->ev_valid) return 0;
-    float a = 0, b = 0, c = 0, d = 0;
+    float ms[4] = {0, 0, 0, 0};
     if (cx->ev_recorded) {
-        if (hipEventSynchronize(cx->ev[3]) != hipSuccess) return 0;
-        (void)hipEventElapsedTime(&a, cx->ev[0], cx->ev[1]);
-        (void)hipEventElapsedTime(&b, cx->ev[1], cx->ev[2]);
-        (void)hipEventElapsedTime(&c, cx->ev[2], cx->ev[3]);
-        (void)hipEventElapsedTime(&d, cx->ev[0], cx->ev[3]);
+        if (hipEventSynchronize(cx->ev[EV_END]) != hipSuccess) return 0;
+        cx->stage_ms(ms);
     }
-    cx->timings[0] = cx->acc[0] + a; cx->timings[1] = cx->acc[1] + b; cx->timings[2] = cx->acc[2] + c; cx->timings[3] = cx->acc[3] + d;
+    for (int i = 0; i < 4; i++) cx->timings[i] = cx->acc[i] + ms[i];
     const int cnt = n < 10 ? n : 10;
     for (int i = 0; i < cnt && i < 8; i++) out[i] = cx->timings[i];
     if (cnt > 8) out[8] = cx->timed_slots;
@@ -2666,9 +2668,7 @@ extern "C" int rm_release_workspace(void)
         }
         for (Ctx *c : mine) {
             std::lock_guard<std::mutex> cl(c->mu);
-            c->ws.release();
-            // (every marker of cached CONTENT goes with the buffers: a fresh allocation may come back at the old address)
-            c->packed_tag = 0; c->packed_ptr = nullptr; c->bits_tag = 0; c->bits_ptr = nullptr; c->log2_ptr = nullptr; c->log2_K = 0;
+            c->ws.release();                  // (what the context remembers of the buffers' contents goes with their stamps)
         }
     });
 }

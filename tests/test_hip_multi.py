@@ -481,3 +481,35 @@ print("NO_DEADLOCK")
 """ % ROOT
     res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert res.returncode == 0 and "NO_DEADLOCK" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+
+
+def test_cached_contents_do_not_outlive_their_allocation(hip, oracle, monkeypatch):
+    """What a context remembers about its buffers' contents -- the packed item image, the dense train rows, the DCG discount table
+    -- holds for the ALLOCATION it was made in: after rm_release_workspace() a call of the same shapes gets its buffers back at
+    sizes (and often addresses) it had before, with other factors, rows and test values behind them, and a larger call
+    reallocates every per-user buffer by growth.  fp32, all ten metrics, K = 10, tie noise on with a few cold items (all-zero
+    factors: users the noise reorders, so that the exact pass takes over the first pass's dense rows); every call against the
+    oracle.  Then release-and-same-shape and growth again through two batches of one host call, which share the item image and
+    its tag between two contexts (a batch holds at least 1,024 users: 1,500 users in batches of 1,024, then 2,600 in batches of
+    2,048)."""
+    from _parity import _check_against_oracle
+    from recometrics_amd.synth import make_problem
+
+    def problem(m, seed):
+        pr = make_problem(m, 3000, 16, np.float32, seed=seed)
+        pr["B"] = pr["B"].copy()
+        pr["B"][np.random.default_rng(seed).random(3000) < 0.05] = 0
+        return pr
+
+    def check(m, seed):
+        _check_against_oracle(hip, oracle, problem(m, seed), 10, noise=True, seed=seed)
+    check(300, 1)
+    hip.load().rm_release_workspace()
+    check(300, 2)
+    check(900, 3)
+    monkeypatch.setenv("RM_BATCH_USERS", "1024")
+    check(1500, 1)
+    hip.load().rm_release_workspace()
+    check(1500, 2)
+    monkeypatch.setenv("RM_BATCH_USERS", "2048")
+    check(2600, 3)
