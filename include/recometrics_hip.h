@@ -104,6 +104,63 @@ int rm_calc_metrics_dev_f64(
     int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test,
     uint64_t seed, void *stream);
 
+/* Metrics from the CALLER'S score matrix (no counterpart in the reference, whose scores are always dot products of two factor matrices): any model that has its
+ * scores as a [users x items] array -- a two-tower model with a non-linear head, an item-kNN, a re-ranker, popularity with
+ * business rules -- is evaluated by the same ten metrics.  The score of item i for user u is S[u * lds + i], exactly as given:
+ * row-major, lds >= n, otherwise arbitrary (rows need not be 16-byte aligned); S is never modified.
+ * Everything else is rm_calc_metrics_* with break_ties_with_noise = 0: eligibility (consider_cold_start, min_items_pool,
+ * min_pos_test), candidates = the items outside the user's train row, the validity rules, the top-K walk, the NaN overrides,
+ * ROC / PR-AUC, NDCG and `cumulative` layout, the ten outputs in the same order (NULL = not requested).  Equal scores are ordered
+ * by item id (+0 == -0); there is no tie noise and no `seed`.  For factors whose k-ordered fma chain yields S, all ten outputs
+ * are the same bits as rm_calc_metrics_* writes.
+ * A score at a TRAIN item is never looked at: NaN or +-Inf there changes nothing.  A NaN among a user's candidates makes that user
+ * NaN in every output; +-Inf among the candidates is treated as the factor call treats it (an infinite best score, or an infinite
+ * score at the other end of what the request ranks -- the K-th place, the worst candidate with ROC-AUC or K >= candidates -- makes
+ * the user NaN).
+ * CSR arrays: validated as for the factor call (bad index pointers / indices: RM_ERR_INVALID naming the row; unsorted rows are
+ * sorted in a copy).  m == 0 returns RM_OK and writes nothing.  RM_ERR_INVALID, decided on the host before any device work:
+ * lds < n, n <= 0, k_metrics outside [1, n], S == NULL, NDCG requested with Xtest_csr == NULL.
+ * rm_calc_metrics_scores_f32/f64: HOST pointers, through the machinery of the host-pointer metric call -- user batches sized so
+ * that a batch's rows (two upload buffers and the masked copy) fit the device, rm_set_devices shards, SIGINT -> RM_ERR_INTERRUPTED
+ * with the finished batches kept, `nthreads` for the fall-back sort; results depend neither on the device list nor on the
+ * batch size.  rm_calc_metrics_scores_dev_f32/f64: DEVICE pointers on the current device, asynchronous on `stream` like
+ * rm_calc_metrics_dev_*; one masked score row (budgeted as n rounded up to a multiple of 192 items, x the score's size) per user is kept in
+ * device memory, and when the rows of m users do not fit a third of what is free the call answers RM_ERR_NOMEM with the bytes per row
+ * and the largest m that fits in the message, as the k_metrics > 256 factor call does.  rm_get_timings covers all four; out[1]
+ * then brackets the kernel that copies and masks the score rows (there is no sweep), out[6] is its blocks = evaluated users. */
+int rm_calc_metrics_scores_f32(
+    const float *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const float *Xtest_csr,
+    int32_t k_metrics, int cumulative,
+    float *p_at_k, float *tp_at_k, float *r_at_k, float *ap_at_k, float *tap_at_k,
+    float *ndcg_at_k, float *hit_at_k, float *rr_at_k, float *roc_auc, float *pr_auc,
+    int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads);
+int rm_calc_metrics_scores_f64(
+    const double *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const double *Xtest_csr,
+    int32_t k_metrics, int cumulative,
+    double *p_at_k, double *tp_at_k, double *r_at_k, double *ap_at_k, double *tap_at_k,
+    double *ndcg_at_k, double *hit_at_k, double *rr_at_k, double *roc_auc, double *pr_auc,
+    int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads);
+int rm_calc_metrics_scores_dev_f32(
+    const float *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const float *Xtest_csr, int64_t nnz_test,
+    int32_t k_metrics, int cumulative,
+    float *p_at_k, float *tp_at_k, float *r_at_k, float *ap_at_k, float *tap_at_k,
+    float *ndcg_at_k, float *hit_at_k, float *rr_at_k, float *roc_auc, float *pr_auc,
+    int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, void *stream);
+int rm_calc_metrics_scores_dev_f64(
+    const double *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const double *Xtest_csr, int64_t nnz_test,
+    int32_t k_metrics, int cumulative,
+    double *p_at_k, double *tp_at_k, double *r_at_k, double *ap_at_k, double *tap_at_k,
+    double *ndcg_at_k, double *hit_at_k, double *rr_at_k, double *roc_auc, double *pr_auc,
+    int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, void *stream);
+
 /* Ranking introspection (host pointers): the ordered top-K item ids / scores per user ([m x k_metrics], -1 / NaN
  * padded), the 1-based position of every test item in the user's FULL candidate ranking ([nnz_test], 0 when the
  * item is masked by the train row or the user is skipped) and status[m] (0 = ranked, 1 = user skipped).  These are

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _binding
 
-__all__ = ["calc_reco_metrics", "recommend_topk", "split_reco_train_test"]
+__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_scores", "recommend_topk", "split_reco_train_test"]
 __version__ = "0.1.0"
 
 # (keyword of calc_reco_metrics, name in the C-ABI order, key of the result dict) -- reference __init__.py:590-613
@@ -267,6 +267,120 @@ def calc_reco_metrics(
         A, lda, B, ldb, c(X_train.indptr), c(X_train.indices), c(X_test.indptr), c(X_test.indices), c(test_values),
         k, want, bool(cumulative), bool(break_ties_with_noise),
         bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, seed, outs=outs)
+
+    if block is not None:
+        import pandas as pd
+        if rename_k:
+            keys = [key[:-1] + str(k) if key.endswith("@K") else key for key in keys]
+        return pd.DataFrame(block, columns=keys, copy=False)
+    out = {key: arr for (_, _, key), arr in zip(_METRICS, arrays) if arr.shape[0]}
+    if not as_df:
+        out["K"] = k
+        return out
+    return _as_frame(out, k, bool(cumulative), bool(rename_k))
+
+
+def calc_reco_metrics_from_scores(
+    X_train, X_test,
+    scores,
+    k=5,
+    as_df=True,
+    precision=True,
+    trunc_precision=False,
+    recall=False,
+    average_precision=True,
+    trunc_average_precision=False,
+    ndcg=True,
+    hit=False,
+    rr=False,
+    roc_auc=False,
+    pr_auc=False,
+    all_metrics=False,
+    rename_k=True,
+    min_pos_test=1,
+    min_items_pool=2,
+    consider_cold_start=True,
+    cumulative=False,
+    nthreads=-1,
+):
+    """The metrics of :func:`calc_reco_metrics` for ANY model: ``scores`` is a NumPy ``[users, items]`` array with the score of
+    every item for every user -- a two-tower model with a non-linear head, an item-kNN, a re-ranker, popularity with business
+    rules -- instead of the factor matrices ``A`` and ``B``.  The reference has no such call.
+
+    ``X_train`` / ``X_test``, ``k``, the metric flags, ``all_metrics``, ``as_df``, ``rename_k``, ``min_pos_test``,
+    ``min_items_pool``, ``consider_cold_start``, ``cumulative`` and ``nthreads`` mean what they mean there, with the same
+    defaults, column names and return shapes; ``X_train=None`` is an empty train matrix with ``consider_cold_start=True``.
+    ``scores`` must have the shape of ``X_test``; it is evaluated in float32 only when it is float32, otherwise in float64; a
+    row-major array (also one with a row stride, such as a column slice of a wider matrix) is passed as it is, anything else is
+    copied once.  It is never modified, and a score at a train item is never looked at.
+
+    There is no ``break_ties_with_noise`` and no ``seed``: the reference's tie noise exists to break the ties of a factor model
+    that has not learned anything (all scores equal), and the caller of this function owns the scores -- equal scores are ordered
+    by item id, the rule ``calc_reco_metrics(..., break_ties_with_noise=False)`` uses, and for scores that ARE ``A @ B.T`` as the
+    library forms it the two calls return the same bits.  There is no ``item_biases`` either: add them to ``scores``.
+    """
+    from scipy.sparse import csr_array, issparse
+
+    requested = dict(precision=precision, trunc_precision=trunc_precision, recall=recall,
+                     average_precision=average_precision, trunc_average_precision=trunc_average_precision,
+                     ndcg=ndcg, hit=hit, rr=rr, roc_auc=roc_auc, pr_auc=pr_auc)
+    requested = {name: bool(all_metrics or flag) for name, flag in requested.items()}
+
+    _fail_if(not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
+    _fail_if(scores.ndim != 2, "'scores' must be a 2-dimensional array.")
+    _fail_if(not issparse(X_test), "'X_test' must be a sparse matrix.")
+    n_users, n_items = X_test.shape
+    _fail_if(n_users >= _INT32_MAX, "Number of test user is larger than maximum supported.")
+    _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    _fail_if(0 in (n_users, n_items), "Input matrices cannot be empty.")
+    _fail_if(X_test.data.shape[0] == 0, "'X_test' is empty.")
+    _fail_if(tuple(scores.shape) != (n_users, n_items), "'scores' and 'X_test' must have the same shape.")
+    _fail_if(scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
+    dtype = np.float32 if scores.dtype == np.float32 else np.float64
+
+    if X_train is None:
+        X_train = csr_array(X_test.shape, dtype=dtype)
+        consider_cold_start = True
+    _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
+    _fail_if(X_train.shape[1] != n_items, "'X_train' and 'X_test' should have the same number of columns.")
+    _fail_if(X_train.shape[0] < n_users, "'X_train' and 'X_test' should have the same number of rows.")
+    if X_train.shape[0] > n_users:
+        warn("'X_train' mas more rows than 'X_test'.")
+
+    _fail_if(not (requested["precision"] or requested["average_precision"] or requested["ndcg"]
+                  or requested["hit"] or requested["rr"] or requested["roc_auc"]),
+             "Must pass at least one metric to calculate.")
+
+    k, nthreads = int(k), int(nthreads)
+    min_pos_test, min_items_pool = int(min_pos_test), int(min_items_pool)
+    _fail_if(k < 1, "'k' must be positive.")
+    _fail_if(min_pos_test < 1 or min_items_pool < 1, "'min_pos_test' and 'min_items_pool' must be positive.")
+    if nthreads < 0:
+        nthreads += multiprocessing.cpu_count() + 1
+    _fail_if(nthreads <= 0, "'nthreads' must be positive (or negative: counted back from the number of CPUs).")
+    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+
+    # ---- everything above raises before the library is touched ----
+    X_train = _csr_int32(X_train)
+    if X_train.shape[0] > n_users:
+        X_train = _csr_int32(X_train[:n_users])
+    X_test = _csr_int32(X_test)
+    test_values = X_test.data if X_test.data.dtype == dtype else X_test.data.astype(dtype)
+    S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
+    c = np.ascontiguousarray
+
+    want = {short: requested[name] for name, short, _ in _METRICS}
+    outs = block = None
+    if as_df and not cumulative:
+        # (the DataFrame's storage up front, as in calc_reco_metrics: the columns ARE the output arrays of the call)
+        keys = [key for (name, _, key) in _METRICS if requested[name]]
+        block = np.empty((n_users, len(keys)), dtype=dtype, order="F")
+        cols = iter(range(len(keys)))
+        outs = [block[:, next(cols)] if requested[name] else np.empty(0, dtype=dtype) for name, _, _ in _METRICS]
+
+    arrays = _binding.calc_metrics_scores(
+        S, lds, c(X_train.indptr), c(X_train.indices), c(X_test.indptr), c(X_test.indices), c(test_values),
+        k, want, bool(cumulative), bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, outs=outs)
 
     if block is not None:
         import pandas as pd

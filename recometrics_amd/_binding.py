@@ -17,6 +17,7 @@ _lib = None
 METRIC_ORDER = ("p", "tp", "r", "ap", "tap", "ndcg", "hit", "rr", "roc", "pr")
 EXPORTS = (
     "rm_calc_metrics_f32", "rm_calc_metrics_f64", "rm_calc_metrics_dev_f32", "rm_calc_metrics_dev_f64",
+    "rm_calc_metrics_scores_f32", "rm_calc_metrics_scores_f64", "rm_calc_metrics_scores_dev_f32", "rm_calc_metrics_scores_dev_f64",
     "rm_rank_f32", "rm_rank_f64", "rm_recommend_f32", "rm_recommend_f64", "rm_recommend_dev_f32", "rm_recommend_dev_f64",
     "rm_debug_scores_f32", "rm_debug_scores_f64", "rm_has_openmp",
     "rm_last_error", "rm_device_count", "rm_set_device", "rm_set_devices", "rm_get_devices", "rm_request_interrupt",
@@ -49,11 +50,16 @@ def load():
     dev = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, vp, vp, vp, i64, i32, ci, ci] + [vp] * 10 + [ci, i32, i32, u64, vp]
     rank_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, vp, vp, i32, ci, ci, i32, i32, u64, vp, vp, vp, vp]
     reco_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32]
+    scores_sig = [vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, ci] + [vp] * 10 + [ci, i32, i32, i32]
+    scores_dev_sig = [vp, sz, i32, i32, vp, vp, i64, vp, vp, vp, i64, i32, ci] + [vp] * 10 + [ci, i32, i32, vp]
     reco_dev_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp]
     for suf in ("f32", "f64"):
         getattr(lib, "rm_recommend_" + suf).argtypes = reco_sig
         getattr(lib, "rm_recommend_dev_" + suf).argtypes = reco_dev_sig
         getattr(lib, "rm_recommend_" + suf).restype = getattr(lib, "rm_recommend_dev_" + suf).restype = ci
+        getattr(lib, "rm_calc_metrics_scores_" + suf).argtypes = scores_sig
+        getattr(lib, "rm_calc_metrics_scores_dev_" + suf).argtypes = scores_dev_sig
+        getattr(lib, "rm_calc_metrics_scores_" + suf).restype = getattr(lib, "rm_calc_metrics_scores_dev_" + suf).restype = ci
         getattr(lib, "rm_calc_metrics_" + suf).argtypes = host
         getattr(lib, "rm_calc_metrics_dev_" + suf).argtypes = dev
         getattr(lib, "rm_rank_" + suf).argtypes = rank_sig
@@ -259,6 +265,47 @@ def calc_metrics_device(dtype, A, lda, B, ldb, m, n, k, train_p, train_i, nnz_tr
     rc = fn(vp(A), lda, vp(B), ldb, m, n, k, vp(train_p), vp(train_i), nnz_train, vp(test_p), vp(test_i), vp(test_v), nnz_test,
             k_metrics, int(bool(cumulative)), int(bool(break_ties_with_noise)), *[vp(o) for o in outs],
             int(bool(consider_cold_start)), min_items_pool, min_pos_test, seed, vp(stream))
+    if rc:
+        _raise(lib, rc)
+
+
+def calc_metrics_scores(S, lds, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
+                        consider_cold_start, min_items_pool, min_pos_test, nthreads, outs=None):
+    """Host-array entry of the metrics from a score matrix (rm_calc_metrics_scores_*): `S` [m, n] row-major with leading
+    dimension `lds` (elements), the rest as `calc_metrics` without tie noise and seed.  Returns the same 10-tuple."""
+    lib = load()
+    dtype = S.dtype.type
+    m, n = S.shape
+    size_arr = m * k_metrics if cumulative else m
+    if outs is None:
+        outs = []
+        for name in METRIC_ORDER:
+            cnt = (m if name in ("roc", "pr") else size_arr) if want.get(name) else 0
+            outs.append(np.empty(cnt, dtype=dtype))
+    fn = getattr(lib, "rm_calc_metrics_scores_" + _suffix(dtype))
+    rc = fn(_p(S), lds, m, n, _p(train_p), _p(train_i), _p(test_p), _p(test_i), _p(test_v),
+            k_metrics, int(bool(cumulative)), *[_p(o) for o in outs],
+            int(bool(consider_cold_start)), min_items_pool, min_pos_test, nthreads)
+    if rc:
+        _raise(lib, rc)
+    if cumulative:
+        outs = [(o.reshape((m, k_metrics)) if o.size else o.reshape((0, 0))) if i < 8 else o for i, o in enumerate(outs)]
+    return tuple(outs)
+
+
+def calc_metrics_scores_device(dtype, S, lds, m, n, train_p, train_i, nnz_train, test_p, test_i, test_v, nnz_test,
+                               k_metrics, outs, cumulative=False, consider_cold_start=True,
+                               min_items_pool=2, min_pos_test=1, stream=0):
+    """Device-pointer entry (rm_calc_metrics_scores_dev_*): every array argument is an integer device address (0 == NULL);
+    `outs` is a sequence of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
+    lib = load()
+    fn = getattr(lib, "rm_calc_metrics_scores_dev_" + _suffix(dtype))
+
+    def vp(x):
+        return C.c_void_p(int(x)) if x else None
+    rc = fn(vp(S), lds, m, n, vp(train_p), vp(train_i), nnz_train, vp(test_p), vp(test_i), vp(test_v), nnz_test,
+            k_metrics, int(bool(cumulative)), *[vp(o) for o in outs],
+            int(bool(consider_cold_start)), min_items_pool, min_pos_test, vp(stream))
     if rc:
         _raise(lib, rc)
 

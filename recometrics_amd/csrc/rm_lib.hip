@@ -31,6 +31,7 @@
 #include "rm_launch.hpp"
 #include "rm_finalize.hpp"
 #include "rm_noise.hpp"
+#include "rm_scores.hpp"
 
 namespace {
 
@@ -304,6 +305,10 @@ template <class T> struct Call {          // one calc_metrics call; every pointe
     // recommendation lists (rm_recommend_*): no test matrix (`test_p` is null), no metric; every user with a candidate gets its ordered
     // list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
     bool reco = false;
+    // metrics from the caller's score matrix (rm_calc_metrics_scores_*): score of item i for user u = S[u * lds + i]; there are no
+    // factors (A, B null, k = 0), no tie noise.  Every evaluated user is streamed: k_score_rows copies its row of S, masked, where the
+    // sweep would have written it, k_pos_scores_given gathers the test items' scores, and the finalisation is the factor call's.
+    bool scores = false; const T *S = nullptr; size_t lds = 0;
 };
 // Layout of the ten metrics of a call (Call::out): the eight top-K metrics have `per` values per user (k_metrics when cumulative,
 // else one), the two AUCs one.  The requested metrics of one user, packed, are a RECORD (what k_noise_gather writes); those of
@@ -816,6 +821,21 @@ Geometry sweep_geometry(const Call<T> &c, const Plan &hp, int NG, bool want_auc,
     return g;
 }
 
+// The caller's scores (Call::scores): there is no sweep, so no grid and no lists -- what the other stages read of the geometry is the
+// row stride of the streamed users' score rows (whole 64-item tiles, as the two-sub-tile sweep of the same plan would leave them)
+// and ONE part of validity statistics per slot (k_score_rows writes it).
+inline Geometry scores_geometry(const Plan &hp, int n, bool want_auc)
+{
+    Geometry g{};
+    g.jmax = want_auc ? hp.jmax : 0;
+    g.n_ublocks = (hp.n_groups + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK;
+    g.nsub = 2; g.tile_items = TILE_ITEMS; g.n_waves = 8;
+    g.tiles_total = (n + TILE_ITEMS - 1) / TILE_ITEMS;
+    g.n_splits = 1; g.part_splits = 1; g.n_part = 1;
+    g.u_split = 0; g.j_shallow = -1;
+    return g;
+}
+
 // One call through the device pipeline: the stages of DESIGN.md section 1 as members, the state they hand on as fields.
 template <class T>
 struct Pipeline {
@@ -866,7 +886,7 @@ struct Pipeline {
         if (c.reco) { min_items_pool = 1; min_pos_test = 0; }          // (lists for whoever has a candidate: k_classify's `reco`)
         for (int i = 0; i < 10; i++) if (c.out[i] && !c.reco) req |= (1 << i);
         want_auc = req & (RQ_ROC | RQ_PR);
-        NG = P::supported_ng(k);
+        NG = c.scores ? 2 : P::supported_ng(k);                        // (scores: no factors, no sweep -- the value is never used)
         if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
         if (!cx.ev_valid) {
             for (int i = 0; i < EV_COUNT; i++) HIP_CHECK(hipEventCreate(&cx.ev[i]));
@@ -904,15 +924,16 @@ struct Pipeline {
         const long long stream_ld_max = ((long long)n + 191) / 192 * 192;             // row stride for either tile size (64 / 96 items)
         // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
         // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
-        want_lane = lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
-        ext_topk = (!want_lane && K > 256) || g_sw.ext_topk;
+        want_lane = !c.scores && lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
+        // (the caller's scores: the same plan -- the row every user needs is a copy of its row of S with the train items masked)
+        ext_topk = (!want_lane && K > 256) || g_sw.ext_topk || c.scores;
         long long stream_cap = 0;
         if (want_auc || ext_topk) {
             stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
             // (a pass over a subset of the users -- the exact second pass of the fp32 tie noise -- stores rows for that subset only)
             const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
             if (ext_topk) {
-                if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, "k_metrics > 256 keeps one score row (" + std::to_string(stream_ld_max * (long long)sizeof(T)) +
+                if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, std::string(c.scores ? "metrics from a score matrix keep one masked score row (" : "k_metrics > 256 keeps one score row (") + std::to_string(stream_ld_max * (long long)sizeof(T)) +
                                            " B) per user in device memory: " + std::to_string(m_rows) + " users do not fit, at most " + std::to_string(stream_cap) + " per call"};
                 ca.force_stream = 1;
             } else if (stream_cap > 0) ca.allow_stream = 1;
@@ -947,9 +968,10 @@ struct Pipeline {
         if (!cx.pinned_plan) HIP_CHECK(hipHostMalloc((void **)&cx.pinned_plan, sizeof(Plan), hipHostMallocDefault));
         // (one answer per call: a later pass -- the exact passes of the tie noise, on this or on a peer context with less free memory --
         // carries the first pass's answer; rows handed over by another pass are proof that they fit)
-        dense_ok = std::is_same<T, float>::value && (c.ext_bits ? true : c.dense_fit >= 0 ? c.dense_fit != 0 : dense_rows_fit(ws, m, n));
+        dense_ok = !c.scores && std::is_same<T, float>::value && (c.ext_bits ? true : c.dense_fit >= 0 ? c.dense_fit != 0 : dense_rows_fit(ws, m, n));
         // the positives' stream: the streamed users' chain beside the table users', and what is made per test entry beside the plan chain
-        flat_early = want_auc && !c.only_users && c.nnz_test > 0 && !g_sw.no_pos_flat;
+        // (the caller's scores: the test entries' scores are gathered by entry whatever the switch says -- there is no kernel by slot)
+        flat_early = want_auc && !c.only_users && c.nnz_test > 0 && (!g_sw.no_pos_flat || c.scores);
         int *ent_user = nullptr; unsigned char *ent_masked = nullptr;
         PosArgs<T> pf{};
         if (flat_early) {
@@ -996,8 +1018,8 @@ struct Pipeline {
             const hipStream_t aux = side.behind(SIDE_PLAN_FORK), aux2 = pos.behind(POS_PLAN_FORK);
             if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
             side.mark(SIDE_CHECKS_DONE);
-            hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
-            if (!items_known) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
+            if (!c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
+            if (!items_known && !c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
             pos.mark(POS_MAXIMA_DONE);
             // (the user of every test entry, for the positives' scores by entry: index pointers only)
             if (attempt == 0 && flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, pos.on(), m, c.test_p, ent_user, plan);
@@ -1024,11 +1046,17 @@ struct Pipeline {
                 // slots of one CU to fall free at once (measured: the read-back 0.2 ms late).  Without dense train rows k_test_masked says
                 // which test items are train items, behind the scores.
                 const hipStream_t sc = pos.fork(POS_SCORES_AFTER_COPY);
+                if (c.scores) {
+                    // (the caller's scores: which test items are train items first -- S is never read at a train item --, then the gather)
+                    hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
+                    hipLaunchKernelGGL(k_pos_scores_given<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, c.S, c.lds, (const int *)ent_user, (const unsigned char *)ent_masked);
+                } else {
                 hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pf, ent_user);
                 // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
                 if (masked_from_bits) side.await(SIDE_ROWS_FOR_POS, sc);
                 else hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
                 hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, ent_masked);
+                }
                 pos.mark(POS_SCORES_DONE);
             }
             RM_TRACE_POINT("run: plan chain + side kernels enqueued");
@@ -1057,6 +1085,7 @@ struct Pipeline {
         std::memcpy(&amax_a, &hp.amax_a, 8); std::memcpy(&amax_b, &hp.amax_b, 8);
         const double tmax = std::is_same<T, float>::value ? 3.0e38 : 1.0e308;
         check_nan = hp.nonfinite || hp.nonfinite_b || !((double)k * amax_a * 1.001 < tmax / std::max(amax_b, 1e-300));
+        if (c.scores) check_nan = false;                               // (k_score_rows looks at every candidate score whatever it is)
     }
 
     // ideal-DCG values of the users with very long test rows (k_top_values: a wavefront per such user, a chain of K dependent
@@ -1099,6 +1128,16 @@ struct Pipeline {
         fa.heavy_npos = ca.heavy_npos;
         stream_ld = (long long)g.tiles_total * g.tile_items;
         if (n_slots == 0) return;
+        if (c.scores) {
+            // the caller's scores: nothing is packed, sampled or seeded and there are no dense train rows or lists -- what is left of
+            // the preparation is the ideal-DCG values, the positives' tables and the two buffers k_score_rows fills
+            launch_top_values();
+            if (want_auc) positives();
+            stream_scores = (T *)ws.get("stream_scores", sizeof(T) * (size_t)std::max(n_stream, 1) * (size_t)stream_ld);
+            pst = (PartialStat<T> *)ws.get("pst", sizeof(PartialStat<T>) * (size_t)n_slots * g.n_part);
+            RM_TRACE_POINT("run: preparation enqueued");
+            return;
+        }
         const int n_groups = hp.n_groups, tiles_total = g.tiles_total, tile_items = g.tile_items;
 
         // ---- pack operands into the MFMA images ----
@@ -1247,6 +1286,18 @@ struct Pipeline {
         if (n_slots == 0) {
             HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
             tm[4] = 0; tm[5] = 0; tm[6] = 0; tm[7] = 0;
+            return;
+        }
+        if (c.scores) {
+            // the caller's scores: k_score_rows in the sweep's place -- a block per user copies the user's row of S into its masked
+            // score row and leaves the candidates' statistics (rm_scores.hpp); the "sweep" timing brackets this launch
+            ScoreRowArgs<T> ra{n, n_stream, stream_slot0, g.n_part, slot_user, c.train_p, c.train_i, c.S, c.lds, stream_scores, stream_ld, pst};
+            if (n_stream > 0) hipLaunchKernelGGL(k_score_rows<T>, dim3((unsigned)n_stream), dim3(SCORE_ROW_THREADS), 0, stream, ra);
+            check_launch(hipGetLastError());
+            RM_TRACE_POINT("run: score rows enqueued");
+            HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
+            tm[4] = 1; tm[5] = 1; tm[6] = n_stream; tm[7] = 0;
+            cx.timed_slots = n_slots; cx.total_slots = n_slots;
             return;
         }
         const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
@@ -1429,7 +1480,8 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
     Pipeline<T> p(c, stream, cx);
     p.begin();
     p.plan_stage();
-    p.g = sweep_geometry<T>(c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
+    p.g = c.scores ? scores_geometry(p.hp, c.n, p.want_auc)
+                   : sweep_geometry<T>(c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
     p.prep();
     p.sweep();
     if (c.reco) p.finalize_reco(); else p.finalize();
@@ -1759,6 +1811,8 @@ template <class T> struct HostCall {              // one host-pointer call (refe
     // rm_recommend_*: `tep` is a row of zeros the entry made up (host-side bookkeeping only: nothing of a test matrix reaches the
     // device), `topk_idx` / `topk_score` (optional) / `status` are the caller's idx / score / status, `pos_rank` is null
     bool reco = false;
+    // rm_calc_metrics_scores_*: the caller's score matrix instead of factors (A, B null, k = 0); its rows travel batch by batch
+    bool scores = false; const T *S = nullptr; size_t lds = 0;
 };
 
 // item factors of a sharded call: uploaded from the host by shard 0, copied device-to-device (xGMI) by the others
@@ -1807,8 +1861,18 @@ inline void print_host_trace(int n_batches, const std::vector<std::pair<const ch
 
 // Users per batch of a host call at most: ~0.4 s of device work at the rate the sweep sustains (2 n k flop per user), whole user
 // blocks, or RM_BATCH_USERS (tests: equal batches of this size); with k_metrics > 256 what one context's lane buffers or score rows hold.
-template <class T> long long batch_users_max(const Workspace &ws, int n, int k, int K)
+// The caller's scores (`scores`): a user of a batch costs its row of S in each of the two upload buffers (ws.get rounds an allocation
+// up by an eighth) and its masked row, which run() wants inside a third of what is then free: b (2.25 + 3) rows <= free memory, taken
+// with a margin for the top-K scratch; what the workspace already holds of exactly these buffers counts as free.
+template <class T> long long batch_users_max(const Workspace &ws, int n, int k, int K, bool scores = false)
 {
+    if (scores) {
+        const long long row = (((long long)n + 191) / 192 * 192) * (long long)sizeof(T);
+        long long batch = free_plus_owned(ws, {"stream_scores", "sel_hi", "sel_lo", "in_S0", "in_S1"}) / (7 * row);
+        if (g_sw.stream_budget_mb >= 0) batch = std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row);
+        if (g_sw.batch_users > 0) batch = std::min<long long>(batch, (long long)g_sw.batch_users);
+        return std::max<long long>(1, std::min<long long>(batch, 1 << 20));
+    }
     const double rate = std::is_same<T, float>::value ? 6.0e13 : 2.5e13;
     double bu = 0.4 * rate / (2.0 * (double)n * (double)k);
     if (g_sw.batch_users > 0) bu = g_sw.batch_users;
@@ -1864,6 +1928,11 @@ template <class T> struct ItemUpload {
     void run(T *dB, int device, hipStream_t up)
     {
         const int n = h.n, k = h.k;
+        if (h.scores) {                                              // no item factors: the shards' handshake alone
+            if (sh && shard == 0) { std::lock_guard<std::mutex> sl(sh->mu); sh->ready = true; sh->failed = false; sh->src = dB; sh->src_device = device; published = true; sh->cv.notify_all(); }
+            else if (sh) { reported = true; sh->copy_done(); }
+            return;
+        }
         if (!sh || shard == 0) {
             // (dense rows: ONE plain copy -- a 2-D copy of pageable memory goes through a staging buffer and a second,
             // device-side pass: 1.1 ms more for BASELINE C2's A and B)
@@ -1917,6 +1986,7 @@ template <class T> struct HostRange {
     const MetricLayout lay;                                           // (per: values per user of the eight top-K metrics)
     // stage_inputs()
     long long tr0 = 0, te0 = 0, nnz_tr = 0, nnz_te = 0;
+    T *dS[2] = {nullptr, nullptr}; const T *cur_S = nullptr;           // the caller's scores: upload buffers of the batches, the one of the batch being enqueued
     T *dB = nullptr, *dA = nullptr, *dtev = nullptr; int *dtrp = nullptr, *dtep = nullptr, *dtri = nullptr, *dtei = nullptr;
     std::vector<int> rb;                                              // rebased index pointers (only when the range does not start at 0)
     const int *trp = nullptr, *tep = nullptr;
@@ -1984,7 +2054,7 @@ template <class T> struct HostRange {
     void plan_batches()
     {
         const bool forced = g_sw.batch_users > 0;                        // tests: equal batches of this size
-        cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K), forced);
+        cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K, h.scores), forced);
         n_batches = (int)cuts.size() - 1;
         long long mb_max = 0;
         for (int bi = 0; bi < n_batches; bi++) mb_max = std::max(mb_max, cuts[bi + 1] - cuts[bi]);
@@ -1994,7 +2064,7 @@ template <class T> struct HostRange {
         // packed while batch i sweeps, and its sweep takes over the compute units as batch i's blocks drain.
         // (not with k_metrics > 256: a batch is then sized by the score rows ONE context may hold -- a third of the free memory --
         // and a second context holding as much again leaves the first one's next batch short: RM_ERR_NOMEM on the third batch)
-        const bool rows_bound = K > 256 || g_sw.ext_topk;             // (the lane buffers of k_metrics > 256 are as large)
+        const bool rows_bound = K > 256 || g_sw.ext_topk || h.scores; // (the lane buffers of k_metrics > 256 are as large; the caller's scores: see upload_users)
         if (n_batches > 1 && !rows_bound && !g_sw.one_context) {
             Ctx &pc = peer_context(cx);
             peer_lock = std::unique_lock<std::mutex>(pc.mu);
@@ -2008,6 +2078,9 @@ template <class T> struct HostRange {
             hblocks[i] = lay.rec_w ? (T *)ctxs[i]->pinned_get(sizeof(T) * lay.block_size((size_t)mb_max)) : nullptr;
         }
         two_ctx = ctxs[1] != ctxs[0];
+        // the caller's scores: the rows of a batch, dense, in one of two buffers -- batch i + 1 travels while batch i runs, and with one
+        // context batch i - 1 has been waited for by then
+        if (h.scores) for (int i = 0; i < std::min(n_batches, 2); i++) dS[i] = (T *)ws.get(i ? "in_S1" : "in_S0", sizeof(T) * (size_t)mb_max * (size_t)n);
         // fp32 tie noise over several batches: every batch runs its first pass only and flags the users the noise can touch in its
         // slice of `range_flag`; ONE exact pass over the flagged users of the whole range follows the last batch.  (Per batch, the
         // exact pass costs two waits on the host -- for the flags, for its own plan -- during which the next batch is not enqueued:
@@ -2027,6 +2100,11 @@ template <class T> struct HostRange {
     void upload_users(int bi)                                         // rows [cuts[bi], cuts[bi + 1]) into their places, on `up`
     {
         const long long b0 = cuts[bi], b1 = cuts[bi + 1];
+        if (h.scores) {
+            const T *src = h.S + ((size_t)u0 + b0) * h.lds;
+            if (h.lds == (size_t)n) HIP_CHECK(hipMemcpyAsync(dS[bi & 1], src, sizeof(T) * (size_t)(b1 - b0) * n, hipMemcpyHostToDevice, up));
+            else HIP_CHECK(hipMemcpy2DAsync(dS[bi & 1], sizeof(T) * n, src, sizeof(T) * h.lds, sizeof(T) * n, (size_t)(b1 - b0), hipMemcpyHostToDevice, up));
+        } else
         if (h.lda == (size_t)k) HIP_CHECK(hipMemcpyAsync(dA + (size_t)b0 * k, h.A + ((size_t)u0 + b0) * k, sizeof(T) * (size_t)(b1 - b0) * k, hipMemcpyHostToDevice, up));
         else HIP_CHECK(hipMemcpy2DAsync(dA + (size_t)b0 * k, sizeof(T) * k, h.A + ((size_t)u0 + b0) * h.lda, sizeof(T) * h.lda, sizeof(T) * k, (size_t)(b1 - b0),
                                         hipMemcpyHostToDevice, up));
@@ -2054,6 +2132,7 @@ template <class T> struct HostRange {
         c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
         c.K = K; c.cumulative = h.cumulative; c.noise = h.noise; c.cold = h.cold; c.min_items_pool = h.mip; c.min_pos_test = h.mpt;
         c.reco = h.reco;
+        if (h.scores) { c.scores = true; c.S = cur_S; c.lds = (size_t)n; c.A = nullptr; c.B = nullptr; }
         c.items_tag = tag; c.seed = h.seed; c.user0 = (long long)u0 + b0;
         return c;
     }
@@ -2106,6 +2185,7 @@ template <class T> struct HostRange {
         InFlight &f = fl[which];
         finish(which);                                               // (the batch two back: its context and staging are free again)
         HIP_CHECK(hipStreamWaitEvent(streams[which], cx.up_ev[bi & 1], 0));
+        cur_S = dS[bi & 1];
         Call<T> c = batch_call(b0, mb);
         f.b0 = b0; f.mb = mb;
         lay.point_at(dblocks[which], (size_t)mb, c.out);
@@ -2269,6 +2349,17 @@ void validate(const T *A, const T *B, int m, int n, int k, const int *trp, const
     if (lda < (size_t)k || ldb < (size_t)k) throw RmError{RM_ERR_INVALID, "leading dimension smaller than k"};
 }
 
+// rm_calc_metrics_scores_*: what is decided on the host before any device work (m == 0 has returned RM_OK by then)
+template <class T>
+void validate_scores(const T *S, size_t lds, int m, int n, int K, const int *trp, const int *tep, const int *tei, long long nnz_test, const void *ndcg, const void *test_v)
+{
+    if (m < 0 || n <= 0) throw RmError{RM_ERR_INVALID, "m must not be negative and n must be positive"};
+    if (!S || !trp || !tep || (!tei && nnz_test > 0)) throw RmError{RM_ERR_INVALID, "null input pointer"};
+    if (lds < (size_t)n) throw RmError{RM_ERR_INVALID, "leading dimension of the score matrix smaller than n (got " + std::to_string(lds) + " with " + std::to_string(n) + " items)"};
+    if (K < 1 || K > n) throw RmError{RM_ERR_INVALID, "k_metrics must lie in [1, n] (got " + std::to_string(K) + " with " + std::to_string(n) + " items)"};
+    if (ndcg && !test_v) throw RmError{RM_ERR_INVALID, "NDCG requested without test values"};
+}
+
 // host-pointer entry: one device (the calling thread's current one), or the devices of rm_set_devices with contiguous user
 // ranges [m g / G, m (g + 1) / G), one host thread + stream + workspace per shard, no exchange between the shards
 template <class T>
@@ -2276,7 +2367,8 @@ void run_host_once(const HostCall<T> &h)
 {
     if (h.m == 0) return;                                            // reference :428-437: no user, nothing written
     if (h.m < 0 || !h.tep) throw RmError{RM_ERR_INVALID, h.m < 0 ? "m, n, k must be positive" : "null input pointer"};
-    validate(h.A, h.B, h.m, h.n, h.k, h.trp, h.tep, h.tei, (long long)h.tep[h.m], h.K, h.lda, h.ldb);
+    if (h.scores) validate_scores(h.S, h.lds, h.m, h.n, h.K, h.trp, h.tep, h.tei, (long long)h.tep[h.m], h.outs[5], h.tev);
+    else validate(h.A, h.B, h.m, h.n, h.k, h.trp, h.tep, h.tei, (long long)h.tep[h.m], h.K, h.lda, h.ldb);
     // the index pointers say how much of the caller's index arrays is read at all: they are looked at here, on the host (2 (m + 1)
     // integers), before anything is sized or copied by them; the indices themselves are validated on the device (run())
     for (const int *p : {h.trp, h.tep}) {
@@ -2563,6 +2655,61 @@ extern "C" int rm_rank_##SUFFIX(                                                
 
 RM_HOST_ENTRY(f32, float)
 RM_HOST_ENTRY(f64, double)
+
+// metrics from the caller's score matrix: the host entry through HostRange (rows of S batch by batch), the device entry through run_dev
+#define RM_SCORES_ENTRY(SUFFIX, T)                                                                                      \
+extern "C" int rm_calc_metrics_scores_##SUFFIX(                                                                         \
+    const T *S, size_t lds, int32_t m, int32_t n,                                                                       \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,                                                           \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr,                                         \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads)     \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        if (m == 0) return;                                                                                             \
+        HostCall<T> h{nullptr, 0, nullptr, 0, m, n, 0, Xtrain_csr_p, Xtrain_csr_i, Xtest_csr_p, Xtest_csr_i, Xtest_csr, \
+                      k_metrics, cumulative != 0, false,                                                                \
+                      {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k, roc_auc, pr_auc},      \
+                      consider_cold_start != 0, min_items_pool, min_pos_test, nullptr, nullptr, nullptr, nullptr, 0};   \
+        h.nthreads = nthreads > 0 ? nthreads : 0;                                                                       \
+        h.scores = true; h.S = S; h.lds = lds;                                                                          \
+        if (m < 0 || n <= 0 || !Xtest_csr_p || !Xtrain_csr_p)                                                          \
+            validate_scores(S, lds, m, n, k_metrics, Xtrain_csr_p, Xtest_csr_p, Xtest_csr_i, 0, ndcg_at_k, Xtest_csr);  \
+        run_host<T>(h);                                                                                                 \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_calc_metrics_scores_dev_##SUFFIX(                                                                     \
+    const T *S, size_t lds, int32_t m, int32_t n,                                                                       \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,                                        \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr, int64_t nnz_test,                       \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, void *stream)         \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        if (m == 0) return;                                                                                             \
+        validate_scores(S, lds, m, n, k_metrics, Xtrain_csr_p, Xtest_csr_p, Xtest_csr_i, (long long)nnz_test, ndcg_at_k, Xtest_csr); \
+        if (nnz_train < 0 || nnz_test < 0) throw RmError{RM_ERR_INVALID, "negative length of an index array"};          \
+        if (nnz_train > 0 && !Xtrain_csr_i) throw RmError{RM_ERR_INVALID, "null train indices"};                        \
+        Call<T> c{};                                                                                                    \
+        c.scores = true; c.S = S; c.lds = lds; c.m = m; c.n = n; c.k = 0;                                               \
+        c.train_p = Xtrain_csr_p; c.train_i = Xtrain_csr_i; c.nnz_train = nnz_train;                                    \
+        c.test_p = Xtest_csr_p; c.test_i = Xtest_csr_i; c.test_v = Xtest_csr; c.nnz_test = nnz_test;                    \
+        c.K = k_metrics; c.cumulative = cumulative != 0; c.noise = false;                                               \
+        T *outs[10] = {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k, roc_auc, pr_auc};      \
+        for (int i = 0; i < 10; i++) c.out[i] = outs[i];                                                                \
+        c.cold = consider_cold_start != 0; c.min_items_pool = min_items_pool; c.min_pos_test = min_pos_test;            \
+        Ctx &cx = context(0);                                                                                           \
+        std::lock_guard<std::mutex> lk(cx.mu);                                                                          \
+        cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;                                                              \
+        c.seed = 0; c.user0 = 0;                                                                                        \
+        run_dev<T>(c, (hipStream_t)stream, cx);                                                                         \
+    });                                                                                                                 \
+}
+
+RM_SCORES_ENTRY(f32, float)
+RM_SCORES_ENTRY(f64, double)
 
 #define RM_RECOMMEND_ENTRY(SUFFIX, T)                                                                                   \
 extern "C" int rm_recommend_##SUFFIX(                                                                                   \

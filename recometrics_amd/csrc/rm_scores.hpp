@@ -1,0 +1,167 @@
+// rm_scores.hpp -- the front of a call whose scores are the CALLER'S matrix S[users x items] (rm_calc_metrics_scores_*; Call::scores).
+//
+// The factor call's sweep does three things for a streamed user: it writes the masked score row k_select_topk / k_rank_streamed
+// read (train items carry the NaN sentinel, as does the padding up to the row stride), it leaves the validity statistics of the
+// user's CANDIDATES (max, min, has-NaN: PartialStat), and -- through k_pos_scores_flat -- it scores the test entries.  Here the scores
+// exist already: k_score_rows copies a user's row of S into that layout and reduces the statistics on the way (2 n s bytes per user:
+// bound by HBM), k_pos_scores_given gathers S[user][test item].  Everything behind them is the factor call's finalisation, unchanged.
+//
+// One difference between a caller's scores and the fma chain's: the chain starts at +0 and never yields -0, and the ordered integer
+// keys of k_select_topk / k_pos_place tell the two zeros apart.  Both kernels store +0 for -0 (the contract: +0 == -0, ties by item id).
+#pragma once
+#include "rm_device.hpp"
+#include "rm_prep.hpp"
+
+namespace rm {
+
+template <class T> __device__ __forceinline__ T score_sentinel();
+template <> __device__ __forceinline__ float score_sentinel<float>() { return nan_sentinel_f(); }
+template <> __device__ __forceinline__ double score_sentinel<double>() { return __longlong_as_double(-1ll); }
+template <class T> __device__ __forceinline__ T score_canonical(T x) { return x == (T)0 ? (T)0 : x; }      // -0 -> +0; NaN stays
+
+// NaN-ignoring max / min (a NaN candidate is reported through has_nan, the sentinel never gets here)
+__device__ __forceinline__ float stat_max(float a, float b) { return __builtin_fmaxf(a, b); }
+__device__ __forceinline__ float stat_min(float a, float b) { return __builtin_fminf(a, b); }
+__device__ __forceinline__ double stat_max(double a, double b) { return __builtin_fmax(a, b); }
+__device__ __forceinline__ double stat_min(double a, double b) { return __builtin_fmin(a, b); }
+
+// scores of the test entries, by entry (the place of k_pos_scores_flat + k_pos_apply_masked): a test item that is a train item of
+// its user scores +inf -- S is not read there -- everything else S[user][item] as given
+template <class T>
+__global__ __launch_bounds__(256) void k_pos_scores_given(PosArgs<T> a, const T *S, size_t lds, const int *ent_user, const unsigned char *ent_masked)
+{
+    if (a.plan->csr_bad & (CSR_BAD_INDPTR | CSR_BAD_INDEX)) return;       // (the test items index the rows of S)
+    const long long e = (long long)a.test_p[0] + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)a.test_p[a.m]) return;
+    const int u = ent_user[e];
+    const int f = a.flags[u];
+    if (!(f & UF_ACTIVE) || (f & UF_ONLY_NDCG)) return;
+    const int item = a.test_i[e];
+    const T s = ent_masked[e] ? (T)__int_as_float(0x7f800000) : score_canonical<T>(S[(size_t)u * lds + (size_t)item]);
+    a.pos_tmp[e] = s;
+    if (sizeof(T) == 4 && a.pos_key) a.pos_key[e] = ((unsigned long long)ord_key((float)s) << 32) | (unsigned)~item;
+}
+
+// ---- the masked score rows and the candidates' statistics ----------------------------------------------------------------------
+// A block per streamed user (row).  The row of S is read in aligned 16-byte pieces, with element loads in front of the first aligned
+// address and behind the last whole piece (`lds` and the caller's pointer are arbitrary: a row starts wherever it starts); the
+// stored row starts 16-byte aligned, so a piece lands at the alignment the head leaves it -- element-aligned vector stores.
+// Train items: the row's sorted train items are merged in by a CURSOR over pieces of SCORE_CHUNK items -- per piece the block marks
+// the train items that fall into it in an LDS bitmap (each thread takes entries cursor + tid, + 256, ... until one lies beyond the
+// piece) and the cursor moves by how many were marked; a score then costs a bit test, not a search.  BASELINE C2's 26,744 items are
+// one piece.
+constexpr int SCORE_ROW_THREADS = 256;
+constexpr int SCORE_CHUNK = 32768;                 // items per piece: a 4 KiB bitmap
+constexpr int SCORE_UNROLL = 4;                    // 16-byte loads in flight per thread
+
+template <class T> struct ScoreRowArgs {
+    int n, n_rows, stream_slot0, n_part;
+    const int *slot_user, *train_p, *train_i;
+    const T *S; size_t lds;
+    T *rows; long long row_ld;                     // [n_rows][row_ld], row_ld >= n, rows 16-byte aligned
+    PartialStat<T> *pst;                           // [n_slots][n_part]: part 0 is written
+};
+
+template <class T>
+__global__ __launch_bounds__(SCORE_ROW_THREADS) void k_score_rows(ScoreRowArgs<T> a)
+{
+    constexpr int VE = 16 / (int)sizeof(T);                                    // scores per 16-byte piece
+    typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
+    typedef T VTU __attribute__((ext_vector_type(16 / sizeof(T)), aligned(sizeof(T))));
+    __shared__ unsigned bitmap[SCORE_CHUNK / 32 + 2];
+    __shared__ int sh_taken;
+    __shared__ T sh_max[SCORE_ROW_THREADS / WAVE], sh_min[SCORE_ROW_THREADS / WAVE];
+    __shared__ int sh_nan[SCORE_ROW_THREADS / WAVE];
+    const int d = blockIdx.x, tid = threadIdx.x;
+    if (d >= a.n_rows) return;
+    const int slot = a.stream_slot0 + d;
+    const int u = a.slot_user[slot];
+    const int n = a.n;
+    const T *src = a.S + (size_t)u * a.lds;
+    T *dst = a.rows + (size_t)d * (size_t)a.row_ld;
+    int cursor = a.train_p[u];
+    const int tr_end = a.train_p[u + 1];
+    // scores in front of the first 16-byte boundary of the source row
+    const int mis = (int)(((size_t)src) & 15);
+    // (a pointer that is not even a multiple of the score's size never reaches a 16-byte boundary: element loads throughout)
+    const int head = (mis % (int)sizeof(T)) ? n : min(n, mis ? (16 - mis) / (int)sizeof(T) : 0);
+    T vmax = -(T)INFINITY, vmin = (T)INFINITY; bool has_nan = false;
+    const T sentinel = score_sentinel<T>();
+    auto one = [&](T x, bool masked) -> T {
+        if (masked) return sentinel;
+        x = score_canonical<T>(x);
+        has_nan |= x != x;
+        vmax = stat_max(vmax, x); vmin = stat_min(vmin, x);
+        return x;
+    };
+    for (int c0 = 0; c0 < n; c0 += SCORE_CHUNK) {
+        const int c1 = min(n, c0 + SCORE_CHUNK);
+        // ---- the train items of [c0, c1) into the bitmap; the cursor moves behind them ----
+        for (int i = tid; i < SCORE_CHUNK / 32 + 2; i += SCORE_ROW_THREADS) bitmap[i] = 0u;
+        if (tid == 0) sh_taken = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int e = cursor + tid; e < tr_end; e += SCORE_ROW_THREADS) {
+            const int it = a.train_i[e];
+            if (it >= c1) break;
+            const unsigned rel = (unsigned)(it - c0);
+            if (rel < (unsigned)SCORE_CHUNK) atomicOr(&bitmap[rel >> 5], 1u << (rel & 31));
+            mine++;
+        }
+        if (mine) atomicAdd(&sh_taken, mine);
+        __syncthreads();
+        cursor += sh_taken;
+        auto masked_bits = [&](int i) -> unsigned {                           // bits of items i, i + 1, ... (i in [c0, c1))
+            const unsigned rel = (unsigned)(i - c0);
+            const unsigned long long w = (unsigned long long)bitmap[rel >> 5] | ((unsigned long long)bitmap[(rel >> 5) + 1] << 32);
+            return (unsigned)(w >> (rel & 31));
+        };
+        // ---- this piece of the row: [lo, hi) element by element around the aligned middle [v0, v1) ----
+        const int lo = c0, hi = c1;
+        int v0 = lo <= head ? head : head + (lo - head + VE - 1) / VE * VE;   // first aligned piece at or behind lo
+        v0 = min(v0, hi);
+        const int v1 = v0 + (hi - v0) / VE * VE;
+        for (int i = lo + tid; i < v0; i += SCORE_ROW_THREADS) dst[i] = one(src[i], masked_bits(i) & 1u);
+        for (int i = v1 + tid; i < hi; i += SCORE_ROW_THREADS) dst[i] = one(src[i], masked_bits(i) & 1u);
+        const int nvec = (v1 - v0) / VE;
+        for (int vb = 0; vb < nvec; vb += SCORE_ROW_THREADS * SCORE_UNROLL) {
+            VT x[SCORE_UNROLL];
+            #pragma unroll
+            for (int q = 0; q < SCORE_UNROLL; q++) {
+                const int v = vb + q * SCORE_ROW_THREADS + tid;
+                if (v < nvec) x[q] = *(const VT *)(src + v0 + v * VE);
+            }
+            #pragma unroll
+            for (int q = 0; q < SCORE_UNROLL; q++) {
+                const int v = vb + q * SCORE_ROW_THREADS + tid;
+                if (v >= nvec) continue;
+                const int i = v0 + v * VE;
+                const unsigned mb = masked_bits(i);
+                VT y;
+                #pragma unroll
+                for (int j = 0; j < VE; j++) y[j] = one(x[q][j], (mb >> j) & 1u);
+                *(VTU *)(dst + i) = y;
+            }
+        }
+        __syncthreads();                                                      // (the bitmap is cleared for the next piece)
+    }
+    // the padding up to the row stride: masked, like the items beyond n of the sweep's last tile
+    for (long long i = (long long)n + tid; i < a.row_ld; i += SCORE_ROW_THREADS) dst[i] = sentinel;
+    // ---- the block's statistics -> part 0 of the slot ----
+    int hn = has_nan ? 1 : 0;
+    #pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        vmax = stat_max(vmax, __shfl_xor(vmax, s)); vmin = stat_min(vmin, __shfl_xor(vmin, s)); hn |= __shfl_xor(hn, s);
+    }
+    const int wv = tid >> 6;
+    if ((tid & 63) == 0) { sh_max[wv] = vmax; sh_min[wv] = vmin; sh_nan[wv] = hn; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < SCORE_ROW_THREADS / WAVE; w++) { vmax = stat_max(vmax, sh_max[w]); vmin = stat_min(vmin, sh_min[w]); hn |= sh_nan[w]; }
+        PartialStat<T> ps;
+        ps.vmax = vmax; ps.vmin = vmin; ps.rocsum = 0; ps.has_nan = hn; ps.pad = 0;
+        a.pst[(size_t)slot * a.n_part] = ps;
+    }
+}
+
+} // namespace rm
