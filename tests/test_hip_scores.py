@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from _parity import NT, TOL, hip_calc
+from _requests import planted_problem, replace_rows
 from _util import assert_close, assert_same_bits
 
 pytestmark = pytest.mark.gpu
@@ -72,59 +73,7 @@ def assert_like_parity(got, want, what):
 
 
 # ---- problems ---------------------------------------------------------------------------------------------------------------------
-def replace_rows(pr, n, rows, dtype):
-    """the problem with the users of `rows` = {user: (train items, test items, test values or None)} replaced"""
-    trp, tri = pr["train"]
-    tep, tei, tev = pr["test"]
-    m = trp.shape[0] - 1
-    TR, TE, TV = [], [], []
-    for u in range(m):
-        if u in rows:
-            a, b, v = rows[u]
-            a, b = np.asarray(a, np.int32), np.asarray(b, np.int32)
-            v = np.arange(1, b.shape[0] + 1, dtype=dtype) if v is None else np.asarray(v, dtype)
-        else:
-            a, b, v = tri[trp[u]:trp[u + 1]], tei[tep[u]:tep[u + 1]], tev[tep[u]:tep[u + 1]]
-        TR.append(a); TE.append(b); TV.append(v)
-    p = np.zeros(m + 1, np.int64); q = np.zeros(m + 1, np.int64)
-    np.cumsum([x.shape[0] for x in TR], out=p[1:]); np.cumsum([x.shape[0] for x in TE], out=q[1:])
-    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
-    return dict(A=pr["A"], B=pr["B"], train=(p.astype(np.int32), cat(TR, np.int32)), test=(q.astype(np.int32), cat(TE, np.int32), cat(TV, dtype)))
-
-
-@functools.lru_cache(maxsize=64)
-def planted_problem(m, n, kf, dtype, seed, K):
-    """i.i.d. factors and make_interactions rows; from 33 users on, the edge users planted in one problem: no test item; 1, 63, 64,
-    1,023 and 1,500 test items (as many as half of the catalogue allows); a train row that is the whole catalogue; one candidate;
-    C = K - 1, K, K + 1 candidates; test items that are train items; negative and zero test values"""
-    from recometrics_amd.synth import make_problem
-    pr = make_problem(m, n, kf, dtype, mean_c=max(2, min(40, n // 8)), seed=seed)
-    if m < 33 or n < 16:
-        return pr
-    rng = np.random.default_rng(seed + 1)
-    items = np.arange(n, dtype=np.int32)
-    rows = {}
-
-    def split(n_test, n_train=None):
-        pick = rng.permutation(n)
-        n_test = max(1, min(n_test, n // 2))
-        n_train = min(40, n // 8) if n_train is None else n_train
-        return np.sort(pick[n_test:n_test + n_train]), np.sort(pick[:n_test]), None
-    rows[0] = (split(1)[0], np.zeros(0, np.int32), None)
-    for u, cnt in zip((1, 2, 3, 4, 5), (1, 63, 64, 1023, 1500)):
-        rows[u] = split(cnt)
-    rows[6] = (items, np.sort(rng.permutation(n)[:3]), None)                     # the train row is the whole catalogue
-    for u, C in zip((7, 8, 9, 10), (1, K - 1, K, K + 1)):
-        C = max(1, min(C, n))
-        cand = np.sort(rng.permutation(n)[:C])
-        rows[u] = (np.setdiff1d(items, cand).astype(np.int32), cand[:max(1, C // 2)], None)
-    tr, te, _ = split(9)
-    rows[11] = (np.sort(np.concatenate([tr, te[:4]])), te, None)                 # four test items are train items too
-    tr, te, _ = split(6)
-    rows[12] = (tr, te, np.array([-3.0, 0.0, 2.0, 0.0, -1.0, 5.0][:te.shape[0]]))
-    tr, te, _ = split(5)
-    rows[13] = (tr, te, np.zeros(te.shape[0]))
-    return replace_rows(pr, n, rows, dtype)
+# (replace_rows and planted_problem live in tests/_requests.py, which plants two more users into the same problem)
 
 
 def run_a_and_b(hip, oracle, pr, K, dtype, pad, what, cumulative=(False, True), **kw):
