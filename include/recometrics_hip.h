@@ -213,6 +213,41 @@ int rm_recommend_dev_f64(
     const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,
     int32_t *idx, double *score, int32_t *status, void *stream);
 
+/* The same lists from the CALLER'S score matrix: rm_recommend_* with the scores of rm_calc_metrics_scores_*.
+ * Score of item i for user u = S[u * lds + i] as given (lds >= n, rows at any alignment; S is never modified).  Candidates = the
+ * items outside row u of the exclusion matrix (validated as everywhere else: unsorted rows are sorted in a copy, bad index pointers /
+ * indices are RM_ERR_INVALID naming the row; Xexcl_csr_p == NULL excludes nothing).  Order = score descending, then item id
+ * ascending; -0 and +0 are equal scores and come out as +0; no tie noise.  idx / score (may be NULL) / status as rm_recommend_*:
+ *   0  the first min(k_top, C) places hold the list, the rest -1 / NaN;   1  the row excludes the whole catalogue;
+ *   2  some CANDIDATE score is NaN or +-Inf: -1 / NaN everywhere.  A score at an excluded item is never looked at.
+ * RM_ERR_INVALID, decided on the host before any device work: S == NULL, lds < n, n <= 0, m < 0, k_top outside [1, n], idx or
+ * status NULL, nnz_excl < 0.  m == 0 returns RM_OK and writes nothing.  Where S is the library's own k-ordered fma chain of some
+ * A, B (rm_debug_scores_*), ids, scores and status are the bits rm_recommend_* writes.
+ * rm_recommend_scores_f32/f64: HOST pointers, through the machinery of rm_calc_metrics_scores_* (user batches with two upload
+ * buffers, rm_set_devices shards, SIGINT -> RM_ERR_INTERRUPTED with the finished batches kept, `nthreads` for the fall-back sort);
+ * results depend neither on the device list nor on the batch size.  rm_recommend_scores_dev_f32/f64: DEVICE pointers on the
+ * current device, asynchronous on `stream` like rm_recommend_dev_*.  Up to k_top = 1024 one kernel reads each row once and
+ * selects the list on the way: NO score row is kept per user (the workspace is O(m) words plus the plan), so the call does not
+ * answer RM_ERR_NOMEM for an m at which rm_calc_metrics_scores_dev_* does.  Beyond 1024 the masked rows are stored as there and the
+ * call may answer RM_ERR_NOMEM with that call's message.  rm_get_timings covers all four: out[1] brackets the row kernel, out[6]
+ * is its blocks. */
+int rm_recommend_scores_f32(
+    const float *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,
+    int32_t *idx, float *score, int32_t *status, int32_t nthreads);
+int rm_recommend_scores_f64(
+    const double *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,
+    int32_t *idx, double *score, int32_t *status, int32_t nthreads);
+int rm_recommend_scores_dev_f32(
+    const float *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,
+    int32_t *idx, float *score, int32_t *status, void *stream);
+int rm_recommend_scores_dev_f64(
+    const double *S, size_t lds, int32_t m, int32_t n,
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,
+    int32_t *idx, double *score, int32_t *status, void *stream);
+
 /* Dense score matrix out[m x n] (host) computed by the sweep's own MFMA contraction -- test hook that pins the
  * "bit-identical to the k-ordered fma chain" claim (reference src/recometrics.hpp:99-112). */
 int rm_debug_scores_f32(const float *A, size_t lda, const float *B, size_t ldb,

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _binding
 
-__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_scores", "recommend_topk", "split_reco_train_test"]
+__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_scores", "recommend_topk", "recommend_topk_from_scores", "split_reco_train_test"]
 __version__ = "0.1.0"
 
 # (keyword of calc_reco_metrics, name in the C-ABI order, key of the result dict) -- reference __init__.py:590-613
@@ -457,3 +457,54 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
     A, lda = _row_major_with_ld(A.astype(dtype, copy=False))
     B, ldb = _row_major_with_ld(B.astype(dtype, copy=False))
     return _binding.recommend(A, lda, B, ldb, excl_p, excl_i, k, bool(return_scores))
+
+
+def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_scores=True):
+    """The ``k`` best items for every user of ANY model: :func:`recommend_topk` with the ``scores`` argument of
+    :func:`calc_reco_metrics_from_scores` -- the lists those metrics are computed over.  The reference has no such call.
+
+    ``scores``: 2-d numeric NumPy array ``[users, items]``, evaluated in float32 only when it is float32, otherwise in float64; a
+    row-major array (also one with a row stride, such as a column slice of a wider matrix) is passed as it is, anything else is
+    copied once.  It is never modified, and a score at an excluded item is never looked at.  ``X_train``: optional sparse
+    user-item matrix of the items to leave out per user (any SciPy format, int32 or int64 indices; never modified), ``None`` leaves
+    nothing out.  ``users``: optional integer array -- lists for these rows of ``scores`` / ``X_train`` only, in this order (the
+    rows are gathered once).  Order: score descending, then item id ascending; ``-0.0`` and ``+0.0`` are equal and come out as
+    ``+0.0``.
+
+    Returns ``(ids, scores, status)`` shaped and coded as :func:`recommend_topk` returns them.
+    """
+    _fail_if(not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
+    _fail_if(scores.ndim != 2, "'scores' must be a 2-dimensional array.")
+    _fail_if(scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
+    n_users, n_items = scores.shape
+    _fail_if(n_items == 0, "Input matrices cannot be empty.")
+    _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
+    _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    k = int(k)
+    _fail_if(k < 1, "'k' must be positive.")
+    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+    if X_train is not None:
+        from scipy.sparse import issparse
+        _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
+        _fail_if(tuple(X_train.shape) != (n_users, n_items), "'scores' and 'X_train' must have the same shape.")
+    if users is not None:
+        users = np.asarray(users)
+        _fail_if(users.ndim != 1 or (users.size and users.dtype.kind not in "iu"), "'users' must be a 1-d integer array.")
+        users = users.astype(np.int64, copy=False)
+        _fail_if(users.size and (users.min() < 0 or users.max() >= n_users), "'users' has entries outside the rows of 'scores'.")
+    dtype = np.float32 if scores.dtype == np.float32 else np.float64
+
+    # ---- everything above raises before the library is touched ----
+    if users is not None:
+        scores = scores[users]                               # (the one gather: a new row-major array)
+        if X_train is not None:
+            X_train = _csr_int32(X_train)[users]
+    excl_p = excl_i = None
+    if X_train is not None:
+        X_train = _csr_int32(X_train)
+        excl_p, excl_i = np.ascontiguousarray(X_train.indptr), np.ascontiguousarray(X_train.indices)
+    m = scores.shape[0]
+    if m == 0:
+        return (np.empty((0, k), np.int32), np.empty((0, k), dtype) if return_scores else None, np.empty(0, np.int32))
+    S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
+    return _binding.recommend_scores(S, lds, excl_p, excl_i, k, bool(return_scores))

@@ -19,6 +19,7 @@ EXPORTS = (
     "rm_calc_metrics_f32", "rm_calc_metrics_f64", "rm_calc_metrics_dev_f32", "rm_calc_metrics_dev_f64",
     "rm_calc_metrics_scores_f32", "rm_calc_metrics_scores_f64", "rm_calc_metrics_scores_dev_f32", "rm_calc_metrics_scores_dev_f64",
     "rm_rank_f32", "rm_rank_f64", "rm_recommend_f32", "rm_recommend_f64", "rm_recommend_dev_f32", "rm_recommend_dev_f64",
+    "rm_recommend_scores_f32", "rm_recommend_scores_f64", "rm_recommend_scores_dev_f32", "rm_recommend_scores_dev_f64",
     "rm_debug_scores_f32", "rm_debug_scores_f64", "rm_has_openmp",
     "rm_last_error", "rm_device_count", "rm_set_device", "rm_set_devices", "rm_get_devices", "rm_request_interrupt",
     "rm_get_timings", "rm_release_workspace", "rm_debug_reload_switches",
@@ -53,7 +54,12 @@ def load():
     scores_sig = [vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, ci] + [vp] * 10 + [ci, i32, i32, i32]
     scores_dev_sig = [vp, sz, i32, i32, vp, vp, i64, vp, vp, vp, i64, i32, ci] + [vp] * 10 + [ci, i32, i32, vp]
     reco_dev_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp]
+    reco_scores_sig = [vp, sz, i32, i32, vp, vp, i32, vp, vp, vp, i32]
+    reco_scores_dev_sig = [vp, sz, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp]
     for suf in ("f32", "f64"):
+        getattr(lib, "rm_recommend_scores_" + suf).argtypes = reco_scores_sig
+        getattr(lib, "rm_recommend_scores_dev_" + suf).argtypes = reco_scores_dev_sig
+        getattr(lib, "rm_recommend_scores_" + suf).restype = getattr(lib, "rm_recommend_scores_dev_" + suf).restype = ci
         getattr(lib, "rm_recommend_" + suf).argtypes = reco_sig
         getattr(lib, "rm_recommend_dev_" + suf).argtypes = reco_dev_sig
         getattr(lib, "rm_recommend_" + suf).restype = getattr(lib, "rm_recommend_dev_" + suf).restype = ci
@@ -359,6 +365,36 @@ def recommend_device(dtype, A, lda, B, ldb, m, n, k, excl_p, excl_i, nnz_excl, k
     def vp(x):
         return C.c_void_p(int(x)) if x else None
     rc = fn(vp(A), lda, vp(B), ldb, m, n, k, vp(excl_p), vp(excl_i), nnz_excl, k_top, vp(idx), vp(score), vp(status), vp(stream))
+    if rc:
+        _raise(lib, rc)
+
+
+def recommend_scores(S, lds, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
+    """Host-array entry of the recommendation lists from a score matrix (rm_recommend_scores_*): `S` [m, n] row-major with leading
+    dimension `lds` (elements), the rest and the return value as `recommend`."""
+    lib = load()
+    dtype = S.dtype.type
+    m, n = S.shape
+    idx = np.empty((m, k_top), dtype=np.int32)
+    sc = np.empty((m, k_top), dtype=dtype) if return_scores else None
+    st = np.empty(m, dtype=np.int32)
+    fn = getattr(lib, "rm_recommend_scores_" + _suffix(dtype))
+    rc = fn(_p(S), lds, m, n, None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p), _p(excl_i), k_top,
+            _p(idx), _p(sc), _p(st), int(nthreads))
+    if rc:
+        _raise(lib, rc)
+    return idx, sc, st
+
+
+def recommend_scores_device(dtype, S, lds, m, n, excl_p, excl_i, nnz_excl, k_top, idx, score, status, stream=0):
+    """Device-pointer entry (rm_recommend_scores_dev_*): every array argument is an integer device address (0 == NULL: `excl_p` =
+    nothing is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
+    lib = load()
+    fn = getattr(lib, "rm_recommend_scores_dev_" + _suffix(dtype))
+
+    def vp(x):
+        return C.c_void_p(int(x)) if x else None
+    rc = fn(vp(S), lds, m, n, vp(excl_p), vp(excl_i), nnz_excl, k_top, vp(idx), vp(score), vp(status), vp(stream))
     if rc:
         _raise(lib, rc)
 

@@ -32,6 +32,7 @@
 #include "rm_finalize.hpp"
 #include "rm_noise.hpp"
 #include "rm_scores.hpp"
+#include "rm_rowtopk.hpp"
 
 namespace {
 
@@ -54,7 +55,7 @@ struct RmError { int code; std::string msg; };
 // tests/test_switches_cpu.py compares this table with that list); nothing here turns a feature of the call off.
 struct Switches {
     bool no_train_bits, no_spec, no_side, ext_topk, no_test_mask, hbm_lists, nsub2, no_pending, no_pos_beside, no_seed, rank_generic,
-         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat;
+         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk;
     long long free_mb, stream_budget_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed;      // -1 = not set
     double batch_users;                                                        // 0 = not set
     std::string splits;
@@ -70,6 +71,7 @@ struct Switches {
         no_defer_auc = on("RM_DEBUG_NO_DEFER_AUC"); noise_sequential = on("RM_DEBUG_NOISE_SEQUENTIAL");
         one_context = on("RM_DEBUG_ONE_CONTEXT"); noise_per_batch = on("RM_DEBUG_NOISE_PER_BATCH"); host_trace = on("RM_HOST_TRACE");
         no_pos_flat = on("RM_DEBUG_NO_POS_FLAT");
+        no_row_topk = on("RM_DEBUG_NO_ROW_TOPK");            // lists from a score matrix: stored rows + k_select_topk at every k_top (A/B timing, tests)
         free_mb = num("RM_DEBUG_FREE_MB"); stream_budget_mb = num("RM_STREAM_BUDGET_MB");
         noise_budget_mb = num("RM_NOISE_BUDGET_MB");
         lane_min_k = num("RM_DEBUG_LANE_MIN_K");                // the smallest k_metrics that takes the lane buffers instead of LDS / HBM lists (A/B timing)
@@ -854,6 +856,7 @@ struct Pipeline {
     long long *grow = nullptr; double *log2tab = nullptr;
     ClassifyArgs ca{};
     bool want_lane = false, ext_topk = false, items_known = false, dense_ok = false;
+    bool row_topk = false;                  // lists from the caller's scores, selected while the row is read (k_topk_rows): no score row is stored
     bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
     Plan hp{};
     int n_slots = 0, n_stream = 0, stream_slot0 = 0; bool check_nan = false;
@@ -925,15 +928,18 @@ struct Pipeline {
         // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
         // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
         want_lane = !c.scores && lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
-        // (the caller's scores: the same plan -- the row every user needs is a copy of its row of S with the train items masked)
+        // (the caller's scores: the same plan -- the row every user needs is a copy of its row of S with the train items masked;
+        // lists of up to ROW_TOPK_MAX_K items from them need no stored row at all: k_topk_rows, rm_rowtopk.hpp)
+        row_topk = c.reco && c.scores && K <= ROW_TOPK_MAX_K && !g_sw.no_row_topk;
         ext_topk = (!want_lane && K > 256) || g_sw.ext_topk || c.scores;
+        if (row_topk) ext_topk = false;
         long long stream_cap = 0;
         if (want_auc || ext_topk) {
             stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
             // (a pass over a subset of the users -- the exact second pass of the fp32 tie noise -- stores rows for that subset only)
             const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
             if (ext_topk) {
-                if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, std::string(c.scores ? "metrics from a score matrix keep one masked score row (" : "k_metrics > 256 keeps one score row (") + std::to_string(stream_ld_max * (long long)sizeof(T)) +
+                if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, std::string(c.scores && c.reco ? "lists of more than 1024 items from a score matrix keep one masked score row (" : c.scores ? "metrics from a score matrix keep one masked score row (" : "k_metrics > 256 keeps one score row (") + std::to_string(stream_ld_max * (long long)sizeof(T)) +
                                            " B) per user in device memory: " + std::to_string(m_rows) + " users do not fit, at most " + std::to_string(stream_cap) + " per call"};
                 ca.force_stream = 1;
             } else if (stream_cap > 0) ca.allow_stream = 1;
@@ -1337,6 +1343,23 @@ struct Pipeline {
         cx.total_slots = n_slots;
     }
 
+    // ---- lists from the caller's scores (row_topk): k_topk_rows in the place of preparation, sweep and finalisation -- a block per
+    // user of the call reads the user's row of S once and writes its list and status; the "sweep" timing brackets this launch ----
+    void topk_rows()
+    {
+        HIP_CHECK(hipEventRecord(cx.ev[EV_PREP_END], stream));
+        RowTopkArgs<T> ra{n, K, c.train_p, c.train_i, c.S, c.lds, c.topk_idx, c.topk_score, c.status};
+        hipLaunchKernelGGL(k_topk_rows<T>, dim3((unsigned)m), dim3(SCORE_ROW_THREADS), 0, stream, ra);
+        HIP_CHECK(hipGetLastError());
+        RM_TRACE_POINT("run: row top-K enqueued");
+        HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
+        double *tm = cx.timings;
+        hipFuncAttributes at{};
+        HIP_CHECK(hipFuncGetAttributes(&at, (const void *)k_topk_rows<T>));
+        tm[4] = 1; tm[5] = 1; tm[6] = m; tm[7] = (double)at.sharedSizeBytes;
+        cx.timed_slots = hp.n_slots; cx.total_slots = hp.n_slots;
+    }
+
     int stream_parts() const { return (int)cdiv(n, STREAM_RANK_THREADS * STREAM_RANK_ITEMS); }
     void rank_streamed_rows(int r0, int r1, hipStream_t st)
     {
@@ -1480,6 +1503,7 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
     Pipeline<T> p(c, stream, cx);
     p.begin();
     p.plan_stage();
+    if (p.row_topk) { p.topk_rows(); p.export_ranks(); return; }
     p.g = c.scores ? scores_geometry(p.hp, c.n, p.want_auc)
                    : sweep_geometry<T>(c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
     p.prep();
@@ -2583,6 +2607,57 @@ void recommend_dev(const T *A, size_t lda, const T *B, size_t ldb, int m, int n,
     run_dev<T>(c, stream, cx);
 }
 
+// ---- recommendation lists from the caller's score matrix: rm_recommend_scores_* ---------------------------------------------
+// rm_recommend_* with the scores of rm_calc_metrics_scores_*: Call::reco && Call::scores.  Up to ROW_TOPK_MAX_K items per list the
+// row kernel of rm_rowtopk.hpp selects them while it reads the row; beyond (or under RM_DEBUG_NO_ROW_TOPK) k_score_rows ->
+// k_select_topk -> k_finalize_reco.  The host entry is HostRange's (rows of S batch by batch, shards, interrupts).
+inline void validate_recommend_scores(const void *S, size_t lds, int m, int n, int K, const void *idx, const void *status)
+{
+    if (m < 0 || n <= 0) throw RmError{RM_ERR_INVALID, "m must not be negative and n must be positive"};
+    if (!S) throw RmError{RM_ERR_INVALID, "null input pointer"};
+    if (!idx || !status) throw RmError{RM_ERR_INVALID, "null output pointer"};
+    if (lds < (size_t)n) throw RmError{RM_ERR_INVALID, "leading dimension of the score matrix smaller than n (got " + std::to_string(lds) + " with " + std::to_string(n) + " items)"};
+    if (K < 1 || K > n) throw RmError{RM_ERR_INVALID, "k_top must lie in [1, n] (got " + std::to_string(K) + " with " + std::to_string(n) + " items)"};
+}
+template <class T>
+void recommend_scores_host(const T *S, size_t lds, int m, int n, const int *xp, const int *xi, int K, int *idx, T *score, int *status, int nthreads)
+{
+    if (m == 0) return;
+    validate_recommend_scores(S, lds, m, n, K, idx, status);
+    const std::vector<int> zeros((size_t)m + 1, 0);
+    HostCall<T> h{nullptr, 0, nullptr, 0, m, n, 0, xp ? xp : zeros.data(), xp ? xi : nullptr, zeros.data(), nullptr, nullptr, K, false, false,
+                  {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, true, 1, 0,
+                  idx, score, nullptr, status, 0};
+    h.nthreads = nthreads > 0 ? nthreads : 0;
+    h.reco = true; h.scores = true; h.S = S; h.lds = lds;
+    run_host<T>(h);
+}
+template <class T>
+void recommend_scores_dev(const T *S, size_t lds, int m, int n, const int *xp, const int *xi, long long nnz, int K,
+                          int *idx, T *score, int *status, hipStream_t stream)
+{
+    if (m == 0) return;
+    validate_recommend_scores(S, lds, m, n, K, idx, status);
+    if (nnz < 0) throw RmError{RM_ERR_INVALID, "negative length of the index array"};
+    if (xp && nnz > 0 && !xi) throw RmError{RM_ERR_INVALID, "null input pointer"};
+    Call<T> c{};
+    c.scores = true; c.S = S; c.lds = lds; c.m = m; c.n = n; c.k = 0;
+    c.train_p = xp; c.train_i = xi; c.nnz_train = xp ? nnz : 0;
+    c.K = K; c.cold = true; c.min_items_pool = 1; c.min_pos_test = 0;
+    c.topk_idx = idx; c.topk_score = score; c.status = status; c.reco = true;
+    c.seed = 0; c.user0 = 0;
+    Ctx &cx = context(0);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
+    if (!xp) {
+        int *z = (int *)cx.ws.get("reco_zero_p", sizeof(int) * ((size_t)m + 1));
+        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // (an earlier call on another stream may still read it)
+        HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)m + 1), stream));
+        c.train_p = z; c.train_i = z;
+    }
+    run_dev<T>(c, stream, cx);
+}
+
 } // namespace
 
 // =====================================================================================================================
@@ -2730,6 +2805,26 @@ extern "C" int rm_recommend_dev_##SUFFIX(                                       
 
 RM_RECOMMEND_ENTRY(f32, float)
 RM_RECOMMEND_ENTRY(f64, double)
+
+#define RM_RECOMMEND_SCORES_ENTRY(SUFFIX, T)                                                                            \
+extern "C" int rm_recommend_scores_##SUFFIX(                                                                            \
+    const T *S, size_t lds, int32_t m, int32_t n,                                                                       \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
+    int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
+{                                                                                                                       \
+    return guarded([&] { recommend_scores_host<T>(S, lds, m, n, Xexcl_csr_p, Xexcl_csr_i, k_top, idx, score, status, nthreads); }); \
+}                                                                                                                       \
+extern "C" int rm_recommend_scores_dev_##SUFFIX(                                                                        \
+    const T *S, size_t lds, int32_t m, int32_t n,                                                                       \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
+    int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
+{                                                                                                                       \
+    return guarded([&] { recommend_scores_dev<T>(S, lds, m, n, Xexcl_csr_p, Xexcl_csr_i, (long long)nnz_excl, k_top, idx, score, status, \
+                                                 (hipStream_t)stream); });                                              \
+}
+
+RM_RECOMMEND_SCORES_ENTRY(f32, float)
+RM_RECOMMEND_SCORES_ENTRY(f64, double)
 
 extern "C" int rm_debug_scores_f32(const float *A, size_t lda, const float *B, size_t ldb, int32_t m, int32_t n, int32_t k, float *out)
 {

@@ -54,6 +54,101 @@ constexpr int SCORE_ROW_THREADS = 256;
 constexpr int SCORE_CHUNK = 32768;                 // items per piece: a 4 KiB bitmap
 constexpr int SCORE_UNROLL = 4;                    // 16-byte loads in flight per thread
 
+// One pass over a row of S, shared by k_score_rows and k_topk_rows (rm_rowtopk.hpp): the pieces of SCORE_CHUNK items with their bitmap
+// of train items, and per piece the element loads around the aligned 16-byte middle.  The caller says what happens to a score:
+//   elem(i, x, masked)      item i, loaded alone (in front of the first 16-byte boundary, behind the last whole piece);
+//   piece(i, x, mb)         items i .. i + VE - 1 of one aligned 16-byte load; bit j of `mb` = item i + j is a train item;
+//   pass()                  called by EVERY thread of the block in front of each step in which a thread handles at most one element or
+//                           one 16-byte load (so it may hold a barrier): SCORE_ROW_THREADS * VE scores per step at the most.
+// `bitmap` (SCORE_CHUNK / 32 + 2 words) and `sh_taken` are the block's LDS; `cursor` / `tr_end` the user's entries of `train_i`.
+template <class T> struct ScoreVec {
+    typedef T Aligned __attribute__((ext_vector_type(16 / sizeof(T))));
+    typedef T Unaligned __attribute__((ext_vector_type(16 / sizeof(T)), aligned(sizeof(T))));
+};
+template <class T, class Elem, class Piece, class Pass>
+__device__ __forceinline__ void walk_score_row(const T *src, const int n, const int *train_i, int cursor, const int tr_end,
+                                               unsigned *bitmap, int *sh_taken, Elem elem, Piece piece, Pass pass)
+{
+    constexpr int VE = 16 / (int)sizeof(T);                                    // scores per 16-byte piece
+    typedef typename ScoreVec<T>::Aligned VT;
+    const int tid = threadIdx.x;
+    // scores in front of the first 16-byte boundary of the source row
+    const int mis = (int)(((size_t)src) & 15);
+    // (a pointer that is not even a multiple of the score's size never reaches a 16-byte boundary: element loads throughout)
+    const int head = (mis % (int)sizeof(T)) ? n : min(n, mis ? (16 - mis) / (int)sizeof(T) : 0);
+    for (int c0 = 0; c0 < n; c0 += SCORE_CHUNK) {
+        const int c1 = min(n, c0 + SCORE_CHUNK);
+        // ---- the train items of [c0, c1) into the bitmap; the cursor moves behind them ----
+        for (int i = tid; i < SCORE_CHUNK / 32 + 2; i += SCORE_ROW_THREADS) bitmap[i] = 0u;
+        if (tid == 0) *sh_taken = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int e = cursor + tid; e < tr_end; e += SCORE_ROW_THREADS) {
+            const int it = train_i[e];
+            if (it >= c1) break;
+            const unsigned rel = (unsigned)(it - c0);
+            if (rel < (unsigned)SCORE_CHUNK) atomicOr(&bitmap[rel >> 5], 1u << (rel & 31));
+            mine++;
+        }
+        if (mine) atomicAdd(sh_taken, mine);
+        __syncthreads();
+        cursor += *sh_taken;
+        auto masked_bits = [&](int i) -> unsigned {                           // bits of items i, i + 1, ... (i in [c0, c1))
+            const unsigned rel = (unsigned)(i - c0);
+            const unsigned long long w = (unsigned long long)bitmap[rel >> 5] | ((unsigned long long)bitmap[(rel >> 5) + 1] << 32);
+            return (unsigned)(w >> (rel & 31));
+        };
+        // ---- this piece of the row: [lo, hi) element by element around the aligned middle [v0, v1) ----
+        const int lo = c0, hi = c1;
+        int v0 = lo <= head ? head : head + (lo - head + VE - 1) / VE * VE;   // first aligned piece at or behind lo
+        v0 = min(v0, hi);
+        const int v1 = v0 + (hi - v0) / VE * VE;
+        for (int i0 = lo; i0 < v0; i0 += SCORE_ROW_THREADS) { pass(); const int i = i0 + tid; if (i < v0) elem(i, src[i], (masked_bits(i) & 1u) != 0u); }
+        for (int i0 = v1; i0 < hi; i0 += SCORE_ROW_THREADS) { pass(); const int i = i0 + tid; if (i < hi) elem(i, src[i], (masked_bits(i) & 1u) != 0u); }
+        const int nvec = (v1 - v0) / VE;
+        for (int vb = 0; vb < nvec; vb += SCORE_ROW_THREADS * SCORE_UNROLL) {
+            VT x[SCORE_UNROLL];
+            #pragma unroll
+            for (int q = 0; q < SCORE_UNROLL; q++) {
+                const int v = vb + q * SCORE_ROW_THREADS + tid;
+                if (v < nvec) x[q] = *(const VT *)(src + v0 + v * VE);
+            }
+            #pragma unroll
+            for (int q = 0; q < SCORE_UNROLL; q++) {
+                pass();
+                const int v = vb + q * SCORE_ROW_THREADS + tid;
+                if (v < nvec) { const int i = v0 + v * VE; piece(i, x[q], masked_bits(i)); }
+            }
+        }
+        __syncthreads();                                                      // (the bitmap is cleared for the next piece)
+    }
+}
+
+// max / min / has-NaN of a thread's candidates (-0 counted and handed back as +0), and their reduction over the block
+template <class T> struct CandStats {
+    T vmax = -(T)INFINITY, vmin = (T)INFINITY; int has_nan = 0;
+    __device__ __forceinline__ T take(T x)
+    {
+        x = score_canonical<T>(x);
+        has_nan |= x != x;
+        vmax = stat_max(vmax, x); vmin = stat_min(vmin, x);
+        return x;
+    }
+    // thread 0 holds the block's statistics afterwards (`sh_*`: SCORE_ROW_THREADS / WAVE entries each; holds a barrier)
+    __device__ __forceinline__ void reduce_block(T *sh_max, T *sh_min, int *sh_nan)
+    {
+        #pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            vmax = stat_max(vmax, __shfl_xor(vmax, s)); vmin = stat_min(vmin, __shfl_xor(vmin, s)); has_nan |= __shfl_xor(has_nan, s);
+        }
+        const int tid = threadIdx.x, wv = tid >> 6;
+        if ((tid & 63) == 0) { sh_max[wv] = vmax; sh_min[wv] = vmin; sh_nan[wv] = has_nan; }
+        __syncthreads();
+        if (tid == 0)
+            for (int w = 1; w < SCORE_ROW_THREADS / WAVE; w++) { vmax = stat_max(vmax, sh_max[w]); vmin = stat_min(vmin, sh_min[w]); has_nan |= sh_nan[w]; }
+    }
+};
+
 template <class T> struct ScoreRowArgs {
     int n, n_rows, stream_slot0, n_part;
     const int *slot_user, *train_p, *train_i;
@@ -65,9 +160,9 @@ template <class T> struct ScoreRowArgs {
 template <class T>
 __global__ __launch_bounds__(SCORE_ROW_THREADS) void k_score_rows(ScoreRowArgs<T> a)
 {
-    constexpr int VE = 16 / (int)sizeof(T);                                    // scores per 16-byte piece
-    typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
-    typedef T VTU __attribute__((ext_vector_type(16 / sizeof(T)), aligned(sizeof(T))));
+    constexpr int VE = 16 / (int)sizeof(T);
+    typedef typename ScoreVec<T>::Aligned VT;
+    typedef typename ScoreVec<T>::Unaligned VTU;
     __shared__ unsigned bitmap[SCORE_CHUNK / 32 + 2];
     __shared__ int sh_taken;
     __shared__ T sh_max[SCORE_ROW_THREADS / WAVE], sh_min[SCORE_ROW_THREADS / WAVE];
@@ -77,89 +172,25 @@ __global__ __launch_bounds__(SCORE_ROW_THREADS) void k_score_rows(ScoreRowArgs<T
     const int slot = a.stream_slot0 + d;
     const int u = a.slot_user[slot];
     const int n = a.n;
-    const T *src = a.S + (size_t)u * a.lds;
     T *dst = a.rows + (size_t)d * (size_t)a.row_ld;
-    int cursor = a.train_p[u];
-    const int tr_end = a.train_p[u + 1];
-    // scores in front of the first 16-byte boundary of the source row
-    const int mis = (int)(((size_t)src) & 15);
-    // (a pointer that is not even a multiple of the score's size never reaches a 16-byte boundary: element loads throughout)
-    const int head = (mis % (int)sizeof(T)) ? n : min(n, mis ? (16 - mis) / (int)sizeof(T) : 0);
-    T vmax = -(T)INFINITY, vmin = (T)INFINITY; bool has_nan = false;
+    CandStats<T> st;
     const T sentinel = score_sentinel<T>();
-    auto one = [&](T x, bool masked) -> T {
-        if (masked) return sentinel;
-        x = score_canonical<T>(x);
-        has_nan |= x != x;
-        vmax = stat_max(vmax, x); vmin = stat_min(vmin, x);
-        return x;
-    };
-    for (int c0 = 0; c0 < n; c0 += SCORE_CHUNK) {
-        const int c1 = min(n, c0 + SCORE_CHUNK);
-        // ---- the train items of [c0, c1) into the bitmap; the cursor moves behind them ----
-        for (int i = tid; i < SCORE_CHUNK / 32 + 2; i += SCORE_ROW_THREADS) bitmap[i] = 0u;
-        if (tid == 0) sh_taken = 0;
-        __syncthreads();
-        int mine = 0;
-        for (int e = cursor + tid; e < tr_end; e += SCORE_ROW_THREADS) {
-            const int it = a.train_i[e];
-            if (it >= c1) break;
-            const unsigned rel = (unsigned)(it - c0);
-            if (rel < (unsigned)SCORE_CHUNK) atomicOr(&bitmap[rel >> 5], 1u << (rel & 31));
-            mine++;
-        }
-        if (mine) atomicAdd(&sh_taken, mine);
-        __syncthreads();
-        cursor += sh_taken;
-        auto masked_bits = [&](int i) -> unsigned {                           // bits of items i, i + 1, ... (i in [c0, c1))
-            const unsigned rel = (unsigned)(i - c0);
-            const unsigned long long w = (unsigned long long)bitmap[rel >> 5] | ((unsigned long long)bitmap[(rel >> 5) + 1] << 32);
-            return (unsigned)(w >> (rel & 31));
-        };
-        // ---- this piece of the row: [lo, hi) element by element around the aligned middle [v0, v1) ----
-        const int lo = c0, hi = c1;
-        int v0 = lo <= head ? head : head + (lo - head + VE - 1) / VE * VE;   // first aligned piece at or behind lo
-        v0 = min(v0, hi);
-        const int v1 = v0 + (hi - v0) / VE * VE;
-        for (int i = lo + tid; i < v0; i += SCORE_ROW_THREADS) dst[i] = one(src[i], masked_bits(i) & 1u);
-        for (int i = v1 + tid; i < hi; i += SCORE_ROW_THREADS) dst[i] = one(src[i], masked_bits(i) & 1u);
-        const int nvec = (v1 - v0) / VE;
-        for (int vb = 0; vb < nvec; vb += SCORE_ROW_THREADS * SCORE_UNROLL) {
-            VT x[SCORE_UNROLL];
+    walk_score_row<T>(a.S + (size_t)u * a.lds, n, a.train_i, a.train_p[u], a.train_p[u + 1], bitmap, &sh_taken,
+        [&](int i, T x, bool masked) { dst[i] = masked ? sentinel : st.take(x); },
+        [&](int i, const VT &x, unsigned mb) {
+            VT y;
             #pragma unroll
-            for (int q = 0; q < SCORE_UNROLL; q++) {
-                const int v = vb + q * SCORE_ROW_THREADS + tid;
-                if (v < nvec) x[q] = *(const VT *)(src + v0 + v * VE);
-            }
-            #pragma unroll
-            for (int q = 0; q < SCORE_UNROLL; q++) {
-                const int v = vb + q * SCORE_ROW_THREADS + tid;
-                if (v >= nvec) continue;
-                const int i = v0 + v * VE;
-                const unsigned mb = masked_bits(i);
-                VT y;
-                #pragma unroll
-                for (int j = 0; j < VE; j++) y[j] = one(x[q][j], (mb >> j) & 1u);
-                *(VTU *)(dst + i) = y;
-            }
-        }
-        __syncthreads();                                                      // (the bitmap is cleared for the next piece)
-    }
+            for (int j = 0; j < VE; j++) y[j] = ((mb >> j) & 1u) ? sentinel : st.take(x[j]);
+            *(VTU *)(dst + i) = y;
+        },
+        [] {});
     // the padding up to the row stride: masked, like the items beyond n of the sweep's last tile
     for (long long i = (long long)n + tid; i < a.row_ld; i += SCORE_ROW_THREADS) dst[i] = sentinel;
     // ---- the block's statistics -> part 0 of the slot ----
-    int hn = has_nan ? 1 : 0;
-    #pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        vmax = stat_max(vmax, __shfl_xor(vmax, s)); vmin = stat_min(vmin, __shfl_xor(vmin, s)); hn |= __shfl_xor(hn, s);
-    }
-    const int wv = tid >> 6;
-    if ((tid & 63) == 0) { sh_max[wv] = vmax; sh_min[wv] = vmin; sh_nan[wv] = hn; }
-    __syncthreads();
+    st.reduce_block(sh_max, sh_min, sh_nan);
     if (tid == 0) {
-        for (int w = 1; w < SCORE_ROW_THREADS / WAVE; w++) { vmax = stat_max(vmax, sh_max[w]); vmin = stat_min(vmin, sh_min[w]); hn |= sh_nan[w]; }
         PartialStat<T> ps;
-        ps.vmax = vmax; ps.vmin = vmin; ps.rocsum = 0; ps.has_nan = hn; ps.pad = 0;
+        ps.vmax = st.vmax; ps.vmin = st.vmin; ps.rocsum = 0; ps.has_nan = st.has_nan; ps.pad = 0;
         a.pst[(size_t)slot * a.n_part] = ps;
     }
 }
