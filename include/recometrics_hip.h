@@ -284,7 +284,9 @@ void rm_debug_reload_switches(void);
  * stream: out[0] plan+pack+positives, out[1] sweep kernel, out[2] finalize, out[3] whole device section;
  * out[4] = launches of the sweep kernel, out[5] = item splits, out[6] = sweep blocks, out[7] = dynamic LDS bytes,
  * out[8] = user lanes (slots) of the launch that out[1] brackets -- when the blocks of streamed users run beside the main
- * launch on a second stream, out[1] times the main launch only --, out[9] = user lanes of the whole call.
+ * launch on a second stream, out[1] times the main launch only --, out[9] = user lanes of the whole call,
+ * out[10] = 1 when the call ran on what the context kept of the previous call's train / test split (same arrays, same contents:
+ * DESIGN.md section 1), 0 when it planned and validated the split itself, -1 for the calls that never reuse one.
  * Forces a synchronisation of that stream.  Returns the number of values written. */
 int rm_get_timings(double *out, int n);
 

@@ -186,10 +186,10 @@ def reload_switches():
 
 def timings():
     lib = load()
-    buf = (C.c_double * 10)()
-    n = lib.rm_get_timings(buf, 10)
+    buf = (C.c_double * 11)()
+    n = lib.rm_get_timings(buf, 11)
     keys = ("prep_ms", "sweep_ms", "finalize_ms", "device_ms", "sweep_launches", "item_splits", "sweep_blocks", "lds_bytes",
-            "timed_slots", "total_slots")
+            "timed_slots", "total_slots", "split_reused")
     return {k: buf[i] for i, k in enumerate(keys[:n])}
 
 

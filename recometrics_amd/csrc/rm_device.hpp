@@ -67,6 +67,9 @@ struct Plan {                                     // produced on device, read ba
     int stream_enable;      // 1 = those users are streamed (their score rows fit the HBM budget), 0 = they get one slot per chunk
     int max_npos;           // longest test row (k_count_long)
     int n_stream_chunks;    // chunks of POS_CHUNK test entries over all streamed users (work items of the positives kernels)
+    // the words of ONE CALL (the rest describes the split): a call that reuses a kept plan zeroes [split_differs, csr_bad) only
+    // (n_heavy and n_only_ndcg lie among them: counters of k_classify that no later kernel reads -- the host keeps their values)
+    int split_differs;                  // k_split_same: some array of the caller's split differs from the context's copy of it
     int nonfinite;                      // some factor of A is NaN / Inf
     int nonfinite_b;                    // some factor of B is NaN / Inf
     int n_noise_flagged;                // fp32 + noise, first pass: users whose ranking the noise can change (rm_noise.hpp)

@@ -55,8 +55,9 @@ struct RmError { int code; std::string msg; };
 // tests/test_switches_cpu.py compares this table with that list); nothing here turns a feature of the call off.
 struct Switches {
     bool no_train_bits, no_spec, no_side, ext_topk, no_test_mask, hbm_lists, nsub2, no_pending, no_pos_beside, no_seed, rank_generic,
-         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk;
-    long long free_mb, stream_budget_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed;      // -1 = not set
+         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk, no_split_cache;
+    long long free_mb, stream_budget_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed, split_cache_mb;      // -1 = not set
+    unsigned long long epoch = 0;                                              // counts load(): what a context keeps of a split was decided under one set of switches
     double batch_users;                                                        // 0 = not set
     std::string splits;
     static bool on(const char *name) { return getenv(name) != nullptr; }
@@ -78,6 +79,9 @@ struct Switches {
         lane_cap_set = num("RM_DEBUG_LANE_CAP");                // entries per lane buffer (A/B timing; rounded to 16, never below what a selection needs)
         sample_seed = num("RM_DEBUG_SAMPLE_SEED");            // items of the sample that seeds the lane buffers' bounds: 0 = none, else forced to 64 / 256 / 1024 / 2048 / 4096 (A/B timing, tests)
         lane_cap_min = num("RM_DEBUG_LANE_CAP_MIN");          // the smallest lane buffers that work: a selection every few tiles (tests)
+        no_split_cache = on("RM_DEBUG_NO_SPLIT_CACHE");        // every call plans, validates and builds its split's tables itself (A/B timing, the tests' reference path)
+        split_cache_mb = num("RM_SPLIT_CACHE_MB");              // the largest split (bytes of its five arrays) a context keeps copies of; 0 = none
+        epoch++;
         const char *b = getenv("RM_BATCH_USERS"); batch_users = b ? atof(b) : 0.0;
         const char *s = getenv("RM_DEBUG_SPLITS"); splits = s ? s : "";
     }
@@ -162,10 +166,39 @@ struct DiscountTable {                       // "log2tab": log2(i + 2), the DCG 
     bool holds(const Workspace &ws, int K_) const { return stamp != 0 && stamp == ws.peek("log2tab").stamp && K >= K_; }
     void set(const Workspace &ws, int K_) { stamp = ws.peek("log2tab").stamp; K = K_; }
 };
+// What a context keeps of the train / test split of its last metric call, for the next call on the same split (one model after
+// another on one split: a hyper-parameter search, an evaluation per epoch): copies of the five arrays, in buffers of their own, and
+// the fact that everything the plan stage derives from them is still in the workspace -- the users' flags, the slot / group / block
+// tables, the device Plan, the user of every test entry and whether it is a train item, the dense train rows (DenseRows), the
+// ideal-DCG values of the long rows.  No later stage of a call writes any of these (k_finalize reads them), every other pass through
+// run() on the context voids the record before it plans, and so does a new allocation of any of the buffers (stamps).
+// `key`: the arrays' addresses and sizes and every decision of the plan stage that does not come from the arrays' contents; whether
+// the CONTENTS are still the ones copied is k_split_same's answer, call by call.
+constexpr long long SPLIT_CACHE_DEFAULT_MB = 1024;      // RM_SPLIT_CACHE_MB when it is not set
+struct SplitKey {
+    const void *arr[SPLIT_ARRAYS]; long long words[SPLIT_ARRAYS], nnz_train, nnz_test;
+    int m, n, k, K, elem, req, min_items_pool, min_pos_test, heavy_npos, ng;
+    int cold, cumulative, want_lane, ext_topk, allow_stream, force_stream, dense_ok, flat_early, csr_checked, rank_out;
+    unsigned long long switches;                                // Switches::epoch
+};
+struct SplitCache {
+    static constexpr const char *copy_names[SPLIT_ARRAYS] = {"split_train_p", "split_train_i", "split_test_p", "split_test_i", "split_test_v"};
+    bool valid = false; SplitKey key{}; Plan hp{}; bool check_nan = false, dense_masked = false;
+    std::vector<std::pair<std::string, unsigned long long>> stamps;       // the buffers the record speaks of, as allocated then
+    void invalidate() { valid = false; }
+    void keep(const Workspace &ws, const char *name) { stamps.emplace_back(name, ws.peek(name).stamp); }
+    bool holds(const Workspace &ws, const SplitKey &k) const
+    {
+        if (!valid || std::memcmp(&key, &k, sizeof(SplitKey)) != 0) return false;
+        for (const auto &s : stamps) if (s.second == 0 || ws.peek(s.first.c_str()).stamp != s.second) return false;
+        return true;
+    }
+    const void *copy(const Workspace &ws, int i) const { return ws.peek(copy_names[i]).ptr; }
+};
 // The roles of the events that order a context's two streams beside the call's against it: who records each and who waits is the
 // table in DESIGN.md section 1.  One event per role; `Beside` (below) is the only code that touches them.
 enum SideMark { SIDE_FORK, SIDE_JOIN, SIDE_PLAN_FORK, SIDE_CHECKS_DONE, SIDE_ROWS_AND_PACKS, SIDE_ROWS_FOR_POS, SIDE_TOP_VALUES,
-                SIDE_SWEEP_FORK, SIDE_SWEEP_DEEP_DONE, SIDE_MERGED, SIDE_MARKS };
+                SIDE_SWEEP_FORK, SIDE_SWEEP_DEEP_DONE, SIDE_MERGED, SIDE_VERDICT, SIDE_SPLIT_KEPT, SIDE_MARKS };
 enum PosMark { POS_PLAN_FORK, POS_MAXIMA_DONE, POS_SCORES_AFTER_COPY, POS_SCORES_DONE, POS_TABLES_INIT, POS_STREAMED_PLACED, POS_MARKS };
 enum PassEvent { EV_START, EV_PREP_END /* = sweep launched: HostRange::exact_beside_last waits for it */, EV_SWEEP_END, EV_END, EV_COUNT };   // timing (Ctx::stage_ms)
 // The page-locked words of a context through which the counts of the fp32 tie noise come back from the device (one 64-byte
@@ -219,6 +252,8 @@ struct Ctx {
     int timed_slots = 0, total_slots = 0;     // slots (user lanes) of the sweep launch the "sweep" timing brackets / of the call
     double acc[4] = {0, 0, 0, 0};            // prep / sweep / finalize / total ms of the batches already read back (host entry)
     PackedItems packed; DenseRows dense; DiscountTable discounts;    // what "Bp", "train_bits" and "log2tab" of `ws` hold
+    SplitCache split;                                                // ... and what the plan stage's buffers hold of the last call's split
+    int split_reused = -1;               // the most recent pass: 1 = it ran on what `split` kept, 0 = it planned itself, -1 = a pass that never reuses
     bool high_priority = false;          // streams of this context are created with the highest priority (the exact passes of the tie noise)
     Plan *pinned_plan = nullptr;                                                    // page-locked landing place of the plan read-back
     void stage_ms(float ms[4]) const       // prep / sweep / finalize / total of the most recent pass, from its four events (which have completed)
@@ -651,6 +686,7 @@ template <class T>
 void check_csr_now(const Call<T> &c, hipStream_t stream, Ctx &cx)
 {
     Plan *plan = (Plan *)cx.ws.get("plan", sizeof(Plan));
+    cx.split.invalidate();                                         // (the Plan is zeroed below)
     if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));
     HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
     launch_csr_checks(c.m, c.n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, c.only_users, stream);
@@ -697,6 +733,7 @@ struct Beside {
     void join(int role) { mark(role); await(role, call); }
     bool marked(int role) const { return at[role] != 0; }              // marked, and the call's stream has not been told to wait yet
     void sync() { if (enabled && st) { HIP_CHECK(hipStreamSynchronize(st)); joined = handed; } }      // the HOST waits (the second plan)
+    void host_wait(int role) { if (enabled) { HIP_CHECK(hipEventSynchronize(ev[role])); joined_at(role); } }      // ... for a mark only
 };
 
 // LDS of a sweep block of depth j (each group's positives table is aligned to its own size, 2^j rows of GU scores: worst-case
@@ -844,7 +881,8 @@ struct Pipeline {
     typedef Prec<T> P;
     typedef typename std::remove_pointer<decltype(typename P::Args{}.thr_shared)>::type ThrT;
     static constexpr int GU = P::GU;
-    const Call<T> &c; hipStream_t stream; Ctx &cx; Workspace &ws;
+    Call<T> c;                              // (a copy: a pass on a kept split reads the context's copies of the five arrays)
+    hipStream_t stream; Ctx &cx; Workspace &ws;
     const int m, n, k, K;
     const bool use_side = !g_sw.no_side;    // (decides what is launched; where it only decides a stream, a record or a wait, Beside does)
     Beside side, pos;                       // kernels that do not depend on one another run beside the call's stream
@@ -858,6 +896,8 @@ struct Pipeline {
     bool want_lane = false, ext_topk = false, items_known = false, dense_ok = false;
     bool row_topk = false;                  // lists from the caller's scores, selected while the row is read (k_topk_rows): no score row is stored
     bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
+    // the split the context kept (SplitCache): may this pass run on it, does it, may the next one run on this pass's
+    bool allow_reuse = true, reused = false, keepable = false; SplitKey split_key{};
     Plan hp{};
     int n_slots = 0, n_stream = 0, stream_slot0 = 0; bool check_nan = false;
     // geometry
@@ -979,6 +1019,19 @@ struct Pipeline {
         // (the caller's scores: the test entries' scores are gathered by entry whatever the switch says -- there is no kernel by slot)
         flat_early = want_auc && !c.only_users && c.nnz_test > 0 && (!g_sw.no_pos_flat || c.scores);
         int *ent_user = nullptr; unsigned char *ent_masked = nullptr;
+        // The split the context kept: when this call's key is the kept one, the pass reads the context's COPIES of the five arrays --
+        // validated when they were made, and the arrays every kept table was derived from -- while k_split_same finds out whether the
+        // caller's arrays still equal them: nothing is ever indexed through an array that has not been validated.
+        const void *theirs[SPLIT_ARRAYS] = {c.train_p, c.train_i, c.test_p, c.test_i, c.test_v};
+        keepable = make_split_key(split_key);
+        cx.split_reused = keepable ? 0 : -1;
+        reused = keepable && allow_reuse && cx.split.holds(ws, split_key) &&
+                 (!dense_ok || cx.dense.fits(ws, m, dense_row_words(n), cx.split.dense_masked));
+        if (reused) {
+            c.train_p = (const int *)cx.split.copy(ws, 0); c.train_i = (const int *)cx.split.copy(ws, 1);
+            c.test_p = (const int *)cx.split.copy(ws, 2); c.test_i = (const int *)cx.split.copy(ws, 3);
+            if (c.test_v) c.test_v = (const T *)cx.split.copy(ws, 4);
+        } else cx.split.invalidate();                                 // (the kernels below overwrite what the record speaks of)
         PosArgs<T> pf{};
         if (flat_early) {
             ent_user = (int *)ws.get("ent_user", sizeof(int) * (size_t)c.nnz_test);
@@ -990,7 +1043,8 @@ struct Pipeline {
             pf.noise_row = c.noise_row; pf.noise_row0 = c.noise_row0; pf.noise_E = c.noise_E; pf.noise_ld = c.noise_ld;
             pf.noise_flag = c.noise_flag; pf.plan = plan;
         }
-        for (int attempt = 0; ; attempt++) {
+        if (reused) plan_reused(pf, ent_user, ent_masked, theirs);
+        else for (int attempt = 0; ; attempt++) {
             // ---- the plan chain: five launches that depend on one another, on the call's stream (index pointers only) ----
             if (attempt == 0) HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
             else {
@@ -1072,26 +1126,127 @@ struct Pipeline {
             throw_csr_defects(hp, c, cx);
             // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
             if (ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0) {
-                ca.allow_stream = 0; ca.check_ptr = 0;
+                ca.allow_stream = 0; ca.check_ptr = 0; keepable = false;     // (a second plan is never kept)
                 // (attempt 0's kernels on BOTH side streams read `flags` and `plan`, which the second plan rewrites: wait for them)
                 side.sync(); pos.sync();
                 continue;
             }
             break;
         }
-        throw_csr_defects(hp, c, cx);
+        if (!reused) throw_csr_defects(hp, c, cx);
         n_slots = hp.n_slots;
         // streamed users own the last slots; the tables and their kernels cover slots [0, stream_slot0)
         n_stream = (want_auc || ext_topk) ? hp.class_count[STREAM_CLASS] : 0;
         stream_slot0 = n_stream > 0 ? hp.class_offset[STREAM_CLASS] : n_slots;
-        // |any partial sum| <= k * max|A| * max|B|: if that is comfortably finite in T, no score is NaN / Inf
+        if (!reused) check_nan = scores_may_overflow();                // (a pass on a kept split assumes the kept answer until verdict())
+    }
+    // |any partial sum| <= k * max|A| * max|B|: if that is comfortably finite in T, no score is NaN / Inf
+    bool scores_may_overflow()
+    {
         if (items_known) { hp.amax_b = cx.packed.amax_b; hp.nonfinite_b = cx.packed.nonfinite_b; }
         else { cx.packed.amax_b = hp.amax_b; cx.packed.nonfinite_b = hp.nonfinite_b; }
         double amax_a, amax_b;
         std::memcpy(&amax_a, &hp.amax_a, 8); std::memcpy(&amax_b, &hp.amax_b, 8);
         const double tmax = std::is_same<T, float>::value ? 3.0e38 : 1.0e308;
-        check_nan = hp.nonfinite || hp.nonfinite_b || !((double)k * amax_a * 1.001 < tmax / std::max(amax_b, 1e-300));
-        if (c.scores) check_nan = false;                               // (k_score_rows looks at every candidate score whatever it is)
+        if (c.scores) return false;                                    // (k_score_rows looks at every candidate score whatever it is)
+        return hp.nonfinite || hp.nonfinite_b || !((double)k * amax_a * 1.001 < tmax / std::max(amax_b, 1e-300));
+    }
+
+    // ---- the split the context kept (SplitCache) ----
+    // Which calls keep and reuse: plain metric calls by device pointers over all their users.  The passes of the tie noise, the
+    // batches of a host-pointer call, lists and score matrices plan for themselves (and void the record).
+    bool make_split_key(SplitKey &key) const
+    {
+        std::memset(&key, 0, sizeof(SplitKey));
+        if (g_sw.no_split_cache || !use_side || c.reco || c.scores || c.noise || c.only_users || c.ext_bits || c.noise_E || c.noise_flag ||
+            c.first_pass_flags || c.flag_snapshot || c.items_tag != 0 || !c.test_p || m <= 0) return false;
+        const void *arr[SPLIT_ARRAYS] = {c.train_p, c.train_i, c.test_p, c.test_i, c.test_v};
+        const long long words[SPLIT_ARRAYS] = {(long long)m + 1, std::max<long long>(c.nnz_train, 0), (long long)m + 1, std::max<long long>(c.nnz_test, 0),
+                                               c.test_v ? std::max<long long>(c.nnz_test, 0) * (long long)(sizeof(T) / 4) : 0};
+        long long total = 0;
+        for (int i = 0; i < SPLIT_ARRAYS; i++) { key.arr[i] = arr[i]; key.words[i] = words[i]; total += words[i]; }
+        if (total * 4 > ((g_sw.split_cache_mb >= 0 ? g_sw.split_cache_mb : SPLIT_CACHE_DEFAULT_MB) << 20)) return false;
+        key.nnz_train = c.nnz_train; key.nnz_test = c.nnz_test;
+        key.m = m; key.n = n; key.k = k; key.K = K; key.elem = (int)sizeof(T); key.req = req;
+        key.min_items_pool = min_items_pool; key.min_pos_test = min_pos_test; key.heavy_npos = ca.heavy_npos; key.ng = NG;
+        key.cold = c.cold; key.cumulative = c.cumulative; key.want_lane = want_lane; key.ext_topk = ext_topk;
+        key.allow_stream = ca.allow_stream; key.force_stream = ca.force_stream; key.dense_ok = dense_ok; key.flat_early = flat_early;
+        key.csr_checked = c.csr_checked; key.rank_out = (c.topk_idx ? 1 : 0) | (c.pos_rank ? 2 : 0) | (c.status ? 4 : 0);
+        key.switches = g_sw.epoch;
+        return true;
+    }
+    // The plan stage of a pass on the kept split.  On the side stream k_split_same, the maxima and the read-back of the call's words
+    // of the Plan (SIDE_VERDICT: the host's one wait, verdict()); on the positives' stream, at once, the scores of the test entries.
+    // Every kernel of this pass reads the copies, so none of them waits for k_split_same.
+    void plan_reused(const PosArgs<T> &pf, const int *ent_user, const unsigned char *ent_masked, const void *const theirs[SPLIT_ARRAYS])
+    {
+        const SplitCache &kept = cx.split;
+        const size_t at = offsetof(Plan, split_differs);
+        HIP_CHECK(hipMemsetAsync((char *)plan + at, 0, offsetof(Plan, csr_bad) - at, stream));
+        // (the comparison first: the host waits for it, and the blocks of the positives' scores take every wave slot they find)
+        const hipStream_t aux = side.fork(SIDE_PLAN_FORK);
+        SplitSameArgs ss{};
+        long long longest = 1;
+        for (int i = 0; i < SPLIT_ARRAYS; i++) {
+            ss.theirs[i] = (const unsigned *)theirs[i]; ss.ours[i] = (const unsigned *)kept.copy(ws, i); ss.words[i] = kept.key.words[i];
+            longest = std::max(longest, ss.words[i]);
+        }
+        ss.plan = plan;
+        const unsigned blocks = (unsigned)std::min<long long>(SPLIT_SAME_BLOCKS, cdiv(cdiv(longest, 4), SPLIT_SAME_THREADS));
+        hipLaunchKernelGGL(k_split_same, dim3(blocks), dim3(SPLIT_SAME_THREADS), 0, aux, ss);
+        hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
+        hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
+        HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, aux));
+        side.mark(SIDE_VERDICT);
+        if (flat_early) {
+            const hipStream_t sc = pos.fork(POS_PLAN_FORK);
+            hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pf, ent_user);
+            hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, ent_masked);      // (`ent_masked`: kept)
+            pos.mark(POS_SCORES_DONE);
+        }
+        check_launch(hipGetLastError());
+        hp = kept.hp; check_nan = kept.check_nan;
+        bits_early = dense_ok; bits_early_masked = kept.dense_masked; masked_from_bits = true;
+        RM_TRACE_POINT("run: kept split, comparison + positives enqueued");
+    }
+    // The host's wait of a pass on the kept split, in front of the sweep's launch (the device is busy with the positives' chain):
+    // are the caller's arrays the kept ones, and does the sweep variant that was prepared fit this call's factors?  If not, the pass is
+    // abandoned -- the host waits for what was enqueued, the record is void -- and run() plans the call from its own arrays.
+    bool verdict()
+    {
+        side.host_wait(SIDE_VERDICT);
+        RM_TRACE_POINT("run: verdict read back");
+        const Plan &rb = *cx.pinned_plan;
+        hp.amax_a = rb.amax_a; hp.amax_b = rb.amax_b; hp.nonfinite = rb.nonfinite; hp.nonfinite_b = rb.nonfinite_b;
+        if (!rb.split_differs && scores_may_overflow() == check_nan) { cx.split_reused = 1; return true; }
+        side.sync(); pos.sync();
+        HIP_CHECK(hipStreamSynchronize(stream));
+        cx.split.invalidate(); cx.dense.invalidate(); cx.packed.invalidate();
+        cx.split_reused = 0;
+        return false;
+    }
+    // A pass that planned for itself leaves its split to the next call: the copies are made on the side stream beside the sweep,
+    // export_ranks() joins them and declares the record valid.
+    void keep_split()
+    {
+        if (!keepable || reused) return;
+        SplitCache &kept = cx.split;
+        void *dst[SPLIT_ARRAYS] = {};
+        try { for (int i = 0; i < SPLIT_ARRAYS; i++) if (split_key.words[i] > 0) dst[i] = ws.get(SplitCache::copy_names[i], (size_t)split_key.words[i] * 4); }
+        catch (const RmError &) { keepable = false; return; }          // (no memory for the copies: nothing is kept)
+        const hipStream_t st = side.on();
+        for (int i = 0; i < SPLIT_ARRAYS; i++)
+            if (dst[i]) HIP_CHECK(hipMemcpyAsync(dst[i], split_key.arr[i], (size_t)split_key.words[i] * 4, hipMemcpyDeviceToDevice, st));
+        side.mark(SIDE_SPLIT_KEPT);
+        std::memcpy(&kept.key, &split_key, sizeof(SplitKey));
+        kept.hp = hp; kept.check_nan = check_nan; kept.dense_masked = dense_ok && cx.dense.masked;
+        kept.stamps.clear();
+        for (const char *name : {"flags", "user_nslots", "uslot_base", "plan", "heavy_users", "slot_user", "slot_chunk", "slot_index", "slot_j", "gj", "grow", "sc_user", "sc_chunk"})
+            kept.keep(ws, name);
+        if (flat_early) { kept.keep(ws, "ent_user"); kept.keep(ws, "ent_masked"); }
+        if (dense_ok) kept.keep(ws, "train_bits");
+        if (fa.heavy_topv) { kept.keep(ws, "heavy_topv"); kept.keep(ws, "heavy_nan"); }
+        for (int i = 0; i < SPLIT_ARRAYS; i++) if (dst[i]) kept.keep(ws, SplitCache::copy_names[i]);
     }
 
     // ideal-DCG values of the users with very long test rows (k_top_values: a wavefront per such user, a chain of K dependent
@@ -1108,6 +1263,7 @@ struct Pipeline {
         fa.heavy_topv = (T *)ws.get("heavy_topv", sizeof(T) * (size_t)m * (size_t)fa.heavy_ld);
         fa.heavy_nan = (unsigned char *)ws.get("heavy_nan", (size_t)m);
         fa.heavy_users = heavy_users; fa.n_heavy = hp.n_heavy;
+        if (reused) return;                                          // (the values depend on the test rows and k_metrics alone: kept)
         hipLaunchKernelGGL((k_top_values<T, T>), dim3(cdiv((long long)hp.n_heavy * WAVE, 256)), dim3(256), 0, side.fork(SIDE_FORK), fa);
         side.mark(SIDE_TOP_VALUES);
     }
@@ -1488,6 +1644,7 @@ struct Pipeline {
             hipLaunchKernelGGL(k_export_pos_rank, dim3(cdiv(m, 128)), dim3(128), 0, stream, c.nnz_test, m, c.test_p, flags, pos_order, rank_sorted, c.pos_rank,
                                (want_auc && n_slots > 0) ? 1 : 0, c.status);
         RM_TRACE_POINT("run: finalisation enqueued");
+        if (side.marked(SIDE_SPLIT_KEPT)) { side.await(SIDE_SPLIT_KEPT, stream); cx.split.valid = true; }      // (keep_split's copies)
         HIP_CHECK(hipEventRecord(cx.ev[EV_END], stream));
         HIP_CHECK(hipEventRecord(cx.done, stream));
         cx.ev_recorded = true;
@@ -1500,16 +1657,24 @@ struct Pipeline {
 template <class T>
 void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
 {
-    Pipeline<T> p(c, stream, cx);
-    p.begin();
-    p.plan_stage();
-    if (p.row_topk) { p.topk_rows(); p.export_ranks(); return; }
-    p.g = c.scores ? scores_geometry(p.hp, c.n, p.want_auc)
-                   : sweep_geometry<T>(c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
-    p.prep();
-    p.sweep();
-    if (c.reco) p.finalize_reco(); else p.finalize();
-    p.export_ranks();
+    // (a pass on the split the context kept may find, in front of its sweep, that the caller's arrays are no longer the kept ones:
+    // the second round plans the call from them, as every call did before there was anything to keep)
+    for (int round = 0; round < 2; round++) {
+        Pipeline<T> p(c, stream, cx);
+        p.allow_reuse = round == 0;
+        p.begin();
+        p.plan_stage();
+        if (p.row_topk) { p.topk_rows(); p.export_ranks(); return; }
+        p.g = c.scores ? scores_geometry(p.hp, c.n, p.want_auc)
+                       : sweep_geometry<T>(p.c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
+        p.prep();
+        if (p.reused && !p.verdict()) continue;
+        p.sweep();
+        p.keep_split();
+        if (c.reco) p.finalize_reco(); else p.finalize();
+        p.export_ranks();
+        return;
+    }
 }
 
 // ---- tie noise on top of run() (rm_noise.hpp) ---------------------------------------------------------------------------
@@ -2525,6 +2690,7 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
     std::lock_guard<std::mutex> lk(cx.mu);
     Workspace &ws = cx.ws;
     cx.packed.invalidate();                                  // the packed item image is overwritten below
+    cx.split.invalidate();                                   // ... and so are the slot tables
     hipStream_t stream = nullptr;
     T *dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
     T *dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
@@ -2889,10 +3055,11 @@ extern "C" int rm_get_timings(double *out, int n)
         cx->stage_ms(ms);
     }
     for (int i = 0; i < 4; i++) cx->timings[i] = cx->acc[i] + ms[i];
-    const int cnt = n < 10 ? n : 10;
+    const int cnt = n < 11 ? n : 11;
     for (int i = 0; i < cnt && i < 8; i++) out[i] = cx->timings[i];
     if (cnt > 8) out[8] = cx->timed_slots;
     if (cnt > 9) out[9] = cx->total_slots;
+    if (cnt > 10) out[10] = cx->split_reused;
     return cnt;
 }
 

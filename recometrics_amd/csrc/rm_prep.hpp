@@ -438,6 +438,39 @@ __global__ void k_absmax(const T *X, size_t ld, long long rows, int k, unsigned 
     }
 }
 
+// Is the caller's train / test split the one the context keeps copies of (SplitCache, rm_lib.hip)?  Up to five arrays are compared
+// with their copies bit for bit, as 32-bit words: 16-byte loads where the caller's array is 16-byte aligned (the copies always
+// are), four pairs of loads in flight per thread.  One reduction per block; a block that met a difference stores 1 to
+// plan->split_differs, which the host zeroed in front of the launch -- the word stays 0 exactly when every array equals its copy.
+// Both sides are read within the sizes of the call, never through what they hold.
+constexpr int SPLIT_ARRAYS = 5, SPLIT_SAME_THREADS = 256, SPLIT_SAME_BLOCKS = 2048;
+struct SplitSameArgs { const unsigned *theirs[SPLIT_ARRAYS], *ours[SPLIT_ARRAYS]; long long words[SPLIT_ARRAYS]; Plan *plan; };
+__global__ __launch_bounds__(SPLIT_SAME_THREADS) void k_split_same(SplitSameArgs a)
+{
+    unsigned diff = 0;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    #pragma unroll 1
+    for (int s = 0; s < SPLIT_ARRAYS; s++) {
+        const unsigned *x = a.theirs[s], *y = a.ours[s];
+        const long long w = a.words[s];
+        if (w <= 0) continue;
+        long long done = 0;
+        if ((((size_t)x) & 15) == 0) {
+            const long long nv = w >> 2;
+            for (long long i = tid; i < nv; i += 4 * stride) {
+                uint4 p[4], q[4];
+                #pragma unroll
+                for (int u = 0; u < 4; u++) { const long long j = i + u * stride; const long long jj = j < nv ? j : i; p[u] = ((const uint4 *)x)[jj]; q[u] = ((const uint4 *)y)[jj]; }
+                #pragma unroll
+                for (int u = 0; u < 4; u++) diff |= (p[u].x ^ q[u].x) | (p[u].y ^ q[u].y) | (p[u].z ^ q[u].z) | (p[u].w ^ q[u].w);
+            }
+            done = nv << 2;
+        }
+        for (long long i = done + tid; i < w; i += stride) diff |= x[i] ^ y[i];
+    }
+    if (__syncthreads_or(diff != 0) && threadIdx.x == 0) a.plan->split_differs = 1;
+}
+
 // A head start for the streaming top-K: the user's test items are candidates themselves, so the K-th best of THEIR scores (known
 // before the sweep: k_pos_scores) is a valid lower bound of the K-th best score overall.  It seeds thr_shared, the bound every
 // partial list of the user filters with from its first tile on (the sweep only ever raises it).  With a model that ranks the
