@@ -143,6 +143,28 @@ def _p(a):
     return None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
 
 
+def _dp(x):
+    """an integer device address (0 == NULL)"""
+    return C.c_void_p(int(x)) if x else None
+
+
+def _metric_outs(outs, want, m, k_metrics, cumulative, dtype):
+    """The ten outputs of a host entry in METRIC_ORDER, as the reference's cpp_funs.calc_reco_metrics returns them (wrapper.pyx:306-323):
+    size-0 arrays for metrics not requested, (m, k) arrays for cumulative top-K metrics.  `outs`: ten caller-owned flat arrays
+    (size 0 = not requested) instead of new ones."""
+    if outs is None:
+        size_arr = m * k_metrics if cumulative else m
+        outs = [np.empty((m if name in ("roc", "pr") else size_arr) if want.get(name) else 0, dtype=dtype) for name in METRIC_ORDER]
+    if cumulative:
+        outs = [(o.reshape((m, k_metrics)) if o.size else o.reshape((0, 0))) if i < 8 else o for i, o in enumerate(outs)]
+    return tuple(outs)
+
+
+def _list_outs(m, k_top, dtype, return_scores=True):
+    """ids [m, k_top], scores [m, k_top] or None, status [m] of a list entry"""
+    return (np.empty((m, k_top), dtype=np.int32), np.empty((m, k_top), dtype=dtype) if return_scores else None, np.empty(m, dtype=np.int32))
+
+
 def has_openmp():
     return bool(load().rm_has_openmp())
 
@@ -241,21 +263,14 @@ def calc_metrics(A, lda, B, ldb, train_p, train_i, test_p, test_i, test_v, k_met
     dtype = A.dtype.type
     m, k = A.shape
     n = B.shape[0]
-    size_arr = m * k_metrics if cumulative else m
-    if outs is None:                                   # `outs`: ten caller-owned flat arrays (size 0 = not requested)
-        outs = []
-        for name in METRIC_ORDER:
-            cnt = (m if name in ("roc", "pr") else size_arr) if want.get(name) else 0
-            outs.append(np.empty(cnt, dtype=dtype))
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
     fn = getattr(lib, "rm_calc_metrics_" + _suffix(dtype))
     rc = fn(_p(A), lda, _p(B), ldb, m, n, k, _p(train_p), _p(train_i), _p(test_p), _p(test_i), _p(test_v),
             k_metrics, int(bool(cumulative)), int(bool(break_ties_with_noise)), *[_p(o) for o in outs],
             int(bool(consider_cold_start)), min_items_pool, min_pos_test, nthreads, seed)
     if rc:
         _raise(lib, rc)
-    if cumulative:
-        outs = [(o.reshape((m, k_metrics)) if o.size else o.reshape((0, 0))) if i < 8 else o for i, o in enumerate(outs)]
-    return tuple(outs)
+    return outs
 
 
 def calc_metrics_device(dtype, A, lda, B, ldb, m, n, k, train_p, train_i, nnz_train, test_p, test_i, test_v, nnz_test,
@@ -265,12 +280,9 @@ def calc_metrics_device(dtype, A, lda, B, ldb, m, n, k, train_p, train_i, nnz_tr
     of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
     lib = load()
     fn = getattr(lib, "rm_calc_metrics_dev_" + _suffix(dtype))
-
-    def vp(x):
-        return C.c_void_p(int(x)) if x else None
-    rc = fn(vp(A), lda, vp(B), ldb, m, n, k, vp(train_p), vp(train_i), nnz_train, vp(test_p), vp(test_i), vp(test_v), nnz_test,
-            k_metrics, int(bool(cumulative)), int(bool(break_ties_with_noise)), *[vp(o) for o in outs],
-            int(bool(consider_cold_start)), min_items_pool, min_pos_test, seed, vp(stream))
+    rc = fn(_dp(A), lda, _dp(B), ldb, m, n, k, _dp(train_p), _dp(train_i), nnz_train, _dp(test_p), _dp(test_i), _dp(test_v), nnz_test,
+            k_metrics, int(bool(cumulative)), int(bool(break_ties_with_noise)), *[_dp(o) for o in outs],
+            int(bool(consider_cold_start)), min_items_pool, min_pos_test, seed, _dp(stream))
     if rc:
         _raise(lib, rc)
 
@@ -282,21 +294,14 @@ def calc_metrics_scores(S, lds, train_p, train_i, test_p, test_i, test_v, k_metr
     lib = load()
     dtype = S.dtype.type
     m, n = S.shape
-    size_arr = m * k_metrics if cumulative else m
-    if outs is None:
-        outs = []
-        for name in METRIC_ORDER:
-            cnt = (m if name in ("roc", "pr") else size_arr) if want.get(name) else 0
-            outs.append(np.empty(cnt, dtype=dtype))
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
     fn = getattr(lib, "rm_calc_metrics_scores_" + _suffix(dtype))
     rc = fn(_p(S), lds, m, n, _p(train_p), _p(train_i), _p(test_p), _p(test_i), _p(test_v),
             k_metrics, int(bool(cumulative)), *[_p(o) for o in outs],
             int(bool(consider_cold_start)), min_items_pool, min_pos_test, nthreads)
     if rc:
         _raise(lib, rc)
-    if cumulative:
-        outs = [(o.reshape((m, k_metrics)) if o.size else o.reshape((0, 0))) if i < 8 else o for i, o in enumerate(outs)]
-    return tuple(outs)
+    return outs
 
 
 def calc_metrics_scores_device(dtype, S, lds, m, n, train_p, train_i, nnz_train, test_p, test_i, test_v, nnz_test,
@@ -306,12 +311,9 @@ def calc_metrics_scores_device(dtype, S, lds, m, n, train_p, train_i, nnz_train,
     `outs` is a sequence of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
     lib = load()
     fn = getattr(lib, "rm_calc_metrics_scores_dev_" + _suffix(dtype))
-
-    def vp(x):
-        return C.c_void_p(int(x)) if x else None
-    rc = fn(vp(S), lds, m, n, vp(train_p), vp(train_i), nnz_train, vp(test_p), vp(test_i), vp(test_v), nnz_test,
-            k_metrics, int(bool(cumulative)), *[vp(o) for o in outs],
-            int(bool(consider_cold_start)), min_items_pool, min_pos_test, vp(stream))
+    rc = fn(_dp(S), lds, m, n, _dp(train_p), _dp(train_i), nnz_train, _dp(test_p), _dp(test_i), _dp(test_v), nnz_test,
+            k_metrics, int(bool(cumulative)), *[_dp(o) for o in outs],
+            int(bool(consider_cold_start)), min_items_pool, min_pos_test, _dp(stream))
     if rc:
         _raise(lib, rc)
 
@@ -322,10 +324,8 @@ def rank(A, B, train_p, train_i, test_p, test_i, k_metrics, break_ties_with_nois
     dtype = A.dtype.type
     m, k = A.shape
     n = B.shape[0]
-    idx = np.empty((m, k_metrics), dtype=np.int32)
-    sc = np.empty((m, k_metrics), dtype=dtype)
+    idx, sc, st = _list_outs(m, k_metrics, dtype)
     pr = np.zeros(max(int(test_i.shape[0]), 1), dtype=np.int64)
-    st = np.empty(m, dtype=np.int32)
     fn = getattr(lib, "rm_rank_" + _suffix(dtype))
     A = np.ascontiguousarray(A)                  # the raw pointer is passed with lda = k: rows must be dense
     B = np.ascontiguousarray(B)
@@ -345,9 +345,7 @@ def recommend(A, lda, B, ldb, excl_p, excl_i, k_top, return_scores=True, nthread
     dtype = A.dtype.type
     m, k = A.shape
     n = B.shape[0]
-    idx = np.empty((m, k_top), dtype=np.int32)
-    sc = np.empty((m, k_top), dtype=dtype) if return_scores else None
-    st = np.empty(m, dtype=np.int32)
+    idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
     fn = getattr(lib, "rm_recommend_" + _suffix(dtype))
     rc = fn(_p(A), lda, _p(B), ldb, m, n, k, None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p), _p(excl_i), k_top,
             _p(idx), _p(sc), _p(st), int(nthreads))
@@ -361,10 +359,7 @@ def recommend_device(dtype, A, lda, B, ldb, m, n, k, excl_p, excl_i, nnz_excl, k
     is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
     lib = load()
     fn = getattr(lib, "rm_recommend_dev_" + _suffix(dtype))
-
-    def vp(x):
-        return C.c_void_p(int(x)) if x else None
-    rc = fn(vp(A), lda, vp(B), ldb, m, n, k, vp(excl_p), vp(excl_i), nnz_excl, k_top, vp(idx), vp(score), vp(status), vp(stream))
+    rc = fn(_dp(A), lda, _dp(B), ldb, m, n, k, _dp(excl_p), _dp(excl_i), nnz_excl, k_top, _dp(idx), _dp(score), _dp(status), _dp(stream))
     if rc:
         _raise(lib, rc)
 
@@ -375,9 +370,7 @@ def recommend_scores(S, lds, excl_p, excl_i, k_top, return_scores=True, nthreads
     lib = load()
     dtype = S.dtype.type
     m, n = S.shape
-    idx = np.empty((m, k_top), dtype=np.int32)
-    sc = np.empty((m, k_top), dtype=dtype) if return_scores else None
-    st = np.empty(m, dtype=np.int32)
+    idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
     fn = getattr(lib, "rm_recommend_scores_" + _suffix(dtype))
     rc = fn(_p(S), lds, m, n, None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p), _p(excl_i), k_top,
             _p(idx), _p(sc), _p(st), int(nthreads))
@@ -391,10 +384,7 @@ def recommend_scores_device(dtype, S, lds, m, n, excl_p, excl_i, nnz_excl, k_top
     nothing is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
     lib = load()
     fn = getattr(lib, "rm_recommend_scores_dev_" + _suffix(dtype))
-
-    def vp(x):
-        return C.c_void_p(int(x)) if x else None
-    rc = fn(vp(S), lds, m, n, vp(excl_p), vp(excl_i), nnz_excl, k_top, vp(idx), vp(score), vp(status), vp(stream))
+    rc = fn(_dp(S), lds, m, n, _dp(excl_p), _dp(excl_i), nnz_excl, k_top, _dp(idx), _dp(score), _dp(status), _dp(stream))
     if rc:
         _raise(lib, rc)
 

@@ -302,25 +302,42 @@ Ctx &peer_context(const Ctx &cx, int offset = PEER_SLOT)
     return *p;
 }
 
-template <class T> struct Call {          // one calc_metrics call; every pointer is a DEVICE pointer
-    const T *A; size_t lda; const T *B; size_t ldb;
-    int m, n, k;
-    const int *train_p, *train_i; long long nnz_train;
-    const int *test_p, *test_i; const T *test_v; long long nnz_test;
-    int K; bool cumulative, noise;
-    T *out[10];                            // p, tp, r, ap, tap, ndcg, hit, rr, roc, pr
-    bool cold; int min_items_pool, min_pos_test;
-    // optional ranking outputs (device)
-    int *topk_idx; T *topk_score; long long *pos_rank; int *status;
+// What a caller asked for: one metric or list call as the C-ABI states it.  Its pointers are HOST pointers in a host entry (HostRange
+// stages the arrays batch by batch) and DEVICE pointers in a device entry and in every Call.
+template <class T> struct Request {
+    // the score source: factors, or the caller's score matrix (rm_calc_metrics_scores_*, rm_recommend_scores_*): score of item i for user u =
+    // S[u * lds + i]; there are then no factors (A, B null, k = 0) and no tie noise.  Every evaluated user is streamed: k_score_rows copies
+    // its row of S, masked, where the sweep would have written it, k_pos_scores_given gathers the test items' scores, and the
+    // finalisation is the factor call's.
+    const T *A = nullptr; size_t lda = 0; const T *B = nullptr; size_t ldb = 0; int k = 0;
+    const T *S = nullptr; size_t lds = 0; bool scores = false;
+    int m = 0, n = 0;
+    const int *train_p = nullptr, *train_i = nullptr; long long nnz_train = 0;       // (lists: the exclusion matrix)
+    const int *test_p = nullptr, *test_i = nullptr; const T *test_v = nullptr; long long nnz_test = 0;
+    int K = 0; bool cumulative = false, noise = false, cold = false; int min_items_pool = 0, min_pos_test = 0;
+    unsigned long long seed = 0;               // tie noise (rm_noise.hpp): the engine of user u of the request is seeded with seed + u
+    // The outputs.  In a host request they are the caller's HOST arrays: HostRange::batch_call resets every one of them in the device call
+    // it makes of the request -- an output added here must be reset there too.
+    T *out[10] = {};                           // p, tp, r, ap, tap, ndcg, hit, rr, roc, pr
+    // optional ranking outputs
+    int *topk_idx = nullptr; T *topk_score = nullptr; long long *pos_rank = nullptr; int *status = nullptr;
+    // recommendation lists (rm_recommend_*): no test matrix (`test_p` is null on the device), no metric; every user with a candidate gets its
+    // ordered list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
+    bool reco = false;
+};
+// one pass over the users of a request, or over a batch of them: the request (every pointer a DEVICE pointer) and the state of the pass
+template <class T> struct Call : Request<T> {
+    Call() = default;
+    explicit Call(const Request<T> &r) : Request<T>(r) {}
     // batches of one host call share the item factors: a non-zero tag says "the packed image and the |B| bound made for this
     // tag are still valid" (set by run_host_range; 0 = always repack)
-    unsigned long long items_tag;
+    unsigned long long items_tag = 0;
     // tie noise (rm_noise.hpp)
-    unsigned long long seed; long long user0;      // the engine of local user u is seeded with seed + user0 + u
-    const unsigned char *only_users;               // optional [m]: evaluate only these users, leave the others' outputs alone
-    const int *noise_row; int noise_row0;          // row of each user in noise_E (null: row = user)
-    const T *noise_E; long long noise_ld;          // per-item noise rows; null = scores as they are
-    int *noise_flag;                               // optional [m] out (fp32 first pass): users the noise can change
+    long long user0 = 0;                           // the engine of local user u is seeded with seed + user0 + u
+    const unsigned char *only_users = nullptr;     // optional [m]: evaluate only these users, leave the others' outputs alone
+    const int *noise_row = nullptr; int noise_row0 = 0;      // row of each user in noise_E (null: row = user)
+    const T *noise_E = nullptr; long long noise_ld = 0;      // per-item noise rows; null = scores as they are
+    int *noise_flag = nullptr;                     // optional [m] out (fp32 first pass): users the noise can change
     bool same_train_rows = false;                  // a later pass of the same call over the same users' rows: dense train rows may be reused
     long long eval_users = -1;                     // users this pass evaluates when fewer than m (only_users given); -1 = all m
     // fp32 tie noise, first pass: right before the sweep is launched the flags set so far (users with a TEST item in the noise
@@ -339,13 +356,6 @@ template <class T> struct Call {          // one calc_metrics call; every pointe
     // dense train rows: decided once per call (-1 = not yet: run() asks dense_rows_fit itself) -- every pass of a call gets the
     // answer the first one got, whatever the passes in between have allocated
     int dense_fit = -1;
-    // recommendation lists (rm_recommend_*): no test matrix (`test_p` is null), no metric; every user with a candidate gets its ordered
-    // list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
-    bool reco = false;
-    // metrics from the caller's score matrix (rm_calc_metrics_scores_*): score of item i for user u = S[u * lds + i]; there are no
-    // factors (A, B null, k = 0), no tie noise.  Every evaluated user is streamed: k_score_rows copies its row of S, masked, where the
-    // sweep would have written it, k_pos_scores_given gathers the test items' scores, and the finalisation is the factor call's.
-    bool scores = false; const T *S = nullptr; size_t lds = 0;
 };
 // Layout of the ten metrics of a call (Call::out): the eight top-K metrics have `per` values per user (k_metrics when cumulative,
 // else one), the two AUCs one.  The requested metrics of one user, packed, are a RECORD (what k_noise_gather writes); those of
@@ -506,6 +516,8 @@ inline long long free_plus_owned(const Workspace &ws, std::initializer_list<cons
     for (const char *nm : names) { auto it = ws.bufs.find(nm); if (it != ws.bufs.end()) owned += (long long)it->second.bytes; }
     return (long long)fr + owned;
 }
+// elements between two stored score rows of n items (stream_scores, the tie noise's rows): whole tiles of either size of the sweep (64 / 96 items)
+inline long long score_row_stride(long long n) { return (n + 191) / 192 * 192; }
 inline long long stream_budget_bytes(const Workspace &ws)
 {
     if (g_sw.stream_budget_mb >= 0) return g_sw.stream_budget_mb << 20;
@@ -547,7 +559,7 @@ template <class T> inline bool lane_lists_fit(const Workspace &ws, int K, long l
 // the CSR cursor (compare, consume, reload, loop) was 9 % of the C2 sweep; one word per lane and tile replaces it.
 // (rows are padded to 192 items = a whole tile of either size, 64 or 96: the row stride does not depend on the sweep's geometry,
 // which is only known behind the plan read-back -- the rows are built before it, beside the plan kernels)
-inline long long dense_row_words(long long n) { return (n + 191) / 192 * 6; }
+inline long long dense_row_words(long long n) { return score_row_stride(n) / 32; }
 // Up to 1 GiB of rows always; beyond that (many users at a small item count: 1M users x 27k items = 3.4 GB) when they take no more
 // than a quarter of the HBM that is free -- what the workspace already holds of the rows and of the streamed users' score rows counts
 // as free, so that equal calls get equal answers -- and no more than 8 GiB: the sweep indexes the rows by 32-bit word offsets.
@@ -964,7 +976,7 @@ struct Pipeline {
         // users then take one sweep slot per chunk of their test row -- same results, the contraction repeated per chunk).
         // The plan assumes they fit; the host looks at their number in the read-back and, should the rows not fit, plans once more
         // without streaming (what used to be two launches in front of k_classify -- count, decide -- on every call).
-        const long long stream_ld_max = ((long long)n + 191) / 192 * 192;             // row stride for either tile size (64 / 96 items)
+        const long long stream_ld_max = score_row_stride(n);
         // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
         // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
         want_lane = !c.scores && lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
@@ -1690,7 +1702,7 @@ template <class T> struct NoiseGeom {
     NoiseGeom(const Workspace &ws, int n)
     {
         per = sizeof(T) == 4 ? 1 : 2;
-        e_ld = ((long long)n + 191) / 192 * 192;                                  // covers either tile size of the sweep
+        e_ld = score_row_stride(n);
         d_ld = ((long long)n * per + MT_N - 1) / MT_N * MT_N;
         const long long row_bytes = e_ld * (long long)sizeof(T) + d_ld * 4;
         long long budget;
@@ -1990,20 +2002,6 @@ struct SignalGuard {
 std::mutex g_dev_mu;
 std::vector<int> g_devices;
 
-template <class T> struct HostCall {              // one host-pointer call (reference signature, src/recometrics_signatures.hpp:48-98)
-    const T *A; size_t lda; const T *B; size_t ldb; int m, n, k;
-    const int *trp, *tri, *tep, *tei; const T *tev;
-    int K; bool cumulative, noise; T *outs[10]; bool cold; int mip, mpt;
-    int *topk_idx; T *topk_score; long long *pos_rank; int *status;
-    unsigned long long seed;
-    int nthreads = 0;                                 // host threads of the fall-back sort of unsorted CSR rows (0 = all)
-    // rm_recommend_*: `tep` is a row of zeros the entry made up (host-side bookkeeping only: nothing of a test matrix reaches the
-    // device), `topk_idx` / `topk_score` (optional) / `status` are the caller's idx / score / status, `pos_rank` is null
-    bool reco = false;
-    // rm_calc_metrics_scores_*: the caller's score matrix instead of factors (A, B null, k = 0); its rows travel batch by batch
-    bool scores = false; const T *S = nullptr; size_t lds = 0;
-};
-
 // item factors of a sharded call: uploaded from the host by shard 0, copied device-to-device (xGMI) by the others
 struct SharedItems {
     std::mutex mu; std::condition_variable cv;
@@ -2056,7 +2054,7 @@ inline void print_host_trace(int n_batches, const std::vector<std::pair<const ch
 template <class T> long long batch_users_max(const Workspace &ws, int n, int k, int K, bool scores = false)
 {
     if (scores) {
-        const long long row = (((long long)n + 191) / 192 * 192) * (long long)sizeof(T);
+        const long long row = score_row_stride(n) * (long long)sizeof(T);
         long long batch = free_plus_owned(ws, {"stream_scores", "sel_hi", "sel_lo", "in_S0", "in_S1"}) / (7 * row);
         if (g_sw.stream_budget_mb >= 0) batch = std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row);
         if (g_sw.batch_users > 0) batch = std::min<long long>(batch, (long long)g_sw.batch_users);
@@ -2072,7 +2070,7 @@ template <class T> long long batch_users_max(const Workspace &ws, int n, int k, 
     const long long lane_blocks = K > 256 && lane_lists_possible<T>(K) ? lane_budget_bytes(ws) * 3 / 4 / lane_list_bytes<T>(K, 1) - lane_blocks_bound<T>(0) : 0;
     if (lane_blocks >= 8) batch = std::max<long long>(1024, std::min<long long>(batch, lane_blocks * 4 * Prec<T>::GU / 1024 * 1024));
     else if (K > 256) {                                            // one score row per user of the batch (run(): ext_topk),
-        const long long row = (((long long)n + 191) / 192 * 192) * (long long)sizeof(T);    // with a margin for what run() allocates first
+        const long long row = score_row_stride(n) * (long long)sizeof(T);    // with a margin for what run() allocates first
         batch = std::max<long long>(1, std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row));
     }
     return batch;
@@ -2104,7 +2102,7 @@ inline std::vector<long long> batch_cuts(long long m, long long batch, bool forc
 // Whatever happens, the other shards must neither wait for item factors that never come nor copy from a buffer that is being
 // reused: the destructor has shard 0 publish (possibly a failure) and then wait for every copy, and the others report theirs.
 template <class T> struct ItemUpload {
-    const HostCall<T> &h; SharedItems *sh; int shard; bool published = false, reported = false;
+    const Request<T> &h; SharedItems *sh; int shard; bool published = false, reported = false;
     ~ItemUpload()
     {
         if (!sh) return;
@@ -2170,7 +2168,7 @@ template <class T> struct HostRange {
     NoiseBeside<T> bes;
     bool bes_ran = false; int bes_count = 0; T *bes_hx = nullptr; int *bes_hu = nullptr;     // what the pass beside the last batch left in page-locked memory
 
-    const HostCall<T> &h; const int u0, m, n, k, K; Ctx &cx; Workspace &ws; hipStream_t stream, up = nullptr;
+    const Request<T> &h; const int u0, m, n, k, K; Ctx &cx; Workspace &ws; hipStream_t stream, up = nullptr;
     SharedItems *shared; int shard; unsigned long long tag;
     const MetricLayout lay;                                           // (per: values per user of the eight top-K metrics)
     // stage_inputs()
@@ -2193,9 +2191,9 @@ template <class T> struct HostRange {
     std::vector<std::pair<const char *, double>> stamps; std::chrono::steady_clock::time_point t_start;
     void stamp(const char *what) { if (g_sw.host_trace) stamps.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count()); }
 
-    HostRange(const HostCall<T> &h_, int u0_, int u1, Ctx &cx_, hipStream_t stream_, SharedItems *shared_, int shard_, unsigned long long tag_)
+    HostRange(const Request<T> &h_, int u0_, int u1, Ctx &cx_, hipStream_t stream_, SharedItems *shared_, int shard_, unsigned long long tag_)
         : lk(cx_.mu), items{h_, shared_, shard_}, bes(cx_), h(h_), u0(u0_), m(u1 - u0_), n(h_.n), k(h_.k), K(h_.K), cx(cx_), ws(cx_.ws), stream(stream_),
-          shared(shared_), shard(shard_), tag(tag_), lay(h_.outs, h_.cumulative ? (size_t)h_.K : 1), ctxs{&cx_, &cx_}, streams{stream_, stream_}
+          shared(shared_), shard(shard_), tag(tag_), lay(h_.out, h_.cumulative ? (size_t)h_.K : 1), ctxs{&cx_, &cx_}, streams{stream_, stream_}
     {
         cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0; cx.ev_recorded = false;
         g_last_ctx = &cx;
@@ -2214,18 +2212,18 @@ template <class T> struct HostRange {
         dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
         if (m <= 0) { items.run(dB, cx.device, up); HIP_CHECK(hipStreamSynchronize(up)); return false; }
         // this range's users: factors, CSR rows with the index pointers rebased to the range
-        tr0 = h.trp[u0]; te0 = h.tep[u0];
-        nnz_tr = (long long)h.trp[u0 + m] - tr0; nnz_te = (long long)h.tep[u0 + m] - te0;
+        tr0 = h.train_p[u0]; te0 = h.test_p[u0];
+        nnz_tr = (long long)h.train_p[u0 + m] - tr0; nnz_te = (long long)h.test_p[u0 + m] - te0;
         dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
         dtrp = (int *)ws.get("in_trp", sizeof(int) * (size_t)(m + 1));
         dtep = h.reco ? nullptr : (int *)ws.get("in_tep", sizeof(int) * (size_t)(m + 1));
         dtri = (int *)ws.get("in_tri", sizeof(int) * (size_t)std::max<long long>(nnz_tr, 1));
         dtei = (int *)ws.get("in_tei", sizeof(int) * (size_t)std::max<long long>(nnz_te, 1));
-        dtev = h.tev ? (T *)ws.get("in_tev", sizeof(T) * (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
-        trp = h.trp + u0; tep = h.tep + u0;
+        dtev = h.test_v ? (T *)ws.get("in_tev", sizeof(T) * (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
+        trp = h.train_p + u0; tep = h.test_p + u0;
         if (tr0 || te0) {
             rb.resize(2 * (size_t)(m + 1));
-            for (int i = 0; i <= m; i++) { rb[i] = h.trp[u0 + i] - (int)tr0; rb[m + 1 + i] = h.tep[u0 + i] - (int)te0; }
+            for (int i = 0; i <= m; i++) { rb[i] = h.train_p[u0 + i] - (int)tr0; rb[m + 1 + i] = h.test_p[u0 + i] - (int)te0; }
             trp = rb.data(); tep = rb.data() + m + 1;
         }
         HIP_CHECK(hipMemcpyAsync(dtrp, trp, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
@@ -2298,9 +2296,9 @@ template <class T> struct HostRange {
         else HIP_CHECK(hipMemcpy2DAsync(dA + (size_t)b0 * k, sizeof(T) * k, h.A + ((size_t)u0 + b0) * h.lda, sizeof(T) * h.lda, sizeof(T) * k, (size_t)(b1 - b0),
                                         hipMemcpyHostToDevice, up));
         const long long r0 = trp[b0], r1 = trp[b1], e0 = tep[b0], e1 = tep[b1];      // range-relative entries of the batch
-        if (r1 > r0) HIP_CHECK(hipMemcpyAsync(dtri + r0, h.tri + tr0 + r0, sizeof(int) * (size_t)(r1 - r0), hipMemcpyHostToDevice, up));
-        if (e1 > e0) HIP_CHECK(hipMemcpyAsync(dtei + e0, h.tei + te0 + e0, sizeof(int) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
-        if (dtev && e1 > e0) HIP_CHECK(hipMemcpyAsync(dtev + e0, h.tev + te0 + e0, sizeof(T) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
+        if (r1 > r0) HIP_CHECK(hipMemcpyAsync(dtri + r0, h.train_i + tr0 + r0, sizeof(int) * (size_t)(r1 - r0), hipMemcpyHostToDevice, up));
+        if (e1 > e0) HIP_CHECK(hipMemcpyAsync(dtei + e0, h.test_i + te0 + e0, sizeof(int) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
+        if (dtev && e1 > e0) HIP_CHECK(hipMemcpyAsync(dtev + e0, h.test_v + te0 + e0, sizeof(T) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
         HIP_CHECK(hipEventRecord(cx.up_ev[bi & 1], up));
     }
     // shard 0 sends the item factors first (the other shards are waiting for them); the others send their own rows first
@@ -2312,17 +2310,17 @@ template <class T> struct HostRange {
         else { upload_users(0); items.run(dB, cx.device, up); HIP_CHECK(hipEventRecord(cx.up_ev[0], up)); }
         stamp("batch 0 rows enqueued");
     }
-    // users [b0, b0 + mb) of the range as a call on the staged arrays: everything but the outputs and the tie noise's flags
+    // users [b0, b0 + mb) of the range as a call on the staged arrays: the request, rebased -- everything but the outputs (the request's
+    // are the caller's host arrays: enqueue_batch and exact_block point a call at device arrays of its own) and the tie noise's flags
     Call<T> batch_call(long long b0, int mb) const
     {
-        Call<T> c{};
-        c.A = dA + (size_t)b0 * k; c.lda = k; c.B = dB; c.ldb = k; c.m = mb; c.n = n; c.k = k;
+        Call<T> c(h);
+        c.A = dA + (size_t)b0 * k; c.lda = k; c.B = dB; c.ldb = k; c.m = mb;
+        if (h.scores) { c.S = cur_S; c.lds = (size_t)n; c.A = nullptr; c.B = nullptr; }
         c.train_p = dtrp + b0; c.train_i = dtri; c.nnz_train = nnz_tr;
         c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
-        c.K = K; c.cumulative = h.cumulative; c.noise = h.noise; c.cold = h.cold; c.min_items_pool = h.mip; c.min_pos_test = h.mpt;
-        c.reco = h.reco;
-        if (h.scores) { c.scores = true; c.S = cur_S; c.lds = (size_t)n; c.A = nullptr; c.B = nullptr; }
-        c.items_tag = tag; c.seed = h.seed; c.user0 = (long long)u0 + b0;
+        std::fill_n(c.out, 10, nullptr); c.topk_idx = nullptr; c.topk_score = nullptr; c.pos_rank = nullptr; c.status = nullptr;
+        c.items_tag = tag; c.user0 = (long long)u0 + b0;
         return c;
     }
     // the device-to-host copies of the batch in flight on context `which`, enqueued behind the batch and once more when its tail
@@ -2353,7 +2351,7 @@ template <class T> struct HostRange {
         HIP_CHECK(hipStreamSynchronize(streams[which]));
         stamp("batch done");
         for (int i = 0; i < 10; i++)
-            if (lay.want[i]) std::memcpy(h.outs[i] + ((size_t)u0 + f.b0) * lay.width(i), hblocks[which] + lay.block_off(i, (size_t)f.mb), sizeof(T) * (size_t)f.mb * lay.width(i));
+            if (lay.want[i]) std::memcpy(h.out[i] + ((size_t)u0 + f.b0) * lay.width(i), hblocks[which] + lay.block_off(i, (size_t)f.mb), sizeof(T) * (size_t)f.mb * lay.width(i));
         stamp("outputs scattered");
         users_copied = std::max<long long>(users_copied, f.b0 + f.mb);
         if (range_noise) flagged_total += ctxs[which]->noise_words->batch_flagged;
@@ -2426,7 +2424,7 @@ template <class T> struct HostRange {
     {
         for (int f = 0; f < count; f++)
             for (int i = 0; i < 10; i++)
-                if (lay.want[i]) std::memcpy(h.outs[i] + ((size_t)u0 + hu[f]) * lay.width(i), hx + (size_t)f * lay.rec_w + lay.rec_off[i], sizeof(T) * lay.width(i));
+                if (lay.want[i]) std::memcpy(h.out[i] + ((size_t)u0 + hu[f]) * lay.width(i), hx + (size_t)f * lay.rec_w + lay.rec_off[i], sizeof(T) * lay.width(i));
     }
     // the exact pass beside the last batch's sweep, on the NOISE_SLOT context and its stream: flags as they stand once the last batch
     // has scored its positives, noise rows for those users (from dense train rows built for them alone), the pipeline for them,
@@ -2491,7 +2489,7 @@ template <class T> struct HostRange {
         for (long long u = 0; u < users_copied; u++) {
             if (!hf[(size_t)u]) continue;
             for (int i = 0; i < 10; i++)
-                if (lay.want[i]) std::fill_n(h.outs[i] + ((size_t)u0 + (size_t)u) * lay.width(i), lay.width(i), std::numeric_limits<T>::quiet_NaN());
+                if (lay.want[i]) std::fill_n(h.out[i] + ((size_t)u0 + (size_t)u) * lay.width(i), lay.width(i), std::numeric_limits<T>::quiet_NaN());
         }
     }
     void drain()                                                      // a failure: nothing may still write into staging that goes away
@@ -2504,7 +2502,7 @@ template <class T> struct HostRange {
 };
 
 template <class T>
-void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t stream, SharedItems *shared, int shard, unsigned long long tag)
+void run_host_range(const Request<T> &h, int u0, int u1, Ctx &cx, hipStream_t stream, SharedItems *shared, int shard, unsigned long long tag)
 {
     HostRange<T> r(h, u0, u1, cx, stream, shared, shard, tag);
     if (!r.stage_inputs()) return;
@@ -2526,53 +2524,85 @@ void run_host_range(const HostCall<T> &h, int u0, int u1, Ctx &cx, hipStream_t s
     if (g_sw.host_trace) print_host_trace(r.n_batches, r.stamps);
 }
 
-// (m == 0 is not an error: the reference's loop over users, src/recometrics.hpp:428-437, simply does not run; the entry
-// points return RM_OK before they get here.  `tei` may be null when there is no test entry at all -- every user is then NaN,
-// as in the reference -- which is what a binding hands over for an empty index array.)
+// ---- what is wrong with a request: decided once per entry, on the host, before any device is asked for ---------------------------------
+// (m == 0 is not an error: the reference's loop over users, src/recometrics.hpp:428-437, simply does not run; the entries return RM_OK
+// before they get here.  `test_i` may be null when there is no test entry at all -- every user is then NaN, as in the reference --
+// which is what a binding hands over for an empty index array.)
+// `host`: the host form also looks at the index pointers themselves -- they say how much of the caller's index arrays is read at all
+// (2 (m + 1) integers, before anything is sized or copied by them), and the lengths of those arrays are read from them -- but only once
+// the arrays it reads are known not to be null.  The indices are validated on the device (run()).
+// Codes, texts and WHICH message a caller gets when several apply are the entries' behaviour (tests/golden/api/entry_errors.json), the
+// differences between the entries included.  Where the order differs for no reason it is kept and marked (*).
 template <class T>
-void validate(const T *A, const T *B, int m, int n, int k, const int *trp, const int *tep, const int *tei, long long nnz_test, int K, size_t lda, size_t ldb)
+void check_request(const Request<T> &r, bool host)
 {
-    if (!A || !B || !trp || !tep || (!tei && nnz_test > 0)) throw RmError{RM_ERR_INVALID, "null input pointer"};
-    if (m <= 0 || n <= 0 || k <= 0) throw RmError{RM_ERR_INVALID, "m, n, k must be positive"};
-    if (K <= 0) throw RmError{RM_ERR_INVALID, "k_metrics must be positive"};
-    if (lda < (size_t)k || ldb < (size_t)k) throw RmError{RM_ERR_INVALID, "leading dimension smaller than k"};
-}
-
-// rm_calc_metrics_scores_*: what is decided on the host before any device work (m == 0 has returned RM_OK by then)
-template <class T>
-void validate_scores(const T *S, size_t lds, int m, int n, int K, const int *trp, const int *tep, const int *tei, long long nnz_test, const void *ndcg, const void *test_v)
-{
-    if (m < 0 || n <= 0) throw RmError{RM_ERR_INVALID, "m must not be negative and n must be positive"};
-    if (!S || !trp || !tep || (!tei && nnz_test > 0)) throw RmError{RM_ERR_INVALID, "null input pointer"};
-    if (lds < (size_t)n) throw RmError{RM_ERR_INVALID, "leading dimension of the score matrix smaller than n (got " + std::to_string(lds) + " with " + std::to_string(n) + " items)"};
-    if (K < 1 || K > n) throw RmError{RM_ERR_INVALID, "k_metrics must lie in [1, n] (got " + std::to_string(K) + " with " + std::to_string(n) + " items)"};
-    if (ndcg && !test_v) throw RmError{RM_ERR_INVALID, "NDCG requested without test values"};
-}
-
-// host-pointer entry: one device (the calling thread's current one), or the devices of rm_set_devices with contiguous user
-// ranges [m g / G, m (g + 1) / G), one host thread + stream + workspace per shard, no exchange between the shards
-template <class T>
-void run_host_once(const HostCall<T> &h)
-{
-    if (h.m == 0) return;                                            // reference :428-437: no user, nothing written
-    if (h.m < 0 || !h.tep) throw RmError{RM_ERR_INVALID, h.m < 0 ? "m, n, k must be positive" : "null input pointer"};
-    if (h.scores) validate_scores(h.S, h.lds, h.m, h.n, h.K, h.trp, h.tep, h.tei, (long long)h.tep[h.m], h.outs[5], h.tev);
-    else validate(h.A, h.B, h.m, h.n, h.k, h.trp, h.tep, h.tei, (long long)h.tep[h.m], h.K, h.lda, h.ldb);
-    // the index pointers say how much of the caller's index arrays is read at all: they are looked at here, on the host (2 (m + 1)
-    // integers), before anything is sized or copied by them; the indices themselves are validated on the device (run())
-    for (const int *p : {h.trp, h.tep}) {
-        int bad = p[0] < 0;
-        for (int u = 0; u < h.m; u++) bad |= p[u + 1] < p[u];
-        if (bad) {
-            int u = 0;
-            while (u < h.m && !(p[u] < 0 || p[u + 1] < p[u])) u++;
-            throw RmError{RM_ERR_INVALID, std::string("CSR index pointers of row ") + std::to_string(u) + " are negative or decreasing (" + (p == h.trp ? "X_train" : "X_test") + ")"};
-        }
-    }
-    if (h.trp[h.m] > 0 && !h.tri) throw RmError{RM_ERR_INVALID, "null train indices"};
+    const auto fail = [](const std::string &msg) { throw RmError{RM_ERR_INVALID, msg}; };
+    const char *null_in = "null input pointer", *mnk = "m, n, k must be positive", *mn = "m must not be negative and n must be positive";
+    const std::string of_n = " with " + std::to_string(r.n) + " items)";
+    const auto ld_covers_k = [&] { if (r.lda < (size_t)r.k || r.ldb < (size_t)r.k) fail("leading dimension smaller than k"); };
+    const auto lds_covers_n = [&] {
+        if (r.lds < (size_t)r.n) fail("leading dimension of the score matrix smaller than n (got " + std::to_string(r.lds) + of_n);
+    };
+    const auto K_in_1_n = [&](const char *name) {
+        if (r.K < 1 || r.K > r.n) fail(std::string(name) + " must lie in [1, n] (got " + std::to_string(r.K) + of_n);
+    };
+    // the length of the test index array (read only behind the null check of `test_p`; the host form has looked at m by then)
+    const auto nnz_test = [&] { return host ? (long long)r.test_p[r.m] : r.nnz_test; };
     // (deviation D8: the reference's walk would use gain 0 for a null Xtest_csr, :620, but its normalisation dereferences
     // the pointer, :870-874 -- a crash there, an error here)
-    if (h.outs[5] && !h.tev) throw RmError{RM_ERR_INVALID, "NDCG requested without test values"};
+    const auto ndcg_has_values = [&] { if (r.out[5] && !r.test_v) fail("NDCG requested without test values"); };
+    // host form (a null array: lists have no test matrix and need no exclusion matrix)
+    const auto index_pointers = [&] {
+        for (const int *p : {r.train_p, r.test_p}) {
+            if (!p) continue;
+            int bad = p[0] < 0;
+            for (int u = 0; u < r.m; u++) bad |= p[u + 1] < p[u];
+            if (bad) {
+                int u = 0;
+                while (u < r.m && !(p[u] < 0 || p[u + 1] < p[u])) u++;
+                fail(std::string("CSR index pointers of row ") + std::to_string(u) + " are negative or decreasing ("
+                     + (p == r.train_p ? "X_train" : "X_test") + ")");
+            }
+        }
+        if (r.train_p && r.train_p[r.m] > 0 && !r.train_i) fail("null train indices");
+    };
+    if (r.reco) {                                                    // lists, from factors or from scores
+        if (r.m < 0 || r.n <= 0 || (!r.scores && r.k <= 0)) fail(r.scores ? mn : mnk);
+        if (r.scores ? !r.S : (!r.A || !r.B)) fail(null_in);
+        if (!r.topk_idx || !r.status) fail("null output pointer");
+        if (r.scores) { lds_covers_n(); K_in_1_n("k_top"); }
+        else { K_in_1_n("k_top"); ld_covers_k(); }                   // (*) the list length in front of the leading dimensions
+        // (device form: the two entries used to ask these two in opposite orders; nnz < 0 and nnz > 0 exclude each other, so one order serves both)
+        if (host) index_pointers();
+        else if (r.nnz_train < 0) fail("negative length of the index array");
+        else if (r.train_p && r.nnz_train > 0 && !r.train_i) fail(null_in);
+        return;
+    }
+    if (r.scores) {                                                  // metrics from scores
+        if (r.m < 0 || r.n <= 0) fail(mn);
+        if (!r.S || !r.train_p || !r.test_p || (!r.test_i && nnz_test() > 0)) fail(null_in);
+        lds_covers_n(); K_in_1_n("k_metrics"); ndcg_has_values();
+        if (host) index_pointers();
+        else if (r.nnz_train < 0 || r.nnz_test < 0) fail("negative length of an index array");
+        else if (r.nnz_train > 0 && !r.train_i) fail("null train indices");
+        return;
+    }
+    // metrics from factors, rm_rank_*.  (*) The host form names a negative m in front of a null pointer, the device form behind it; and
+    // the device form leaves the lengths and a null train index array to the device's own checks of the CSR arrays.
+    if (host && r.m < 0) fail(mnk);
+    if (!r.A || !r.B || !r.train_p || !r.test_p || (!r.test_i && nnz_test() > 0)) fail(null_in);
+    if (r.m <= 0 || r.n <= 0 || r.k <= 0) fail(mnk);
+    if (r.K <= 0) fail("k_metrics must be positive");
+    ld_covers_k();
+    if (host) index_pointers();
+    ndcg_has_values();
+}
+
+// a host-pointer request that has passed check_request: one device (the calling thread's current one), or the devices of rm_set_devices with
+// contiguous user ranges [m g / G, m (g + 1) / G), one host thread + stream + workspace per shard, no exchange between the shards
+template <class T>
+void run_host_once(const Request<T> &h)
+{
     std::vector<int> devs;
     { std::lock_guard<std::mutex> lk(g_dev_mu); devs = g_devices; }
     const unsigned long long tag = g_call_counter.fetch_add(1);
@@ -2628,30 +2658,48 @@ void run_host_once(const HostCall<T> &h)
 // thread walking every entry: 26-33 ms at BASELINE C2); here the rows are uploaded as they come and validated on the device (run():
 // k_check_csr_*, ~40 us).  Only when some row turns out unsorted is a copy of the index / value arrays sorted on the host
 // (csrc/rm_csr.cpp, multi-threaded, stable like SciPy's) and the call run again on the copy -- the caller's arrays are const.
+// Recommendation lists have no test matrix: a row of zeros stands for its index pointers in the host-side bookkeeping of the batches
+// (nothing of it reaches the device), and for the exclusion matrix's when there is none.
 template <class T>
-void run_host(const HostCall<T> &h)
+void run_host(Request<T> h, int nthreads)
 {
+    std::vector<int> zeros;
+    if (h.reco) {
+        zeros.assign((size_t)h.m + 1, 0);
+        h.test_p = zeros.data();
+        if (!h.train_p) h.train_p = zeros.data();
+    }
+    h.nnz_train = h.train_p[h.m]; h.nnz_test = h.test_p[h.m];
     try { run_host_once<T>(h); return; }
     catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; }
     if (h.topk_idx && !h.reco) throw RmError{RM_ERR_INVALID, "rm_rank_*: the CSR rows must be sorted (pos_rank is indexed by the caller's entry order)"};
-    const size_t nnz_tr = (size_t)h.trp[h.m], nnz_te = (size_t)h.tep[h.m];
-    std::vector<int> tri(h.tri, h.tri + nnz_tr), tei(h.tei, h.tei + nnz_te);
+    std::vector<int> tri(h.train_i, h.train_i + h.nnz_train), tei(h.test_i, h.test_i + h.nnz_test);
     std::vector<T> tev;
-    if (h.tev) tev.assign(h.tev, h.tev + nnz_te);
-    int rc = rm_csr_sort_rows(h.trp, tri.data(), nullptr, 0, h.m, h.nthreads);
-    if (rc == RM_OK) rc = rm_csr_sort_rows(h.tep, tei.data(), h.tev ? (void *)tev.data() : nullptr, h.tev ? (int32_t)sizeof(T) : 0, h.m, h.nthreads);
+    if (h.test_v) tev.assign(h.test_v, h.test_v + h.nnz_test);
+    int rc = rm_csr_sort_rows(h.train_p, tri.data(), nullptr, 0, h.m, nthreads);
+    if (rc == RM_OK) rc = rm_csr_sort_rows(h.test_p, tei.data(), h.test_v ? (void *)tev.data() : nullptr, h.test_v ? (int32_t)sizeof(T) : 0, h.m, nthreads);
     if (rc != RM_OK) throw RmError{rc, "sorting a copy of the CSR rows failed"};
-    HostCall<T> h2 = h;
-    h2.tri = tri.data(); h2.tei = tei.data(); h2.tev = h.tev ? tev.data() : nullptr;
-    try { run_host_once<T>(h2); }
+    h.train_i = tri.data(); h.test_i = tei.data(); h.test_v = h.test_v ? tev.data() : nullptr;
+    try { run_host_once<T>(h); }
     catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; throw RmError{RM_ERR_INVALID, "CSR rows are not sorted"}; }
 }
 
 // device-pointer entry: the same fall-back through the host (the arrays are const device memory of the caller's: the sorted copies live in
 // the context's workspace)
+// (lists without an exclusion matrix: the index pointers become a row of zeros)
 template <class T>
-void run_dev(Call<T> c, hipStream_t stream, Ctx &cx)
+void run_dev(const Request<T> &r, hipStream_t stream)
 {
+    Call<T> c(r);
+    Ctx &cx = context(0);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
+    if (r.reco && !r.train_p) {
+        int *z = (int *)cx.ws.get("reco_zero_p", sizeof(int) * ((size_t)r.m + 1));
+        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // (an earlier call on another stream may still read it)
+        HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)r.m + 1), stream));
+        c.train_p = z; c.train_i = z; c.nnz_train = 0;
+    }
     try { run_call<T>(c, stream, cx); return; }
     catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; }
     const size_t m1 = (size_t)c.m + 1, nnz_tr = (size_t)std::max<long long>(c.nnz_train, 0), nnz_te = (size_t)std::max<long long>(c.nnz_test, 0);
@@ -2722,106 +2770,65 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-// ---- recommendation lists: rm_recommend_* ---------------------------------------------------------------------------------
-// The metric call's pipeline in its `reco` mode (Call::reco: k_classify without a test matrix, the sweep without positives,
-// k_finalize_reco).  `xp == NULL`: nothing is excluded -- the index pointers become a row of zeros.
-inline void validate_recommend(const void *A, const void *B, int m, int n, int k, int K, size_t lda, size_t ldb, const void *idx, const void *status)
+// ---- the entries: a request from the C arguments of its family, checked, run ------------------------------------------------------------
+// The four families are two score sources -- factors, or the caller's score matrix -- times two kinds of request, and the host and the
+// device form of a family state the same request: the device form adds the lengths of the index arrays (the host form reads them from the
+// index pointers) and a stream, the host form the threads of the fall-back sort.
+template <class T> Request<T> from_factors(const T *A, size_t lda, const T *B, size_t ldb, int k) { return Request<T>{A, lda, B, ldb, k}; }
+template <class T> Request<T> from_scores(const T *S, size_t lds)
 {
-    if (m < 0 || n <= 0 || k <= 0) throw RmError{RM_ERR_INVALID, "m, n, k must be positive"};
-    if (!A || !B) throw RmError{RM_ERR_INVALID, "null input pointer"};
-    if (!idx || !status) throw RmError{RM_ERR_INVALID, "null output pointer"};
-    if (K < 1 || K > n) throw RmError{RM_ERR_INVALID, "k_top must lie in [1, n] (got " + std::to_string(K) + " with " + std::to_string(n) + " items)"};
-    if (lda < (size_t)k || ldb < (size_t)k) throw RmError{RM_ERR_INVALID, "leading dimension smaller than k"};
+    Request<T> r;
+    r.S = S; r.lds = lds; r.scores = true;
+    return r;
 }
 template <class T>
-void recommend_host(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, int k, const int *xp, const int *xi, int K,
-                    int *idx, T *score, int *status, int nthreads)
+Request<T> metrics_request(Request<T> r, int m, int n, const int *train_p, const int *train_i, long long nnz_train,
+                           const int *test_p, const int *test_i, const T *test_v, long long nnz_test,
+                           int K, int cumulative, int noise, const std::array<T *, 10> &out,
+                           int cold, int min_items_pool, int min_pos_test, unsigned long long seed)
 {
-    if (m == 0) return;
-    validate_recommend(A, B, m, n, k, K, lda, ldb, idx, status);
-    const std::vector<int> zeros((size_t)m + 1, 0);
-    HostCall<T> h{A, lda, B, ldb, m, n, k, xp ? xp : zeros.data(), xp ? xi : nullptr, zeros.data(), nullptr, nullptr, K, false, false,
-                  {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, true, 1, 0,
-                  idx, score, nullptr, status, 0};
-    h.nthreads = nthreads > 0 ? nthreads : 0;
-    h.reco = true;
-    run_host<T>(h);
+    r.m = m; r.n = n;
+    r.train_p = train_p; r.train_i = train_i; r.nnz_train = nnz_train;
+    r.test_p = test_p; r.test_i = test_i; r.test_v = test_v; r.nnz_test = nnz_test;
+    r.K = K; r.cumulative = cumulative != 0; r.noise = noise != 0;
+    std::copy(out.begin(), out.end(), r.out);
+    r.cold = cold != 0; r.min_items_pool = min_items_pool; r.min_pos_test = min_pos_test; r.seed = seed;
+    return r;
 }
+// Recommendation lists (rm_recommend_*, rm_recommend_scores_*): the metric call's pipeline in its `reco` mode (k_classify without a test
+// matrix, the sweep without positives, k_finalize_reco); every user is eligible.  `xp == NULL`: nothing is excluded.  From the caller's
+// scores, up to ROW_TOPK_MAX_K items per list the row kernel of rm_rowtopk.hpp selects them while it reads the row; beyond (or under
+// RM_DEBUG_NO_ROW_TOPK) k_score_rows -> k_select_topk -> k_finalize_reco.
 template <class T>
-void recommend_dev(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, int k, const int *xp, const int *xi, long long nnz, int K,
-                   int *idx, T *score, int *status, hipStream_t stream)
+Request<T> lists_request(Request<T> r, int m, int n, const int *xp, const int *xi, long long nnz, int K, int *idx, T *score, int *status)
 {
-    if (m == 0) return;
-    validate_recommend(A, B, m, n, k, K, lda, ldb, idx, status);
-    if (xp && nnz > 0 && !xi) throw RmError{RM_ERR_INVALID, "null input pointer"};
-    if (nnz < 0) throw RmError{RM_ERR_INVALID, "negative length of the index array"};
-    Call<T> c{};
-    c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.m = m; c.n = n; c.k = k;
-    c.train_p = xp; c.train_i = xi; c.nnz_train = xp ? nnz : 0;
-    c.K = K; c.cold = true; c.min_items_pool = 1; c.min_pos_test = 0;
-    c.topk_idx = idx; c.topk_score = score; c.status = status; c.reco = true;
-    c.seed = 0; c.user0 = 0;
-    Ctx &cx = context(0);
-    std::lock_guard<std::mutex> lk(cx.mu);
-    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
-    if (!xp) {
-        int *z = (int *)cx.ws.get("reco_zero_p", sizeof(int) * ((size_t)m + 1));
-        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // (an earlier call on another stream may still read it)
-        HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)m + 1), stream));
-        c.train_p = z; c.train_i = z;
-    }
-    run_dev<T>(c, stream, cx);
+    r.m = m; r.n = n;
+    r.train_p = xp; r.train_i = xp ? xi : nullptr; r.nnz_train = nnz;
+    r.K = K; r.cold = true; r.min_items_pool = 1; r.min_pos_test = 0;
+    r.topk_idx = idx; r.topk_score = score; r.status = status; r.reco = true;
+    return r;
 }
 
-// ---- recommendation lists from the caller's score matrix: rm_recommend_scores_* ---------------------------------------------
-// rm_recommend_* with the scores of rm_calc_metrics_scores_*: Call::reco && Call::scores.  Up to ROW_TOPK_MAX_K items per list the
-// row kernel of rm_rowtopk.hpp selects them while it reads the row; beyond (or under RM_DEBUG_NO_ROW_TOPK) k_score_rows ->
-// k_select_topk -> k_finalize_reco.  The host entry is HostRange's (rows of S batch by batch, shards, interrupts).
-inline void validate_recommend_scores(const void *S, size_t lds, int m, int n, int K, const void *idx, const void *status)
+template <class T> void host_entry(const Request<T> &r, int nthreads)
 {
-    if (m < 0 || n <= 0) throw RmError{RM_ERR_INVALID, "m must not be negative and n must be positive"};
-    if (!S) throw RmError{RM_ERR_INVALID, "null input pointer"};
-    if (!idx || !status) throw RmError{RM_ERR_INVALID, "null output pointer"};
-    if (lds < (size_t)n) throw RmError{RM_ERR_INVALID, "leading dimension of the score matrix smaller than n (got " + std::to_string(lds) + " with " + std::to_string(n) + " items)"};
-    if (K < 1 || K > n) throw RmError{RM_ERR_INVALID, "k_top must lie in [1, n] (got " + std::to_string(K) + " with " + std::to_string(n) + " items)"};
+    if (r.m == 0) return;                                            // reference :428-437: no user, nothing written
+    check_request(r, true);
+    run_host<T>(r, nthreads > 0 ? nthreads : 0);                     // (host threads of the fall-back sort of unsorted CSR rows: 0 = all)
 }
-template <class T>
-void recommend_scores_host(const T *S, size_t lds, int m, int n, const int *xp, const int *xi, int K, int *idx, T *score, int *status, int nthreads)
+template <class T> void dev_entry(const Request<T> &r, void *stream)
 {
-    if (m == 0) return;
-    validate_recommend_scores(S, lds, m, n, K, idx, status);
-    const std::vector<int> zeros((size_t)m + 1, 0);
-    HostCall<T> h{nullptr, 0, nullptr, 0, m, n, 0, xp ? xp : zeros.data(), xp ? xi : nullptr, zeros.data(), nullptr, nullptr, K, false, false,
-                  {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, true, 1, 0,
-                  idx, score, nullptr, status, 0};
-    h.nthreads = nthreads > 0 ? nthreads : 0;
-    h.reco = true; h.scores = true; h.S = S; h.lds = lds;
-    run_host<T>(h);
+    if (r.m == 0) return;
+    check_request(r, false);
+    run_dev<T>(r, (hipStream_t)stream);
 }
-template <class T>
-void recommend_scores_dev(const T *S, size_t lds, int m, int n, const int *xp, const int *xi, long long nnz, int K,
-                          int *idx, T *score, int *status, hipStream_t stream)
+// rm_rank_*: the factor metrics' host request with the ranking outputs, its AP / ROC-AUC / PR-AUC going to scratch arrays
+template <class T> void rank_entry(Request<T> r, int *topk_idx, T *topk_score, long long *pos_rank, int *status)
 {
-    if (m == 0) return;
-    validate_recommend_scores(S, lds, m, n, K, idx, status);
-    if (nnz < 0) throw RmError{RM_ERR_INVALID, "negative length of the index array"};
-    if (xp && nnz > 0 && !xi) throw RmError{RM_ERR_INVALID, "null input pointer"};
-    Call<T> c{};
-    c.scores = true; c.S = S; c.lds = lds; c.m = m; c.n = n; c.k = 0;
-    c.train_p = xp; c.train_i = xi; c.nnz_train = xp ? nnz : 0;
-    c.K = K; c.cold = true; c.min_items_pool = 1; c.min_pos_test = 0;
-    c.topk_idx = idx; c.topk_score = score; c.status = status; c.reco = true;
-    c.seed = 0; c.user0 = 0;
-    Ctx &cx = context(0);
-    std::lock_guard<std::mutex> lk(cx.mu);
-    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
-    if (!xp) {
-        int *z = (int *)cx.ws.get("reco_zero_p", sizeof(int) * ((size_t)m + 1));
-        if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // (an earlier call on another stream may still read it)
-        HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)m + 1), stream));
-        c.train_p = z; c.train_i = z;
-    }
-    run_dev<T>(c, stream, cx);
+    if (!topk_idx || !topk_score || !pos_rank || !status) throw RmError{RM_ERR_INVALID, "null output pointer"};     // (*) even with m == 0
+    std::vector<T> ap((size_t)std::max(r.m, 1)), roc((size_t)std::max(r.m, 1)), pr((size_t)std::max(r.m, 1));
+    r.out[3] = ap.data(); r.out[8] = roc.data(); r.out[9] = pr.data();
+    r.topk_idx = topk_idx; r.topk_score = topk_score; r.pos_rank = pos_rank; r.status = status;
+    host_entry<T>(r, 0);
 }
 
 } // namespace
@@ -2840,12 +2847,12 @@ extern "C" int rm_calc_metrics_##SUFFIX(                                        
     int32_t nthreads, uint64_t seed)                                                                                    \
 {                                                                                                                       \
     return guarded([&] {                                                                                                \
-        HostCall<T> h{A, lda, B, ldb, m, n, k, Xtrain_csr_p, Xtrain_csr_i, Xtest_csr_p, Xtest_csr_i, Xtest_csr,         \
-                      k_metrics, cumulative != 0, break_ties_with_noise != 0,                                           \
-                      {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k, roc_auc, pr_auc},      \
-                      consider_cold_start != 0, min_items_pool, min_pos_test, nullptr, nullptr, nullptr, nullptr, seed};\
-        h.nthreads = nthreads > 0 ? nthreads : 0;                                                                       \
-        run_host<T>(h);                                                                                                 \
+        host_entry<T>(metrics_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xtrain_csr_p, Xtrain_csr_i, 0,       \
+                                         Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0, k_metrics, cumulative,                 \
+                                         break_ties_with_noise,                                                         \
+                                         {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,     \
+                                          roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, seed),   \
+                      nthreads);                                                                                        \
     });                                                                                                                 \
 }                                                                                                                       \
 extern "C" int rm_calc_metrics_dev_##SUFFIX(                                                                            \
@@ -2858,22 +2865,12 @@ extern "C" int rm_calc_metrics_dev_##SUFFIX(                                    
     uint64_t seed, void *stream)                                                                                        \
 {                                                                                                                       \
     return guarded([&] {                                                                                                \
-        if (m == 0) return;                                                                                             \
-        validate(A, B, m, n, k, Xtrain_csr_p, Xtest_csr_p, Xtest_csr_i, (long long)nnz_test, k_metrics, lda, ldb);      \
-        if (ndcg_at_k && !Xtest_csr) throw RmError{RM_ERR_INVALID, "NDCG requested without test values"};               \
-        Call<T> c{};                                                                                                    \
-        c.A = A; c.lda = lda; c.B = B; c.ldb = ldb; c.m = m; c.n = n; c.k = k;                                          \
-        c.train_p = Xtrain_csr_p; c.train_i = Xtrain_csr_i; c.nnz_train = nnz_train;                                    \
-        c.test_p = Xtest_csr_p; c.test_i = Xtest_csr_i; c.test_v = Xtest_csr; c.nnz_test = nnz_test;                    \
-        c.K = k_metrics; c.cumulative = cumulative != 0; c.noise = break_ties_with_noise != 0;                          \
-        T *outs[10] = {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k, roc_auc, pr_auc};      \
-        for (int i = 0; i < 10; i++) c.out[i] = outs[i];                                                                \
-        c.cold = consider_cold_start != 0; c.min_items_pool = min_items_pool; c.min_pos_test = min_pos_test;            \
-        Ctx &cx = context(0);                                                                                           \
-        std::lock_guard<std::mutex> lk(cx.mu);                                                                          \
-        cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;                                                              \
-        c.seed = seed; c.user0 = 0;                                                                                     \
-        run_dev<T>(c, (hipStream_t)stream, cx);                                                                         \
+        dev_entry<T>(metrics_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xtrain_csr_p, Xtrain_csr_i, nnz_train,\
+                                        Xtest_csr_p, Xtest_csr_i, Xtest_csr, nnz_test, k_metrics, cumulative,           \
+                                        break_ties_with_noise,                                                          \
+                                        {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,      \
+                                         roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, seed),    \
+                     stream);                                                                                           \
     });                                                                                                                 \
 }                                                                                                                       \
 extern "C" int rm_rank_##SUFFIX(                                                                                        \
@@ -2883,14 +2880,10 @@ extern "C" int rm_rank_##SUFFIX(                                                
     int32_t min_pos_test, uint64_t seed, int32_t *topk_idx, T *topk_score, int64_t *pos_rank, int32_t *status)          \
 {                                                                                                                       \
     return guarded([&] {                                                                                                \
-        if (!topk_idx || !topk_score || !pos_rank || !status) throw RmError{RM_ERR_INVALID, "null output pointer"};     \
-        std::vector<T> ap((size_t)std::max(m, 1)), roc((size_t)std::max(m, 1)), pr((size_t)std::max(m, 1));             \
-        HostCall<T> h{A, lda, B, ldb, m, n, k, Xtrain_csr_p, Xtrain_csr_i, Xtest_csr_p, Xtest_csr_i, (const T *)nullptr,\
-                      k_metrics, false, break_ties_with_noise != 0,                                                     \
-                      {nullptr, nullptr, nullptr, ap.data(), nullptr, nullptr, nullptr, nullptr, roc.data(), pr.data()},\
-                      consider_cold_start != 0, min_items_pool, min_pos_test,                                           \
-                      topk_idx, topk_score, (long long *)pos_rank, status, seed};                                       \
-        run_host<T>(h);                                                                                                 \
+        rank_entry<T>(metrics_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xtrain_csr_p, Xtrain_csr_i, 0,       \
+                                         Xtest_csr_p, Xtest_csr_i, nullptr, 0, k_metrics, 0, break_ties_with_noise, {}, \
+                                         consider_cold_start, min_items_pool, min_pos_test, seed),                      \
+                      topk_idx, topk_score, (long long *)pos_rank, status);                                             \
     });                                                                                                                 \
 }
 
@@ -2908,16 +2901,11 @@ extern "C" int rm_calc_metrics_scores_##SUFFIX(                                 
     T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads)     \
 {                                                                                                                       \
     return guarded([&] {                                                                                                \
-        if (m == 0) return;                                                                                             \
-        HostCall<T> h{nullptr, 0, nullptr, 0, m, n, 0, Xtrain_csr_p, Xtrain_csr_i, Xtest_csr_p, Xtest_csr_i, Xtest_csr, \
-                      k_metrics, cumulative != 0, false,                                                                \
-                      {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k, roc_auc, pr_auc},      \
-                      consider_cold_start != 0, min_items_pool, min_pos_test, nullptr, nullptr, nullptr, nullptr, 0};   \
-        h.nthreads = nthreads > 0 ? nthreads : 0;                                                                       \
-        h.scores = true; h.S = S; h.lds = lds;                                                                          \
-        if (m < 0 || n <= 0 || !Xtest_csr_p || !Xtrain_csr_p)                                                          \
-            validate_scores(S, lds, m, n, k_metrics, Xtrain_csr_p, Xtest_csr_p, Xtest_csr_i, 0, ndcg_at_k, Xtest_csr);  \
-        run_host<T>(h);                                                                                                 \
+        host_entry<T>(metrics_request<T>(from_scores<T>(S, lds), m, n, Xtrain_csr_p, Xtrain_csr_i, 0,                   \
+                                         Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0, k_metrics, cumulative, 0,              \
+                                         {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,     \
+                                          roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, 0),      \
+                      nthreads);                                                                                        \
     });                                                                                                                 \
 }                                                                                                                       \
 extern "C" int rm_calc_metrics_scores_dev_##SUFFIX(                                                                     \
@@ -2929,23 +2917,11 @@ extern "C" int rm_calc_metrics_scores_dev_##SUFFIX(                             
     T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, void *stream)         \
 {                                                                                                                       \
     return guarded([&] {                                                                                                \
-        if (m == 0) return;                                                                                             \
-        validate_scores(S, lds, m, n, k_metrics, Xtrain_csr_p, Xtest_csr_p, Xtest_csr_i, (long long)nnz_test, ndcg_at_k, Xtest_csr); \
-        if (nnz_train < 0 || nnz_test < 0) throw RmError{RM_ERR_INVALID, "negative length of an index array"};          \
-        if (nnz_train > 0 && !Xtrain_csr_i) throw RmError{RM_ERR_INVALID, "null train indices"};                        \
-        Call<T> c{};                                                                                                    \
-        c.scores = true; c.S = S; c.lds = lds; c.m = m; c.n = n; c.k = 0;                                               \
-        c.train_p = Xtrain_csr_p; c.train_i = Xtrain_csr_i; c.nnz_train = nnz_train;                                    \
-        c.test_p = Xtest_csr_p; c.test_i = Xtest_csr_i; c.test_v = Xtest_csr; c.nnz_test = nnz_test;                    \
-        c.K = k_metrics; c.cumulative = cumulative != 0; c.noise = false;                                               \
-        T *outs[10] = {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k, roc_auc, pr_auc};      \
-        for (int i = 0; i < 10; i++) c.out[i] = outs[i];                                                                \
-        c.cold = consider_cold_start != 0; c.min_items_pool = min_items_pool; c.min_pos_test = min_pos_test;            \
-        Ctx &cx = context(0);                                                                                           \
-        std::lock_guard<std::mutex> lk(cx.mu);                                                                          \
-        cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;                                                              \
-        c.seed = 0; c.user0 = 0;                                                                                        \
-        run_dev<T>(c, (hipStream_t)stream, cx);                                                                         \
+        dev_entry<T>(metrics_request<T>(from_scores<T>(S, lds), m, n, Xtrain_csr_p, Xtrain_csr_i, nnz_train,            \
+                                        Xtest_csr_p, Xtest_csr_i, Xtest_csr, nnz_test, k_metrics, cumulative, 0,        \
+                                        {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,      \
+                                         roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, 0),       \
+                     stream);                                                                                           \
     });                                                                                                                 \
 }
 
@@ -2958,15 +2934,20 @@ extern "C" int rm_recommend_##SUFFIX(                                           
     const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
     int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
 {                                                                                                                       \
-    return guarded([&] { recommend_host<T>(A, lda, B, ldb, m, n, k, Xexcl_csr_p, Xexcl_csr_i, k_top, idx, score, status, nthreads); }); \
+    return guarded([&] {                                                                                                \
+        host_entry<T>(lists_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xexcl_csr_p, Xexcl_csr_i, 0, k_top,    \
+                                       idx, score, status), nthreads);                                                  \
+    });                                                                                                                 \
 }                                                                                                                       \
 extern "C" int rm_recommend_dev_##SUFFIX(                                                                               \
     const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
     const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
     int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
 {                                                                                                                       \
-    return guarded([&] { recommend_dev<T>(A, lda, B, ldb, m, n, k, Xexcl_csr_p, Xexcl_csr_i, (long long)nnz_excl, k_top, idx, score, status, \
-                                          (hipStream_t)stream); });                                                     \
+    return guarded([&] {                                                                                                \
+        dev_entry<T>(lists_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xexcl_csr_p, Xexcl_csr_i, nnz_excl,     \
+                                      k_top, idx, score, status), stream);                                              \
+    });                                                                                                                 \
 }
 
 RM_RECOMMEND_ENTRY(f32, float)
@@ -2978,15 +2959,20 @@ extern "C" int rm_recommend_scores_##SUFFIX(                                    
     const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
     int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
 {                                                                                                                       \
-    return guarded([&] { recommend_scores_host<T>(S, lds, m, n, Xexcl_csr_p, Xexcl_csr_i, k_top, idx, score, status, nthreads); }); \
+    return guarded([&] {                                                                                                \
+        host_entry<T>(lists_request<T>(from_scores<T>(S, lds), m, n, Xexcl_csr_p, Xexcl_csr_i, 0, k_top,                \
+                                       idx, score, status), nthreads);                                                  \
+    });                                                                                                                 \
 }                                                                                                                       \
 extern "C" int rm_recommend_scores_dev_##SUFFIX(                                                                        \
     const T *S, size_t lds, int32_t m, int32_t n,                                                                       \
     const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
     int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
 {                                                                                                                       \
-    return guarded([&] { recommend_scores_dev<T>(S, lds, m, n, Xexcl_csr_p, Xexcl_csr_i, (long long)nnz_excl, k_top, idx, score, status, \
-                                                 (hipStream_t)stream); });                                              \
+    return guarded([&] {                                                                                                \
+        dev_entry<T>(lists_request<T>(from_scores<T>(S, lds), m, n, Xexcl_csr_p, Xexcl_csr_i, nnz_excl, k_top,          \
+                                      idx, score, status), stream);                                                     \
+    });                                                                                                                 \
 }
 
 RM_RECOMMEND_SCORES_ENTRY(f32, float)
