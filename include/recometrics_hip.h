@@ -280,6 +280,18 @@ void rm_request_interrupt(void);
  * while a call is running. */
 void rm_debug_reload_switches(void);
 
+/* Test hooks over the table of sweep-kernel instantiations; none of them touches a device.  elem_bytes = 4 /
+ * 8 picks the precision (anything else returns -1).  A variant is six ints, the kernel's template arguments: ng (factor groups of
+ * 8; 0 = the kernel that takes the count at run time), auc, dump, list mode (0 LDS, 1 HBM replace-the-minimum, 2 HBM append), item
+ * sub-tiles per step (fp64: always 2), spec.
+ *   rm_debug_sweep_variants  writes the first `cap` rows of the table to out[6 * cap] (out may be NULL) and returns the row count
+ *   rm_debug_find_sweep      the variant that serves a request of the pipeline (ngt = the group count the operands were packed
+ *                            for): 0 and the key in out6, or -1 where there is no kernel for it
+ *   rm_debug_supported_ng    the factor-group count a call with k factors runs as */
+int rm_debug_sweep_variants(int elem_bytes, int *out, int cap);
+int rm_debug_find_sweep(int elem_bytes, int ng, int ngt, int auc, int dump, int lmode, int nsub, int spec, int *out6);
+int rm_debug_supported_ng(int elem_bytes, int k);
+
 /* Timings of the most recent successful call on this thread, milliseconds measured with HIP events on the call's
  * stream: out[0] plan+pack+positives, out[1] sweep kernel, out[2] finalize, out[3] whole device section;
  * out[4] = launches of the sweep kernel, out[5] = item splits, out[6] = sweep blocks, out[7] = dynamic LDS bytes,

@@ -1,6 +1,10 @@
 """Builds recometrics_amd/csrc/librecometrics_hip.so for gfx950 (in-tree; hipcc cross-compiles without a GPU).
 
-The library is several translation units (host + prep/finalize kernels, fp32 sweep, fp64 sweeps) compiled in parallel."""
+The library is several translation units compiled in parallel: the host side with the preparation and finalisation kernels
+(rm_lib.hip), and the sweep kernels.  Every instantiation of the two sweep kernels lives in ONE source, csrc/rm_sweep_units.hip,
+compiled once per unit of SWEEP_UNITS with the unit's family and specialisation as -D defines (the file's header lists the
+families), and once without them: the table that walks the units' rows.  A unit is spelled "source" or "source:unit" in SOURCES
+and in the stamp's `translation_units`; its object is csrc/<source stem>[.<unit>].o."""
 import concurrent.futures
 import glob
 import os
@@ -9,10 +13,12 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "librecometrics_hip.so")
-SOURCES = ["rm_lib.hip", "rm_sweep32.hip", "rm_sweep32_large.hip", "rm_sweep64_small.hip", "rm_sweep64_small_s1.hip", "rm_sweep64_large.hip", "rm_sweep64_large_s1.hip",
-           # the fp32 sweep families x the specialisations of the epilogue's switches (rm_sweep.hpp k_sweep SPEC): one unit each
-           "rm_sweep32_n3.hip", "rm_sweep32_n3_s1.hip", "rm_sweep32_n3_s2.hip", "rm_sweep32_lds.hip", "rm_sweep32_lds_s1.hip", "rm_sweep32_lds_s2.hip",
-           "rm_sweep32_hbm.hip", "rm_sweep32_hbm_s1.hip", "rm_sweep32_hbm_s2.hip", "rm_split.cpp", "rm_csr.cpp"]
+SWEEP_SRC = "rm_sweep_units.hip"
+# unit -> (RM_FAMILY, RM_SPEC): the sweep families x the specialisations of the epilogue's switches (k_sweep / k_sweep64 SPEC)
+SWEEP_UNITS = {"sweep32_dump": (4, 0), "sweep32_large": (3, 0)}
+SWEEP_UNITS.update({"sweep64_%s_s%d" % (name, spec): (fam, spec) for name, fam in (("small", 5), ("large", 6)) for spec in range(2)})
+SWEEP_UNITS.update({"sweep32_%s_s%d" % (name, spec): (fam, spec) for name, fam in (("n3", 0), ("lds", 1), ("hbm", 2)) for spec in range(3)})
+SOURCES = ["rm_lib.hip"] + [SWEEP_SRC + ":" + u for u in SWEEP_UNITS] + [SWEEP_SRC, "rm_split.cpp", "rm_csr.cpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-inline-asm"]   # m0 is clobbered by the LDS-DMA asm on purpose
 
 
@@ -25,7 +31,7 @@ def _hipcc():
 
 def _deps():
     root = os.path.dirname(os.path.dirname(CSRC))
-    return (glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(CSRC, "*.cpp"))
+    return (glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.cpp"))
             + glob.glob(os.path.join(root, "include", "*.h")))
 
 
@@ -39,7 +45,7 @@ def sources_digest():
     for p in sorted(_deps()):
         h.update(os.path.basename(p).encode() + b"\0")
         h.update(open(p, "rb").read())
-    h.update(repr((SOURCES, FLAGS, SWEEP_FLAGS)).encode())
+    h.update(repr((SOURCES, SWEEP_UNITS, FLAGS, SWEEP_FLAGS)).encode())
     return h.hexdigest()
 
 
@@ -73,11 +79,14 @@ SWEEP_FLAGS = ["-fno-slp-vectorize"]
 
 def _headers():
     root = os.path.dirname(os.path.dirname(CSRC))
-    return glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(root, "include", "*.h"))
+    return glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(root, "include", "*.h"))
 
 
-def _compile(src, extra, incremental=False):
-    obj = os.path.join(CSRC, os.path.splitext(src)[0] + ".o")
+def _compile(tu, extra, incremental=False):
+    src, _, unit = tu.partition(":")
+    obj = os.path.join(CSRC, os.path.splitext(src)[0] + ("." + unit if unit else "") + ".o")
+    if unit:
+        extra = list(extra) + ["-DRM_FAMILY=%d" % SWEEP_UNITS[unit][0], "-DRM_SPEC=%d" % SWEEP_UNITS[unit][1]]
     # (development only, `build(incremental=True)`: an object newer than its source and every header is kept; the library's own
     # stamp stays content-based)
     if incremental and os.path.exists(obj):
@@ -94,7 +103,7 @@ def _compile(src, extra, incremental=False):
         cmd = [_hipcc()] + FLAGS + list(extra) + ["-c", os.path.join(CSRC, src), "-o", obj]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
-        raise RuntimeError("hipcc failed on %s:\n%s%s" % (src, res.stdout, res.stderr))
+        raise RuntimeError("hipcc failed on %s:\n%s%s" % (tu, res.stdout, res.stderr))
     return obj, res.stderr
 
 

@@ -1,5 +1,5 @@
-// rm_launch.hpp -- argument blocks of the two sweep kernels and the launch entry points of their translation units
-// (the sweeps are compiled in separate .hip files so that the build parallelises).
+// rm_launch.hpp -- argument blocks of the two sweep kernels, and the table of their instantiations: key, row, lookup
+// (the sweeps are compiled as several translation units so that the build parallelises; every unit contributes its rows).
 #pragma once
 #include "rm_device.hpp"
 #include "rm_list.hpp"
@@ -87,22 +87,31 @@ struct Sweep64Args {
     const int *noise_row; int noise_row0; const double *noise_E; long long noise_ld;     // tie noise: see SweepArgs
 };
 
-// return 0 = launched, -1 = unsupported factor-group count, otherwise a hipError_t
-int launch_sweep32(bool auc, bool dump, int lmode, int nsub, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_hbm_s0(bool auc, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_hbm_s1(bool auc, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_hbm_s2(bool auc, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_lds_s0(bool auc, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_lds_s1(bool auc, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_lds_s2(bool auc, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_n3_s0(bool auc, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_n3_s1(bool auc, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_n3_s2(bool auc, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep32_large(bool auc, bool dump, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa);
-int launch_sweep64(bool auc, bool dump, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const Sweep64Args &sa);
-int launch_sweep64_small_s0(bool auc, bool dump, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const Sweep64Args &sa);
-int launch_sweep64_small_s1(bool auc, bool dump, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const Sweep64Args &sa);
-int launch_sweep64_large_s0(bool auc, bool dump, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const Sweep64Args &sa);
-int launch_sweep64_large_s1(bool auc, bool dump, int lmode, int NG, dim3 grid, size_t lds, hipStream_t stream, const Sweep64Args &sa);
+// ---- the table of sweep kernel variants (rm_sweep_units.hip) -------------------------------------------------------------
+// A variant is named by the kernel's own template arguments; k_sweep64 has no NSUB, its rows say 2.  ng 0 = the kernel that
+// takes the factor-group count at run time (sa.ngt).
+struct SweepKey { int ng, auc, dump, lmode, nsub, spec; };
+inline bool operator==(const SweepKey &a, const SweepKey &b)
+{
+    return a.ng == b.ng && a.auc == b.auc && a.dump == b.dump && a.lmode == b.lmode && a.nsub == b.nsub && a.spec == b.spec;
+}
+// launch: sets the dynamic-LDS attribute, launches, returns hipGetLastError()
+template <class Args> struct SweepRow { SweepKey key; int (*launch)(dim3 grid, size_t lds, hipStream_t stream, const Args &sa); };
+template <class Args> struct SweepRows { const SweepRow<Args> *row; int n; };
+
+// rows of the precision's translation unit `unit` = 0, 1, ...; {nullptr, 0} behind the last
+template <class Args> SweepRows<Args> sweep_rows(int unit);
+// What the pipeline asks for -> the key of the variant that serves it; false = no kernel for this request.  lmode: 0 = LDS lists,
+// 1 = HBM replace-the-minimum (K <= 32), 2 = HBM append buffers.  Only ng > 64 looks at ngt.
+template <class Args> bool sweep_key(int ng, int ngt, bool auc, bool dump, int lmode, int nsub, int spec, SweepKey &key);
+
+template <class Args> const SweepRow<Args> *find_sweep(const SweepKey &key)
+{
+    for (int u = 0;; u++) {
+        const SweepRows<Args> r = sweep_rows<Args>(u);
+        if (!r.row) return nullptr;
+        for (int i = 0; i < r.n; i++) if (r.row[i].key == key) return r.row + i;
+    }
+}
 
 } // namespace rm

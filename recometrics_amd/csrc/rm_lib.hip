@@ -413,13 +413,25 @@ __global__ void k_export_pos_rank(long long nnz, int m, const int *test_p, const
     for (int e = test_p[u]; e < test_p[u + 1]; e++) pos_rank[e] = ranked ? rank_sorted[test_p[u] + pos_order[e]] : 0;
 }
 
+// factor groups of 8 a call with k factors runs as: the smallest count the table has a kernel for, beyond those whole chunks
+template <class Args> int table_ng(int k, int chunk)
+{
+    const int ng = std::max(1, (k + 7) / 8);
+    int best = 0;
+    for (int u = 0;; u++) {
+        const SweepRows<Args> r = sweep_rows<Args>(u);
+        if (!r.row) break;
+        for (int i = 0; i < r.n; i++) if (r.row[i].key.ng >= ng && (!best || r.row[i].key.ng < best)) best = r.row[i].key.ng;
+    }
+    return best ? best : (ng + chunk - 1) / chunk * chunk;
+}
+
 // ---- per-precision traits: which sweep kernel, which operand image, how many users ride on a wavefront ----
 template <class T> struct Prec;
 template <> struct Prec<float> {
     static constexpr int GU = GROUP_USERS;               // users per group
     typedef float4 PackT;  typedef u32x2 ListT;  typedef SweepArgs Args;
-    // factor groups of 8: the instantiated counts up to 512 factors, beyond that whole 128-factor chunks (run-time count)
-    static int supported_ng(int k) { const int ng = (k + 7) / 8; for (int o : {2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 16, 32, 64}) if (ng <= o) return o; return (ng + 15) / 16 * 16; }
+    static int supported_ng(int k) { return table_ng<Args>(k, 16); }      // beyond 512 factors: whole 128-factor chunks
     static const char *limit() { return "unsupported factor count"; }
     static size_t lds_b(int NG, int tile = TILE_ITEMS) { return 2ull * std::min(NG, 16) * 2 * tile * 16; }
     static long long items_units(int tiles, int NG, int tile = TILE_ITEMS) { return (long long)tiles * NG * 2 * tile; }
@@ -429,9 +441,6 @@ template <> struct Prec<float> {
     static constexpr int pend_cap_max = 8;                // keys per lane: measured flat from 3 to 8 at C2, best at 6-8
     static constexpr int max_nsub = 3;
     static size_t lists_b(int, int K) { return (size_t)GROUPS_PER_BLOCK * (K + 2) * GU * 8; }      // one list per group, shared by its waves
-    static void set_pending(SweepArgs &sa, int cap, int off) { sa.pend_cap = cap; sa.pend_off = off; }
-    static void set_sync(SweepArgs &sa, int off) { sa.sync_off = off; }
-    static void set_ublocks(SweepArgs &sa, int first, int count) { sa.ublock0 = first; sa.n_ublocks = count; }
     // K > 32: entries per lane buffer of the sweep (rm_list.hpp; a multiple of 16, and a selection's K + slack survivors plus a tile's
     // sixteen appends must fit one lane: 2K + 16), lanes per user
     static int lane_cap(int K) { return (2 * K + 16 + 15) / 16 * 16; }
@@ -440,7 +449,7 @@ template <> struct Prec<float> {
 template <> struct Prec<double> {
     static constexpr int GU = GROUP_USERS64;
     typedef double2 PackT;  typedef u32x4 ListT;  typedef Sweep64Args Args;
-    static int supported_ng(int k) { const int ng = (k + 7) / 8; for (int o : {2, 3, 4, 5, 6, 7, 8, 16, 32, 64}) if (ng <= o) return o; return (ng + 7) / 8 * 8; }
+    static int supported_ng(int k) { return table_ng<Args>(k, 8); }       // beyond 512 factors: whole 64-factor chunks
     static const char *limit() { return "unsupported factor count"; }
     static size_t lds_b(int NG, int = TILE_ITEMS) { return 2ull * std::min(NG, 8) * 4 * TILE_ITEMS * 16; }
     static long long items_units(int tiles, int NG, int = TILE_ITEMS) { return (long long)tiles * NG * 4 * TILE_ITEMS; }
@@ -450,9 +459,6 @@ template <> struct Prec<double> {
     static constexpr int pend_cap_max = 3;                // a user spans four lanes here: larger buffers only delay the bound (measured)
     static constexpr int max_nsub = 2;
     static size_t lists_b(int ns, int K) { return 4ull * ns * K * GU * sizeof(ListT); }               // one list per wave
-    static void set_pending(Sweep64Args &sa, int cap, int off) { sa.pend_cap = cap; sa.pend_off = off; }
-    static void set_sync(Sweep64Args &sa, int off) { sa.sync_off = off; }
-    static void set_ublocks(Sweep64Args &sa, int first, int count) { sa.ublock0 = first; sa.n_ublocks = count; }
     // (four lanes per user: K + slack + a tile's eight appends must fit ONE lane, the user's four hold ~5K together)
     static int lane_cap(int K) { return (K + lane_sel_slack(K) + 8 + 16 + 15) / 16 * 16; }
     static constexpr int lanes_per_user = 4, lane_tile = 8;
@@ -463,14 +469,13 @@ inline void check_launch(int rc)
     if (rc == -1) throw RmError{RM_ERR_UNSUPPORTED, "unsupported factor count"};
     if (rc != 0) throw RmError{RM_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString((hipError_t)rc)};
 }
-inline void dispatch_sweep(bool auc, bool dump, bool llds, int nsub, int NG, dim3 grid, size_t lds, hipStream_t stream, const SweepArgs &sa)
+template <class Args>
+void dispatch_sweep(bool auc, bool dump, bool llds, int nsub, int NG, dim3 grid, size_t lds, hipStream_t stream, const Args &sa)
 {
-    // list mode of the fp32 sweep (rm_sweep.hpp): 0 = LDS, 1 = HBM replace-the-minimum (K <= 32), 2 = HBM append buffers
-    check_launch(launch_sweep32(auc, dump, llds ? 0 : (sa.buffered_lists ? 2 : 1), nsub, NG, grid, lds, stream, sa));
-}
-inline void dispatch_sweep(bool auc, bool dump, bool llds, int, int NG, dim3 grid, size_t lds, hipStream_t stream, const Sweep64Args &sa)
-{
-    check_launch(launch_sweep64(auc, dump, llds ? 0 : (sa.buffered_lists ? 2 : 1), NG, grid, lds, stream, sa));
+    SweepKey key;
+    const SweepRow<Args> *row = sweep_key<Args>(NG, sa.ngt, auc, dump, llds ? LM_LDS : (sa.buffered_lists ? LM_HBM_APPEND : LM_HBM), nsub, sa.spec, key)
+                                    ? find_sweep<Args>(key) : nullptr;
+    check_launch(row ? row->launch(grid, lds, stream, sa) : -1);
 }
 
 inline void pack_operands(const float *A, size_t lda, const float *B, size_t ldb, int n, int k, int NG, int tile_items, const int *slot_user,
@@ -647,8 +652,8 @@ inline void seed_from_sample(const Args &sa, Workspace &ws, int S, int NG, int n
     // (a sweep with three sub-tiles per step has its item image in 96-item tiles and its dense train rows in words of them: the DUMP
     // variant, two sub-tiles, gets an image of the sample of its own and no dense rows -- the seed kernel walks the sparse rows)
     if (items64) { sd.Bp = (decltype(sd.Bp))items64; sd.glists = (decltype(sd.glists))lists; set_ext_bits(sd, nullptr, 0); }
-    P::set_pending(sd, 0, 0);
-    P::set_sync(sd, (int)P::lds_b(NG));
+    sd.pend_cap = 0;  sd.pend_off = 0;
+    sd.sync_off = (int)P::lds_b(NG);
     dispatch_sweep(false, true, false, 2, NG, dim3((unsigned)n_ublocks), P::lds_b(NG) + SYNC_BYTES, stream, sd);
     const dim3 grid((unsigned)cdiv(n_slots, 4)), block(256);
 #define RM_SEED_LAUNCH(NV) hipLaunchKernelGGL((k_seed_from_sample<T, ThrT, NV>), grid, block, 0, stream, n_slots, sa.K, (const T *)sample, sa.slot_user, sa.slot_chunk, sa.train_p, sa.train_i, sa.thr_shared)
@@ -1365,8 +1370,8 @@ struct Pipeline {
         sa.Ap = (decltype(sa.Ap))Ap; sa.Bp = (decltype(sa.Bp))Bp; sa.slot_user = slot_user; sa.slot_chunk = slot_chunk;
         sa.train_p = c.train_p; sa.train_i = c.train_i; sa.gj = gj; sa.grow = grow;
         sa.pos_score = pos_score; sa.pos_item = pos_item; sa.hist = hist; sa.glists = glists; sa.lane_cap = lane_cap; sa.lane_cnt = lane_cnt; sa.pl = pl; sa.pst = pst; sa.dump = nullptr;
-        P::set_pending(sa, g.pend_cap, 0);
-        P::set_sync(sa, (int)g.sync_off);
+        sa.pend_cap = g.pend_cap;  sa.pend_off = 0;
+        sa.sync_off = (int)g.sync_off;
         sa.stream_slot0 = stream_slot0; sa.stream_ld = stream_ld; sa.stream_scores = stream_scores;
         set_part_extra(sa, g.part_extra);
         sa.noise_row = c.noise_row; sa.noise_row0 = c.noise_row0; sa.noise_E = c.noise_E; sa.noise_ld = c.noise_ld;
@@ -1480,14 +1485,14 @@ struct Pipeline {
             const int u_split = g.u_split, n_ublocks = g.n_ublocks;
             side.enabled = true;                                   // (the second launch runs beside the first whatever RM_DEBUG_NO_SIDE says)
             typename P::Args sb = sa;                              // the deep blocks: lists in HBM, as computed above
-            P::set_ublocks(sb, u_split, n_ublocks - u_split);
+            sb.ublock0 = u_split;  sb.n_ublocks = n_ublocks - u_split;
             typename P::Args sl = sa;                              // the shallow blocks: lists in LDS
-            P::set_ublocks(sl, 0, u_split);
+            sl.ublock0 = 0;  sl.n_ublocks = u_split;
             // (the tail of the two-level grid = the cheapest user blocks = the first ones: the shallow launch's, then the deep one's)
             sl.tail_ublocks = std::min(g.tail_ublocks, u_split);
             sb.tail_ublocks = g.tail_ublocks - sl.tail_ublocks;
-            P::set_pending(sl, g.pend_cap, 0);
-            P::set_sync(sl, (int)(g.lds_l - SYNC_BYTES));
+            sl.pend_cap = g.pend_cap;  sl.pend_off = 0;
+            sl.sync_off = (int)(g.lds_l - SYNC_BYTES);
             dispatch_sweep(want_auc, false, false, g.nsub, NG, dim3((unsigned)((n_ublocks - u_split - sb.tail_ublocks) * g.n_splits + sb.tail_ublocks * g.tail_splits)), g.lds_total, side.fork(SIDE_SWEEP_FORK), sb);
             side.mark(SIDE_SWEEP_DEEP_DONE);
             dispatch_sweep(want_auc, false, true, g.nsub, NG, dim3((unsigned)((u_split - sl.tail_ublocks) * g.n_splits + sl.tail_ublocks * g.tail_splits)), g.lds_l, stream, sl);
@@ -2764,7 +2769,7 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
     sa.tiles_total = tiles_total; sa.jmax = 0; sa.check_nan = 1; sa.Ap = (decltype(sa.Ap))Ap; sa.Bp = (decltype(sa.Bp))Bp;
     sa.slot_user = slot_user; sa.slot_chunk = zeros; sa.train_p = zeros; sa.train_i = zeros; sa.gj = zeros + m + 1; sa.grow = grow;
     sa.glists = glists; sa.dump = dump;
-    P::set_sync(sa, (int)P::lds_b(NG));
+    sa.sync_off = (int)P::lds_b(NG);
     dispatch_sweep(false, true, false, 2, NG, dim3(n_ublocks), P::lds_b(NG) + SYNC_BYTES, stream, sa);
     HIP_CHECK(hipMemcpyAsync(out, dump, sizeof(T) * (size_t)m * n, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -3030,6 +3035,38 @@ extern "C" int rm_get_devices(int32_t *devices, int32_t cap)
 extern "C" void rm_request_interrupt(void) { g_interrupt = 1; }
 
 extern "C" void rm_debug_reload_switches(void) { g_sw.load(); }
+
+// test hooks over the table of sweep variants (rm_launch.hpp): host only, no device is touched
+template <class Args> int debug_sweep_variants(int *out, int cap)
+{
+    int n = 0;
+    for (int u = 0;; u++) {
+        const SweepRows<Args> r = sweep_rows<Args>(u);
+        if (!r.row) return n;
+        for (int i = 0; i < r.n; i++, n++)
+            if (out && n < cap) std::memcpy(out + 6 * n, &r.row[i].key, sizeof(SweepKey));
+    }
+}
+template <class Args> int debug_find_sweep(int ng, int ngt, int auc, int dump, int lmode, int nsub, int spec, int *out6)
+{
+    SweepKey key;
+    if (!sweep_key<Args>(ng, ngt, auc != 0, dump != 0, lmode, nsub, spec, key) || !find_sweep<Args>(key)) return -1;
+    if (out6) std::memcpy(out6, &key, sizeof key);
+    return 0;
+}
+extern "C" int rm_debug_sweep_variants(int elem_bytes, int *out, int cap)
+{
+    return elem_bytes == 4 ? debug_sweep_variants<SweepArgs>(out, cap) : elem_bytes == 8 ? debug_sweep_variants<Sweep64Args>(out, cap) : -1;
+}
+extern "C" int rm_debug_find_sweep(int elem_bytes, int ng, int ngt, int auc, int dump, int lmode, int nsub, int spec, int *out6)
+{
+    return elem_bytes == 4   ? debug_find_sweep<SweepArgs>(ng, ngt, auc, dump, lmode, nsub, spec, out6)
+           : elem_bytes == 8 ? debug_find_sweep<Sweep64Args>(ng, ngt, auc, dump, lmode, nsub, spec, out6) : -1;
+}
+extern "C" int rm_debug_supported_ng(int elem_bytes, int k)
+{
+    return elem_bytes == 4 ? Prec<float>::supported_ng(k) : elem_bytes == 8 ? Prec<double>::supported_ng(k) : -1;
+}
 
 extern "C" int rm_get_timings(double *out, int n)
 {
