@@ -292,6 +292,14 @@ int rm_debug_sweep_variants(int elem_bytes, int *out, int cap);
 int rm_debug_find_sweep(int elem_bytes, int ng, int ngt, int auc, int dump, int lmode, int nsub, int spec, int *out6);
 int rm_debug_supported_ng(int elem_bytes, int k);
 
+/* Test hooks: the launch ledger.  Every successful launch of a sweep kernel is counted against its row of the table (one counter
+ * per row and precision, safe across the host threads of one call; host only).
+ *   rm_debug_sweep_launched        returns the row count and writes to counts[i], i < cap, the launches of row i -- in the order of
+ *                                  rm_debug_sweep_variants -- since the last reset (counts may be NULL); -1 for an unknown precision
+ *   rm_debug_sweep_launched_reset  zeroes the counters of both precisions */
+int rm_debug_sweep_launched(int elem_bytes, int *counts, int cap);
+void rm_debug_sweep_launched_reset(void);
+
 /* Timings of the most recent successful call on this thread, milliseconds measured with HIP events on the call's
  * stream: out[0] plan+pack+positives, out[1] sweep kernel, out[2] finalize, out[3] whole device section;
  * out[4] = launches of the sweep kernel, out[5] = item splits, out[6] = sweep blocks, out[7] = dynamic LDS bytes,

@@ -24,6 +24,7 @@ EXPORTS = (
     "rm_last_error", "rm_device_count", "rm_set_device", "rm_set_devices", "rm_get_devices", "rm_request_interrupt",
     "rm_get_timings", "rm_release_workspace", "rm_debug_reload_switches",
     "rm_debug_sweep_variants", "rm_debug_find_sweep", "rm_debug_supported_ng",
+    "rm_debug_sweep_launched", "rm_debug_sweep_launched_reset",
     "rm_split_f32", "rm_split_f64", "rm_split_size", "rm_split_copy", "rm_split_free", "rm_split_last_error",
     "rm_csr_rows_sorted", "rm_csr_sort_rows",
 )
@@ -98,6 +99,8 @@ def load():
     lib.rm_debug_sweep_variants.argtypes = [ci, C.POINTER(ci), ci]
     lib.rm_debug_find_sweep.argtypes = [ci] * 8 + [C.POINTER(ci)]
     lib.rm_debug_supported_ng.argtypes = [ci, ci]
+    lib.rm_debug_sweep_launched.argtypes = [ci, C.POINTER(ci), ci]
+    lib.rm_debug_sweep_launched_reset.restype = None
     _lib = lib
     return lib
 

@@ -469,13 +469,34 @@ inline void check_launch(int rc)
     if (rc == -1) throw RmError{RM_ERR_UNSUPPORTED, "unsupported factor count"};
     if (rc != 0) throw RmError{RM_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString((hipError_t)rc)};
 }
+// The launch ledger (tests: rm_debug_sweep_launched): successful launches per row of the table since the last reset, one counter per
+// row and precision, in the order rm_debug_sweep_variants lists the rows.  Host only; the shards of one call launch from several
+// host threads, hence the atomics (relaxed: a test reads them after its call has returned).
+constexpr int LEDGER_ROWS = 512;                          // more than either table has (272 / 143): a longer table stops being counted behind it
+std::atomic<int> g_sweep_launched[2][LEDGER_ROWS];
+template <class Args> inline std::atomic<int> *sweep_ledger() { return g_sweep_launched[std::is_same<Args, Sweep64Args>::value ? 1 : 0]; }
+template <class Args> inline void count_launch(const SweepRow<Args> *row)
+{
+    for (int u = 0, base = 0;; u++) {
+        const SweepRows<Args> r = sweep_rows<Args>(u);
+        if (!r.row) return;
+        if (row >= r.row && row < r.row + r.n) {
+            const int i = base + (int)(row - r.row);
+            if (i < LEDGER_ROWS) sweep_ledger<Args>()[i].fetch_add(1, std::memory_order_relaxed);
+            return;
+        }
+        base += r.n;
+    }
+}
 template <class Args>
 void dispatch_sweep(bool auc, bool dump, bool llds, int nsub, int NG, dim3 grid, size_t lds, hipStream_t stream, const Args &sa)
 {
     SweepKey key;
     const SweepRow<Args> *row = sweep_key<Args>(NG, sa.ngt, auc, dump, llds ? LM_LDS : (sa.buffered_lists ? LM_HBM_APPEND : LM_HBM), nsub, sa.spec, key)
                                     ? find_sweep<Args>(key) : nullptr;
-    check_launch(row ? row->launch(grid, lds, stream, sa) : -1);
+    const int rc = row ? row->launch(grid, lds, stream, sa) : -1;
+    if (rc == 0) count_launch(row);
+    check_launch(rc);
 }
 
 inline void pack_operands(const float *A, size_t lda, const float *B, size_t ldb, int n, int k, int NG, int tile_items, const int *slot_user,
@@ -3066,6 +3087,21 @@ extern "C" int rm_debug_find_sweep(int elem_bytes, int ng, int ngt, int auc, int
 extern "C" int rm_debug_supported_ng(int elem_bytes, int k)
 {
     return elem_bytes == 4 ? Prec<float>::supported_ng(k) : elem_bytes == 8 ? Prec<double>::supported_ng(k) : -1;
+}
+// the launch ledger of dispatch_sweep
+template <class Args> int debug_sweep_launched(int *counts, int cap)
+{
+    const int n = debug_sweep_variants<Args>(nullptr, 0);
+    for (int i = 0; counts && i < n && i < cap; i++) counts[i] = i < LEDGER_ROWS ? sweep_ledger<Args>()[i].load(std::memory_order_relaxed) : 0;
+    return n;
+}
+extern "C" int rm_debug_sweep_launched(int elem_bytes, int *counts, int cap)
+{
+    return elem_bytes == 4 ? debug_sweep_launched<SweepArgs>(counts, cap) : elem_bytes == 8 ? debug_sweep_launched<Sweep64Args>(counts, cap) : -1;
+}
+extern "C" void rm_debug_sweep_launched_reset(void)
+{
+    for (auto &prec : g_sweep_launched) for (auto &c : prec) c.store(0, std::memory_order_relaxed);
 }
 
 extern "C" int rm_get_timings(double *out, int n)
