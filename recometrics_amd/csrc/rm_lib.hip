@@ -207,7 +207,7 @@ struct NoiseWords {
     int first_early;         // users flagged when a first pass launches its sweep (Call::flag_count_host; for the last batch of a host
                              // call it is the word of the RANGE's context, also when that batch runs on the peer context)
     int first_final;         // ... and after that pass's k_finalize (run_call)
-    int sequential;          // flagged users as a sequential exact pass counts them (noise_exact_pass)
+    int sequential;          // flagged users as a sequential exact pass counts them (ExactPass::sequential)
     int range_early;         // host entry: flagged users of the range as the pass beside the last batch counts them
     int batch_flagged;       // host entry: users the first pass of a batch on this context flagged
 };
@@ -302,9 +302,27 @@ Ctx &peer_context(const Ctx &cx, int offset = PEER_SLOT)
     return *p;
 }
 
+// The outputs of a request, as one value (a call that writes somewhere else assigns another one).  In a host request they are the
+// caller's HOST arrays.
+template <class T> struct Outputs {
+    T *out[10] = {};                           // p, tp, r, ap, tap, ndcg, hit, rr, roc, pr
+    // optional ranking outputs
+    int *topk_idx = nullptr; T *topk_score = nullptr; long long *pos_rank = nullptr; int *status = nullptr;
+    // the same arrays from user `u` on: `per` values per user of the eight top-K metrics, K per list (`pos_rank` is indexed by test
+    // entry: the index pointers of those users carry the offset)
+    Outputs from_user(size_t u, size_t per, int K) const
+    {
+        Outputs o = *this;
+        for (int i = 0; i < 10; i++) if (out[i]) o.out[i] = out[i] + u * (i >= 8 ? 1 : per);
+        if (topk_idx) o.topk_idx = topk_idx + u * (size_t)K;
+        if (topk_score) o.topk_score = topk_score + u * (size_t)K;
+        if (status) o.status = status + u;
+        return o;
+    }
+};
 // What a caller asked for: one metric or list call as the C-ABI states it.  Its pointers are HOST pointers in a host entry (HostRange
 // stages the arrays batch by batch) and DEVICE pointers in a device entry and in every Call.
-template <class T> struct Request {
+template <class T> struct Request : Outputs<T> {
     // the score source: factors, or the caller's score matrix (rm_calc_metrics_scores_*, rm_recommend_scores_*): score of item i for user u =
     // S[u * lds + i]; there are then no factors (A, B null, k = 0) and no tie noise.  Every evaluated user is streamed: k_score_rows copies
     // its row of S, masked, where the sweep would have written it, k_pos_scores_given gathers the test items' scores, and the
@@ -316,46 +334,58 @@ template <class T> struct Request {
     const int *test_p = nullptr, *test_i = nullptr; const T *test_v = nullptr; long long nnz_test = 0;
     int K = 0; bool cumulative = false, noise = false, cold = false; int min_items_pool = 0, min_pos_test = 0;
     unsigned long long seed = 0;               // tie noise (rm_noise.hpp): the engine of user u of the request is seeded with seed + u
-    // The outputs.  In a host request they are the caller's HOST arrays: HostRange::batch_call resets every one of them in the device call
-    // it makes of the request -- an output added here must be reset there too.
-    T *out[10] = {};                           // p, tp, r, ap, tap, ndcg, hit, rr, roc, pr
-    // optional ranking outputs
-    int *topk_idx = nullptr; T *topk_score = nullptr; long long *pos_rank = nullptr; int *status = nullptr;
     // recommendation lists (rm_recommend_*): no test matrix (`test_p` is null on the device), no metric; every user with a candidate gets its
     // ordered list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
     bool reco = false;
+    Outputs<T> &outputs() { return *this; }
 };
-// one pass over the users of a request, or over a batch of them: the request (every pointer a DEVICE pointer) and the state of the pass
-template <class T> struct Call : Request<T> {
+// Which pass of a call this is (the tie noise, rm_noise.hpp, makes several of one call), and the three groups of fields that say so.
+enum PassKind {
+    PASS_ORDINARY,       // the users as they are, the scores as they are
+    PASS_FIRST,          // fp32 tie noise: everybody on the plain scores; the users the noise can touch are flagged (PassFlags)
+    PASS_EXACT,          // fp32 tie noise: a subset of the users, each with its row of noise (PassSubset; set_exact_pass)
+    PASS_NOISE_ALL       // fp64 tie noise: everybody with its row of noise
+};
+template <class T> struct PassSubset {             // who is evaluated, and with which noise
+    const unsigned char *only_users = nullptr;     // optional [m]: evaluate only these users, leave the others' outputs alone
+    const int *noise_row = nullptr; int noise_row0 = 0;      // row of each user in noise_E (null: row = user)
+    const T *noise_E = nullptr; long long noise_ld = 0;      // per-item noise rows; null = scores as they are
+    long long eval_users = -1;                     // users this pass evaluates when fewer than m (only_users given); -1 = all m
+};
+struct PassFlags {                                 // who is told about the users the noise can change
+    int *noise_flag = nullptr;                     // optional [m] out (fp32 first pass): users the noise can change
+    // fp32 tie noise, first pass: right before the sweep is launched the flags set so far (users with a TEST item in the noise
+    // zone: all of them are known by then) are copied to `flag_snapshot`, their number to `*flag_count_host` (page-locked), and
+    // `flags_event` is recorded -- the exact pass of those users can start beside the sweep (run_call)
+    int *flag_snapshot = nullptr; int *flag_count_host = nullptr; hipEvent_t flags_event = nullptr;
+    // fp32 tie noise of a host-pointer call in user batches: the batch only runs its FIRST pass and flags the users the noise can
+    // touch in this array (its slice of a range-wide one); the exact pass over all flagged users of the range follows the
+    // last batch (HostRange::exact_late) -- per batch it costs two host-side waits that keep the next batch from being enqueued
+    int *first_pass_flags = nullptr;
+};
+struct PassRows {                                  // dense train rows handed over or remembered
+    // rows built by another pass of the same call over the same users (the exact noise pass beside the first sweep reads the
+    // first pass's rows instead of building 463 MB of its own at BASELINE C2)
+    const unsigned *ext_bits = nullptr; long long ext_words = 0; bool ext_masked = false;
+    bool same_train_rows = false;                  // a later pass of the same call over the same users' rows: dense train rows may be reused
+    // decided once per call (-1 = not yet: run() asks dense_rows_fit itself) -- every pass of a call gets the answer the first one
+    // got, whatever the passes in between have allocated
+    int dense_fit = -1;
+};
+template <class T> struct PassRole : PassSubset<T>, PassFlags, PassRows { PassKind kind = PASS_ORDINARY; };
+// one pass over the users of a request, or over a batch of them: the request (every pointer a DEVICE pointer), the call's identity
+// and the role of the pass
+template <class T> struct Call : Request<T>, PassRole<T> {
     Call() = default;
     explicit Call(const Request<T> &r) : Request<T>(r) {}
     // batches of one host call share the item factors: a non-zero tag says "the packed image and the |B| bound made for this
     // tag are still valid" (set by run_host_range; 0 = always repack)
     unsigned long long items_tag = 0;
-    // tie noise (rm_noise.hpp)
-    long long user0 = 0;                           // the engine of local user u is seeded with seed + user0 + u
-    const unsigned char *only_users = nullptr;     // optional [m]: evaluate only these users, leave the others' outputs alone
-    const int *noise_row = nullptr; int noise_row0 = 0;      // row of each user in noise_E (null: row = user)
-    const T *noise_E = nullptr; long long noise_ld = 0;      // per-item noise rows; null = scores as they are
-    int *noise_flag = nullptr;                     // optional [m] out (fp32 first pass): users the noise can change
-    bool same_train_rows = false;                  // a later pass of the same call over the same users' rows: dense train rows may be reused
-    long long eval_users = -1;                     // users this pass evaluates when fewer than m (only_users given); -1 = all m
-    // fp32 tie noise, first pass: right before the sweep is launched the flags set so far (users with a TEST item in the noise
-    // zone: all of them are known by then) are copied to `flag_snapshot`, their number to `*flag_count_host` (page-locked), and
-    // `flags_event` is recorded -- the exact pass of those users can start beside the sweep (run_call)
-    int *flag_snapshot = nullptr; int *flag_count_host = nullptr; hipEvent_t flags_event = nullptr;
-    // dense train rows built by another pass of the same call over the same users (the exact noise pass beside the first sweep
-    // reads the first pass's rows instead of building 463 MB of its own at BASELINE C2)
-    const unsigned *ext_bits = nullptr; long long ext_words = 0; bool ext_masked = false;
-    // fp32 tie noise of a host-pointer call in user batches: the batch only runs its FIRST pass and flags the users the noise can
-    // touch in this array (its slice of a range-wide one); the exact pass over all flagged users of the range follows the
-    // last batch (noise_exact_pass) -- per batch it costs two host-side waits that keep the next batch from being enqueued
-    int *first_pass_flags = nullptr;
+    long long user0 = 0;                           // tie noise: the engine of local user u is seeded with seed + user0 + u
     // the CSR arrays of these users have been validated by an earlier pass of the same call (plan kernels k_check_csr_*)
     bool csr_checked = false;
-    // dense train rows: decided once per call (-1 = not yet: run() asks dense_rows_fit itself) -- every pass of a call gets the
-    // answer the first one got, whatever the passes in between have allocated
-    int dense_fit = -1;
+    // an ordinary pass of a call without noise (the only kind that keeps or reuses a split, Pipeline::make_split_key)
+    bool plain() const { return this->kind == PASS_ORDINARY && !this->noise; }
 };
 // Layout of the ten metrics of a call (Call::out): the eight top-K metrics have `per` values per user (k_metrics when cumulative,
 // else one), the two AUCs one.  The requested metrics of one user, packed, are a RECORD (what k_noise_gather writes); those of
@@ -372,12 +402,21 @@ struct MetricLayout {
     // the outputs of a call whose metric block of `users` users starts at `block`
     template <class T> void point_at(T *block, size_t users, T **out) const { for (int i = 0; i < 10; i++) out[i] = want[i] ? block + block_off(i, users) : nullptr; }
 };
-// what makes a pass an EXACT pass of the fp32 tie noise: `rows` users (those marked in `only`), each with its row of noise in E
+// The three places that give a call a role other than the ordinary one.
+// A first pass of the fp32 tie noise, flagging into `flag` [m]:
+template <class T> inline void set_first_pass(Call<T> &c, int *flag) { c.kind = PASS_FIRST; c.noise_flag = flag; }
+// the fp64 pass: a row of noise in E for every user, in user order
+template <class T> inline void set_noise_for_all(Call<T> &c, const T *E, long long ld)
+{
+    c.kind = PASS_NOISE_ALL; c.noise_row = nullptr; c.noise_row0 = 0; c.noise_E = E; c.noise_ld = ld;
+}
+// an EXACT pass of the fp32 tie noise: `rows` users (those marked in `only`), each with its row of noise in E; it tells nobody
 template <class T>
 inline void set_exact_pass(Call<T> &c, const unsigned char *only, const int *noise_row, int row0, const T *E, long long ld, int rows)
 {
-    c.only_users = only; c.noise_row = noise_row; c.noise_row0 = row0; c.noise_E = E; c.noise_ld = ld; c.eval_users = rows;
-    c.noise_flag = nullptr; c.first_pass_flags = nullptr; c.flag_snapshot = nullptr;
+    c.kind = PASS_EXACT;
+    static_cast<PassSubset<T> &>(c) = PassSubset<T>{only, noise_row, row0, E, ld, rows};
+    static_cast<PassFlags &>(c) = PassFlags{};
     c.csr_checked = true;                                            // (the first pass looked at every row)
 }
 // internal status: some CSR row is not sorted (the entry points sort a copy of the rows and run again; never returned to a caller)
@@ -1196,8 +1235,7 @@ struct Pipeline {
     bool make_split_key(SplitKey &key) const
     {
         std::memset(&key, 0, sizeof(SplitKey));
-        if (g_sw.no_split_cache || !use_side || c.reco || c.scores || c.noise || c.only_users || c.ext_bits || c.noise_E || c.noise_flag ||
-            c.first_pass_flags || c.flag_snapshot || c.items_tag != 0 || !c.test_p || m <= 0) return false;
+        if (g_sw.no_split_cache || !use_side || c.reco || c.scores || !c.plain() || c.items_tag != 0 || !c.test_p || m <= 0) return false;
         const void *arr[SPLIT_ARRAYS] = {c.train_p, c.train_i, c.test_p, c.test_i, c.test_v};
         const long long words[SPLIT_ARRAYS] = {(long long)m + 1, std::max<long long>(c.nnz_train, 0), (long long)m + 1, std::max<long long>(c.nnz_test, 0),
                                                c.test_v ? std::max<long long>(c.nnz_test, 0) * (long long)(sizeof(T) / 4) : 0};
@@ -1759,52 +1797,23 @@ void noise_make_rows(Ctx &cx, const Call<T> &c0, const NoiseGeom<T> &g, const in
                            D, g.d_ld, E, g.e_ld);
 }
 
-// The exact pass of the fp32 tie noise over the users flagged in `flag` [m]: rows of noise for them (in batches of what the memory
-// budget allows), the whole pipeline again for exactly those users.  `n_known` < 0: the number of flagged users is counted here
-// (one wait for the stream).  Returns that number; `row_user_out` (optional) receives the workspace array of their indices.
-template <class T>
-int noise_exact_pass(const Call<T> &c0, const int *flag, const int *skip, int n_known, hipStream_t stream, Ctx &cx, const int **row_user_out = nullptr)
-{
-    Workspace &ws = cx.ws;
-    const int m = c0.m;
-    const NoiseGeom<T> g(ws, c0.n);
-    int *noise_row = (int *)ws.get("noise_row", sizeof(int) * (size_t)m);
-    int *row_user = (int *)ws.get("noise_row_user", sizeof(int) * (size_t)(n_known >= 0 ? std::max(n_known, 1) : m));
-    int *counter = (int *)ws.get("noise_counter", sizeof(int));
-    unsigned char *only = (unsigned char *)ws.get("noise_only", (size_t)m);
-    HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(int), stream));
-    hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, flag, skip, noise_row, row_user, counter);
-    int n_flagged = n_known;
-    if (n_known < 0) {
-        HIP_CHECK(hipMemcpyAsync(&cx.noise_words->sequential, counter, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        n_flagged = cx.noise_words->sequential;
-    }
-    if (row_user_out) *row_user_out = row_user;
-    for (long long r0 = 0; r0 < n_flagged; r0 += g.cap) {
-        const int rows = (int)std::min<long long>(g.cap, n_flagged - r0);
-        hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, noise_row, (int)r0, (int)r0 + rows, only);
-        unsigned *D = (unsigned *)ws.get("noise_draws", sizeof(unsigned) * (size_t)rows * (size_t)g.d_ld);
-        T *E = (T *)ws.get("noise_rows", sizeof(T) * (size_t)rows * (size_t)g.e_ld);
-        noise_make_rows<T>(cx, c0, g, row_user + r0, rows, c0.train_p, c0.user0, D, E, stream);
-        Call<T> c = c0;
-        set_exact_pass<T>(c, only, noise_row, (int)r0, E, g.e_ld, rows);
-        run<T>(c, stream, cx);
-    }
-    return n_flagged;
-}
-
-// The exact pass of the fp32 tie noise BESIDE a running sweep: the users flagged by the time a first pass launches its sweep (every
-// user with a TEST item in the noise zone) are evaluated on the NOISE_SLOT context of `cx` and its high-priority stream, into
-// buffers of that context.  What the two callers share lives here -- run_call (device entry, un-ranged batches) and the host entry
-// (beside the last batch of a range); each brings its count, its dense train rows and its output pointers, calls the steps in
-// order (open, assign, rows, run_pass) and delivers the results itself.
-template <class T> struct NoiseBeside {
-    Ctx &cx;                                                         // whose `flags_ev` the pass waits for; g_last_ctx again afterwards
-    Ctx *pc = nullptr; hipStream_t ps = nullptr;                     // the NOISE_SLOT context, its stream
-    std::unique_lock<std::mutex> lock;                               // ... and its mutex, held until this object goes
+// The exact pass of the fp32 tie noise over flagged users: a row of noise for each of them, the whole pipeline again for exactly
+// those users.  One driver for its two forms:
+//   sequential  constructed on the call's own context and stream; sequential() evaluates the flagged users in pieces of what the
+//               memory budget allows (NoiseGeom::cap);
+//   beside      BESIDE a running sweep: constructed on the call's context alone and opened on its NOISE_SLOT context and that one's
+//               high-priority stream, behind `flags_ev` -- the users flagged by the time a first pass launches its sweep (every user
+//               with a TEST item in the noise zone), in one piece, into a metric block of that context (block()).  run_call (device
+//               entry, un-ranged batches) and the host entry (beside the last batch of a range) each bring their count and deliver
+//               the results themselves.
+template <class T> struct ExactPass {
+    Ctx &cx;                                                         // the call's context: whose `flags_ev` a pass beside waits for; g_last_ctx again afterwards
+    Ctx *pc = nullptr; hipStream_t ps = nullptr;                     // where the pass runs: that context, or its NOISE_SLOT context; the stream
+    std::unique_lock<std::mutex> lock;                               // beside: the NOISE_SLOT context's mutex, held until this object goes
     int *noise_row = nullptr, *row_user = nullptr; unsigned char *only = nullptr;
-    explicit NoiseBeside(Ctx &c) : cx(c) {}
+    explicit ExactPass(Ctx &c) : cx(c) {}                            // (beside: open() follows)
+    ExactPass(Ctx &c, hipStream_t stream) : cx(c), pc(&c), ps(stream) {}
+    bool beside() const { return pc != &cx; }
     void open(hipEvent_t other = nullptr)
     {
         pc = &peer_context(cx, NOISE_SLOT);
@@ -1814,32 +1823,38 @@ template <class T> struct NoiseBeside {
         HIP_CHECK(hipStreamWaitEvent(ps, cx.flags_ev, 0));           // flags, their snapshot and the dense train rows are in place
         if (other) HIP_CHECK(hipStreamWaitEvent(ps, other, 0));
     }
-    // A row for every user flagged in `flags` [m].  `known` > 0: their number; else they are counted on the pass's stream and the
-    // count is read back through `*word` (one wait for that stream).  Returns the number.
-    int assign(int m, const int *flags, int known, int *word)
+    // A row for every user flagged in `flags` [m] and not in `skip` (optional).  `known` >= 0: their number; else they are counted
+    // on the pass's stream and the count is read back through `*word` (one wait for that stream).  Returns the number.
+    int assign(int m, const int *flags, const int *skip, int known, int *word)
     {
         Workspace &pw = pc->ws;
         noise_row = (int *)pw.get("noise_row", sizeof(int) * (size_t)m);
-        row_user = (int *)pw.get("noise_row_user", sizeof(int) * (size_t)(known > 0 ? known : m));
+        row_user = (int *)pw.get("noise_row_user", sizeof(int) * (size_t)(known >= 0 ? std::max(known, 1) : m));
         int *counter = (int *)pw.get("noise_counter", sizeof(int));
         only = (unsigned char *)pw.get("noise_only", (size_t)m);
         HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(int), ps));
-        hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, flags, (const int *)nullptr, noise_row, row_user, counter);
-        if (known > 0) return known;
+        hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, flags, skip, noise_row, row_user, counter);
+        if (known >= 0) return known;
         HIP_CHECK(hipMemcpyAsync(word, counter, sizeof(int), hipMemcpyDeviceToHost, ps));
         HIP_CHECK(hipStreamSynchronize(ps));
         return *word;
     }
-    // The noise rows of the `rows_n` flagged users and the fields of their exact pass in `c` (a call over all m users).  Dense train
-    // rows: the first pass's when `cx` still holds them for exactly these users, or with `own_rows` rows built here for the
-    // flagged users alone (train items only; fp32, when they fit the PEER workspace).
-    void rows(Call<T> &c, const NoiseGeom<T> &g, int rows_n, bool own_rows)
+    // the metric block of a pass that must not write into the call's outputs, [metric][users x width], in the pass's workspace
+    void block(Call<T> &c, const MetricLayout &lay) const
+    {
+        lay.point_at((T *)pc->ws.get("o_exact", sizeof(T) * std::max<size_t>(lay.block_size((size_t)c.m), 1)), (size_t)c.m, c.out);
+    }
+    // The flagged users of rows [r0, r0 + rows) through the pipeline, as passes of call `c` (over all its m users): their noise rows,
+    // then run().  Dense train rows of a pass beside: the first pass's when `cx` still holds them for exactly these users, or with
+    // `own_rows` rows built here for the flagged users alone (train items only; fp32, when they fit the PEER workspace).  A
+    // sequential pass finds the rows of its own context itself (Call::same_train_rows).
+    void step(Call<T> c, const NoiseGeom<T> &g, long long r0, int rows, bool own_rows = false)
     {
         Workspace &pw = pc->ws;
         const int m = c.m, n = c.n;
-        hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, noise_row, 0, rows_n, only);
-        unsigned *D = (unsigned *)pw.get("noise_draws", sizeof(unsigned) * (size_t)rows_n * (size_t)g.d_ld);
-        T *E = (T *)pw.get("noise_rows", sizeof(T) * (size_t)rows_n * (size_t)g.e_ld);
+        hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, noise_row, (int)r0, (int)r0 + rows, only);
+        unsigned *D = (unsigned *)pw.get("noise_draws", sizeof(unsigned) * (size_t)rows * (size_t)g.d_ld);
+        T *E = (T *)pw.get("noise_rows", sizeof(T) * (size_t)rows * (size_t)g.e_ld);
         const long long words = dense_row_words(n);
         unsigned *bits = nullptr;
         if (own_rows) {
@@ -1851,24 +1866,28 @@ template <class T> struct NoiseBeside {
                 c.ext_bits = bits; c.ext_words = words; c.ext_masked = false;
             }
             c.dense_fit = fit ? 1 : 0;
-        } else if (cx.dense.built_by(cx.ws, c.items_tag, c.train_p, m)) {
+        } else if (beside() && cx.dense.built_by(cx.ws, c.items_tag, c.train_p, m)) {
             c.ext_bits = cx.dense.rows(cx.ws); c.ext_words = cx.dense.words; c.ext_masked = cx.dense.masked;             // the first pass's rows
         }
-        noise_make_rows<T>(own_rows ? *pc : cx, c, g, row_user, rows_n, c.train_p, c.user0, D, E, ps, bits, words);
-        set_exact_pass<T>(c, only, noise_row, 0, E, g.e_ld, rows_n);
-    }
-    void run_pass(const Call<T> &c)
-    {
-        // (whatever fails in there -- the peer context duplicates workspace under memory pressure --, nothing of it may still be
-        // reading this context's buffers (flag snapshot, dense train rows, A / B) when the error reaches the caller)
+        noise_make_rows<T>(own_rows ? *pc : cx, c, g, row_user + r0, rows, c.train_p, c.user0, D, E, ps, bits, words);
+        set_exact_pass<T>(c, only, noise_row, (int)r0, E, g.e_ld, rows);
+        // (beside: whatever fails in there -- the peer context duplicates workspace under memory pressure --, nothing of it may still
+        // be reading the call's context's buffers (flag snapshot, dense train rows, A / B) when the error reaches the caller)
         try { run<T>(c, ps, *pc); }
         catch (...) {
-            sync();
-            if (pc->side_stream) (void)hipStreamSynchronize(pc->side_stream);
+            if (beside()) { sync(); if (pc->side_stream) (void)hipStreamSynchronize(pc->side_stream); }
             g_last_ctx = &cx;
             throw;
         }
         g_last_ctx = &cx;                                            // rm_get_timings reports the main pass, not the small exact one
+    }
+    // the sequential pass: every flagged user, in pieces of `cap` rows; returns their number
+    int sequential(const Call<T> &c, const int *flags, const int *skip, int known, int *word)
+    {
+        const NoiseGeom<T> g(pc->ws, c.n);
+        const int n_flagged = assign(c.m, flags, skip, known, word);
+        for (long long r0 = 0; r0 < n_flagged; r0 += g.cap) step(c, g, r0, (int)std::min<long long>(g.cap, n_flagged - r0));
+        return n_flagged;
     }
     void sync() { if (pc) (void)hipStreamSynchronize(ps); }
 };
@@ -1887,9 +1906,9 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     Workspace &ws = cx.ws;
     const int m = c0.m;
     cx.need_noise_words();
-    if (sizeof(T) == 4 && c0.first_pass_flags) {                    // a batch of a host-pointer call: see Call::first_pass_flags
+    if (sizeof(T) == 4 && c0.first_pass_flags) {                    // a batch of a host-pointer call: see PassFlags::first_pass_flags
         Call<T> c1 = c0;
-        c1.noise_flag = c0.first_pass_flags;
+        set_first_pass(c1, c0.first_pass_flags);
         run<T>(c1, stream, cx);
         return;
     }
@@ -1902,13 +1921,12 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
             const int mb = (int)std::min<long long>(g.cap, m - b0);
             Call<T> c = c0;
             c.A = c0.A + (size_t)b0 * c0.lda; c.m = mb; c.train_p = c0.train_p + b0; c.test_p = c0.test_p + b0; c.user0 = c0.user0 + b0;
-            for (int i = 0; i < 10; i++) if (c0.out[i]) c.out[i] = c0.out[i] + (size_t)b0 * lay.width(i);
-            if (c0.topk_idx) { c.topk_idx = c0.topk_idx + (size_t)b0 * c0.K; c.topk_score = c0.topk_score + (size_t)b0 * c0.K; c.status = c0.status + b0; }
+            c.outputs() = c0.from_user((size_t)b0, lay.per, c0.K);
             if (c0.only_users) c.only_users = c0.only_users + b0;
             unsigned *D = (unsigned *)ws.get("noise_draws", sizeof(unsigned) * (size_t)mb * (size_t)g.d_ld);
             T *E = (T *)ws.get("noise_rows", sizeof(T) * (size_t)mb * (size_t)g.e_ld);
             noise_make_rows<T>(cx, c0, g, nullptr, mb, c.train_p, c.user0, D, E, stream);
-            c.noise_E = E; c.noise_ld = g.e_ld; c.noise_row = nullptr; c.noise_row0 = 0;
+            set_noise_for_all(c, E, g.e_ld);
             run<T>(c, stream, cx);
         }
         return;
@@ -1916,11 +1934,11 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     int *flag = (int *)ws.get("noise_flag", sizeof(int) * (size_t)m);
     HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int) * (size_t)m, stream));
     Call<T> c1 = c0;
-    c1.noise_flag = flag;
+    set_first_pass(c1, flag);
     // Every user the noise can touch through a TEST item in the zone -- in practice all the flagged users -- is known once the
     // positives are scored, before the first sweep starts: their exact pass (noise rows, a small sweep, two dozen short
-    // launches: 1.4 ms at BASELINE C2) runs on the PEER context and its stream BESIDE the first sweep, writes into buffers of its
-    // own, and a scatter behind both puts its results over the first pass's.  Users flagged only by the first pass's
+    // launches: 1.4 ms at BASELINE C2) runs on the PEER context and its stream BESIDE the first sweep, writes into a metric block of
+    // its own, and a scatter behind both puts its results over the first pass's.  Users flagged only by the first pass's
     // k_finalize (a top-K score in the zone) get the sequential exact pass below, as does everybody when the ranking outputs
     // of rm_rank_* are wanted.
     const bool beside = !c0.topk_idx && !c0.only_users && !g_sw.noise_sequential;
@@ -1932,7 +1950,7 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     }
     Plan *plan = (Plan *)ws.get("plan", sizeof(Plan));
     int n_beside = 0;
-    NoiseBeside<T> nb(cx);
+    ExactPass<T> nb(cx);
     run<T>(c1, stream, cx);
     // The exact pass beside the first sweep: enqueued right behind the first pass, on the NOISE_SLOT context's HIGH-PRIORITY streams
     // (create_stream) -- at normal priority its kernels would only be served when the sweep, which fills every compute unit, drains.
@@ -1943,18 +1961,12 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
         const int n_early = cx.noise_words->first_early;
         if (n_early > 0 && n_early <= g.cap) {
             nb.open();
-            nb.assign(m, snap, n_early, nullptr);
+            nb.assign(m, snap, nullptr, n_early, nullptr);
             Call<T> c = c0;
-            nb.rows(c, g, n_early, false);
-            static const char *tnames[10] = {"t_p", "t_tp", "t_r", "t_ap", "t_tap", "t_ndcg", "t_hit", "t_rr", "t_roc", "t_pr"};
+            nb.block(c, lay);
             ScatterArgs<T> sc{};
-            for (int i = 0; i < 10; i++) {
-                sc.width[i] = (int)lay.width(i);
-                sc.dst[i] = c0.out[i];
-                c.out[i] = c0.out[i] ? (T *)nb.pc->ws.get(tnames[i], sizeof(T) * (size_t)m * lay.width(i)) : nullptr;
-                sc.src[i] = c.out[i];
-            }
-            nb.run_pass(c);
+            for (int i = 0; i < 10; i++) { sc.width[i] = (int)lay.width(i); sc.dst[i] = c0.out[i]; sc.src[i] = c.out[i]; }
+            nb.step(c, g, 0, n_early);
             HIP_CHECK(hipEventRecord(cx.pass_ev, nb.ps));
             HIP_CHECK(hipStreamWaitEvent(stream, cx.pass_ev, 0));    // behind the first pass (stream order) AND the exact one
             hipLaunchKernelGGL(k_noise_scatter<T>, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, snap, sc);
@@ -1971,7 +1983,7 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
         if (n_flagged <= 0) return false;
         Call<T> c = c0;
         c.same_train_rows = true;
-        noise_exact_pass<T>(c, flag, n_beside > 0 ? (const int *)snap : (const int *)nullptr, n_flagged, stream, cx);
+        ExactPass<T>(cx, stream).sequential(c, flag, n_beside > 0 ? (const int *)snap : (const int *)nullptr, n_flagged, nullptr);
         return true;
     };
     if (defer) *defer = tail;
@@ -2191,7 +2203,7 @@ template <class T> struct HostRange {
     std::lock_guard<std::mutex> lk;
     ItemUpload<T> items;
     std::unique_lock<std::mutex> peer_lock;
-    NoiseBeside<T> bes;
+    ExactPass<T> bes;
     bool bes_ran = false; int bes_count = 0; T *bes_hx = nullptr; int *bes_hu = nullptr;     // what the pass beside the last batch left in page-locked memory
 
     const Request<T> &h; const int u0, m, n, k, K; Ctx &cx; Workspace &ws; hipStream_t stream, up = nullptr;
@@ -2203,7 +2215,7 @@ template <class T> struct HostRange {
     T *dB = nullptr, *dA = nullptr, *dtev = nullptr; int *dtrp = nullptr, *dtep = nullptr, *dtri = nullptr, *dtei = nullptr;
     std::vector<int> rb;                                              // rebased index pointers (only when the range does not start at 0)
     const int *trp = nullptr, *tep = nullptr;
-    int *d_topk_idx = nullptr, *d_status = nullptr; T *d_topk_score = nullptr; long long *d_pos_rank = nullptr;
+    Outputs<T> d_rank;                                                // the ranking outputs of the range on the device (rm_rank_*, lists)
     // plan_batches()
     std::vector<long long> cuts; int n_batches = 0;
     Ctx *ctxs[2]; hipStream_t streams[2]; bool two_ctx = false;
@@ -2255,10 +2267,10 @@ template <class T> struct HostRange {
         HIP_CHECK(hipMemcpyAsync(dtrp, trp, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
         if (dtep) HIP_CHECK(hipMemcpyAsync(dtep, tep, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
         if (h.topk_idx) {
-            d_topk_idx = (int *)ws.get("o_topk_idx", sizeof(int) * (size_t)m * K);
-            if (h.topk_score) d_topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
-            if (h.pos_rank) d_pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
-            d_status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
+            d_rank.topk_idx = (int *)ws.get("o_topk_idx", sizeof(int) * (size_t)m * K);
+            if (h.topk_score) d_rank.topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
+            if (h.pos_rank) d_rank.pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
+            d_rank.status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
         }
         return true;
     }
@@ -2337,7 +2349,7 @@ template <class T> struct HostRange {
         stamp("batch 0 rows enqueued");
     }
     // users [b0, b0 + mb) of the range as a call on the staged arrays: the request, rebased -- everything but the outputs (the request's
-    // are the caller's host arrays: enqueue_batch and exact_block point a call at device arrays of its own) and the tie noise's flags
+    // are the caller's host arrays: enqueue_batch and ExactPass::block point a call at device arrays of its own) and the tie noise's flags
     Call<T> batch_call(long long b0, int mb) const
     {
         Call<T> c(h);
@@ -2345,7 +2357,7 @@ template <class T> struct HostRange {
         if (h.scores) { c.S = cur_S; c.lds = (size_t)n; c.A = nullptr; c.B = nullptr; }
         c.train_p = dtrp + b0; c.train_i = dtri; c.nnz_train = nnz_tr;
         c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
-        std::fill_n(c.out, 10, nullptr); c.topk_idx = nullptr; c.topk_score = nullptr; c.pos_rank = nullptr; c.status = nullptr;
+        c.outputs() = Outputs<T>{};
         c.items_tag = tag; c.user0 = (long long)u0 + b0;
         return c;
     }
@@ -2361,10 +2373,10 @@ template <class T> struct HostRange {
         if (lay.rec_w) HIP_CHECK(hipMemcpyAsync(hblocks[which], dblocks[which], sizeof(T) * lay.block_size((size_t)mb), hipMemcpyDeviceToHost, bs));
         if (h.topk_idx) {
             const long long e0 = tep[b0], e1 = tep[b0 + mb];          // this batch's test entries (range-relative)
-            HIP_CHECK(hipMemcpyAsync(h.topk_idx + ((size_t)u0 + b0) * K, d_topk_idx + (size_t)b0 * K, sizeof(int) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
-            if (h.topk_score) HIP_CHECK(hipMemcpyAsync(h.topk_score + ((size_t)u0 + b0) * K, d_topk_score + (size_t)b0 * K, sizeof(T) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
-            HIP_CHECK(hipMemcpyAsync(h.status + u0 + b0, d_status + b0, sizeof(int) * (size_t)mb, hipMemcpyDeviceToHost, bs));
-            if (h.pos_rank && e1 > e0) HIP_CHECK(hipMemcpyAsync(h.pos_rank + te0 + e0, d_pos_rank + e0, sizeof(long long) * (size_t)(e1 - e0), hipMemcpyDeviceToHost, bs));
+            HIP_CHECK(hipMemcpyAsync(h.topk_idx + ((size_t)u0 + b0) * K, d_rank.topk_idx + (size_t)b0 * K, sizeof(int) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
+            if (h.topk_score) HIP_CHECK(hipMemcpyAsync(h.topk_score + ((size_t)u0 + b0) * K, d_rank.topk_score + (size_t)b0 * K, sizeof(T) * (size_t)mb * K, hipMemcpyDeviceToHost, bs));
+            HIP_CHECK(hipMemcpyAsync(h.status + u0 + b0, d_rank.status + b0, sizeof(int) * (size_t)mb, hipMemcpyDeviceToHost, bs));
+            if (h.pos_rank && e1 > e0) HIP_CHECK(hipMemcpyAsync(h.pos_rank + te0 + e0, d_rank.pos_rank + e0, sizeof(long long) * (size_t)(e1 - e0), hipMemcpyDeviceToHost, bs));
         }
     }
 
@@ -2401,11 +2413,8 @@ template <class T> struct HostRange {
         cur_S = dS[bi & 1];
         Call<T> c = batch_call(b0, mb);
         f.b0 = b0; f.mb = mb;
+        c.outputs() = d_rank.from_user((size_t)b0, lay.per, K);      // (the ranking outputs of rm_rank_* and of the lists, when asked for)
         lay.point_at(dblocks[which], (size_t)mb, c.out);
-        if (h.topk_idx) {
-            c.topk_idx = d_topk_idx + (size_t)b0 * K; c.topk_score = d_topk_score ? d_topk_score + (size_t)b0 * K : nullptr;
-            c.pos_rank = d_pos_rank; c.status = d_status + b0;
-        }
         if (range_noise) c.first_pass_flags = range_flag + b0;
         const bool snap_here = range_noise && bi == n_batches - 1;
         if (snap_here) {
@@ -2430,9 +2439,8 @@ template <class T> struct HostRange {
     void finish_all() { const int older = two_ctx ? ((n_batches - 2) & 1) : 0; finish(older); finish(older ^ 1); g_last_ctx = &cx; }
 
     // ---- fp32 tie noise over the whole range (see `range_noise` in plan_batches) ----
-    // every user of the range; the metric block of an exact pass, [metric][users of the range x width], in workspace `w`
+    // every user of the range (an exact pass over it writes into a metric block of its own, ExactPass::block)
     Call<T> range_call() const { Call<T> c = batch_call(0, m); c.csr_checked = true; return c; }      // (every batch has looked at its rows)
-    void exact_block(Call<T> &c, Workspace &w) const { lay.point_at((T *)w.get("o_exact", sizeof(T) * std::max<size_t>(lay.block_size((size_t)m), 1)), (size_t)m, c.out); }
     // an exact pass's results leave the device packed: one record of `lay.rec_w` values per evaluated user (k_noise_gather)
     void gather_exact(Ctx &gc, const Call<T> &c, const int *row_user, int count, hipStream_t st, T *&hx, int *&hu)
     {
@@ -2468,13 +2476,12 @@ template <class T> struct HostRange {
         // (the earlier batches' flags as they stand: a flag their k_finalize sets later is the sequential pass's, below)
         if (b0_last > 0) HIP_CHECK(hipMemcpyAsync(range_snap, range_flag, sizeof(int) * (size_t)b0_last, hipMemcpyDeviceToDevice, bes.ps));
         // (the wait in there: the last batch's positives are scored; its sweep has just been launched)
-        const int n_early = bes.assign(m, range_snap, -1, &cx.noise_words->range_early);
+        const int n_early = bes.assign(m, range_snap, nullptr, -1, &cx.noise_words->range_early);
         const NoiseGeom<T> g(bes.pc->ws, n);
         if (n_early <= 0 || n_early > g.cap) return;                  // nobody, or more rows than the budget holds at once: the sequential pass
         Call<T> c = range_call();
-        bes.rows(c, g, n_early, true);                                // rows of the flagged users alone, train items only
-        exact_block(c, bes.pc->ws);
-        bes.run_pass(c);
+        bes.block(c, lay);
+        bes.step(c, g, 0, n_early, true);                             // dense rows of the flagged users alone, train items only
         gather_exact(*bes.pc, c, bes.row_user, n_early, bes.ps, bes_hx, bes_hu);
         bes_ran = true; bes_count = n_early;
     }
@@ -2490,17 +2497,17 @@ template <class T> struct HostRange {
         }
         // into a metric block of its own, from which the host takes the flagged users' values
         Call<T> c = range_call();
-        exact_block(c, ws);
+        ExactPass<T> late_pass(cx, stream);
+        late_pass.block(c, lay);
         // (every batch reports how many users its first pass flagged: when the pass beside the last batch has seen them all --
         // the usual case -- nothing is left to look for)
         const long long late = flagged_total - (bes_ran ? bes_count : 0);
         if (late <= 0) return;
-        const int *row_user = nullptr;
-        const int n_flagged = noise_exact_pass<T>(c, range_flag, bes_ran ? (const int *)range_snap : (const int *)nullptr, -1, stream, cx, &row_user);
+        const int n_flagged = late_pass.sequential(c, range_flag, bes_ran ? (const int *)range_snap : (const int *)nullptr, -1, &cx.noise_words->sequential);
         stamp("exact pass enqueued");
         if (n_flagged <= 0) return;
         T *hx = nullptr; int *hu = nullptr;
-        gather_exact(cx, c, row_user, n_flagged, stream, hx, hu);
+        gather_exact(cx, c, late_pass.row_user, n_flagged, stream, hx, hu);
         HIP_CHECK(hipStreamSynchronize(stream));
         scatter_exact(hx, hu, n_flagged);
         stamp("exact pass scattered");
@@ -2800,7 +2807,12 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
 // The four families are two score sources -- factors, or the caller's score matrix -- times two kinds of request, and the host and the
 // device form of a family state the same request: the device form adds the lengths of the index arrays (the host form reads them from the
 // index pointers) and a stream, the host form the threads of the fall-back sort.
-template <class T> Request<T> from_factors(const T *A, size_t lda, const T *B, size_t ldb, int k) { return Request<T>{A, lda, B, ldb, k}; }
+template <class T> Request<T> from_factors(const T *A, size_t lda, const T *B, size_t ldb, int k)
+{
+    Request<T> r;
+    r.A = A; r.lda = lda; r.B = B; r.ldb = ldb; r.k = k;
+    return r;
+}
 template <class T> Request<T> from_scores(const T *S, size_t lds)
 {
     Request<T> r;

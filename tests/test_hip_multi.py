@@ -415,6 +415,62 @@ def test_noise_and_batch_pipelines_agree(hip, env, monkeypatch):
         assert_same_bits(g, w, "%s under %s" % (name, env))
 
 
+def _late_flagged_problem():
+    """fp32, 3,000 users x 900 items, all scores of one sign per user: B = |B| with a few all-zero item rows, and every third user has
+    A = -|A| -- its non-zero items score well below zero, so its top-K is made of the exactly-zero items.  Every second one of those
+    users loses the zero items of its test row (one entry always stays): the tie noise's first pass flags it only in k_finalize."""
+    from recometrics_amd.synth import make_problem
+    pr = make_problem(3000, 900, 12, np.float32, mean_c=40, seed=23)
+    B = np.abs(pr["B"])
+    zero = np.random.default_rng(4).random(900) < 0.05
+    B[zero] = 0
+    A = pr["A"].copy()
+    A[::3] = -np.abs(A[::3])
+    tep, tei, tev = pr["test"]
+    keep = np.ones(tei.shape[0], bool)
+    for u in range(0, 3000, 6):
+        row = slice(int(tep[u]), int(tep[u + 1]))
+        k = ~zero[tei[row]]
+        if not k.any():
+            k[0] = True
+        keep[row] = k
+    new_p = np.zeros_like(tep)
+    np.cumsum(np.bincount(np.repeat(np.arange(3000), np.diff(tep))[keep], minlength=3000), out=new_p[1:])
+    return {"A": A, "B": B, "train": pr["train"], "test": (new_p, tei[keep], tev[keep])}
+
+
+def test_users_flagged_by_the_top_k_alone_get_their_exact_pass(hip, oracle, monkeypatch):
+    """fp32 tie noise, K = 8, all ten metrics: users the first pass flags LATE ONLY -- a top-K score in the noise zone (|s| < 2^-14), no
+    test item there -- are not known when the pass beside the sweep starts: they get the sequential pass behind it, which must skip
+    the users evaluated beside (the skip mask: the flag snapshot) and count the others.  Two legs against the oracle: one batch (the
+    device entry's pass beside the first sweep, its scatter on the device, then the late pass), and three batches on two contexts
+    (the pass beside the last batch, then the late pass over the range with the range's snapshot as the mask).
+    What this test sees: a user flagged late only has no test item in the zone, and the noise does not move the rank of a test item
+    outside the zone -- its metric values are the same with and without the noise.  So the test guards the WIRING: the right users
+    get the right rows, and nobody else's outputs are overwritten.  It does not guard the noise values: those are pinned by
+    test_tie_noise_rankings_equal_the_oracle and the g9_* fixtures."""
+    from _parity import _check_against_oracle
+    pr = _late_flagged_problem()
+    K, zone = 8, 2.0 ** -14
+    trp, tri = pr["train"]
+    tep, tei, _ = pr["test"]
+    S = pr["A"].astype(np.float64) @ pr["B"].astype(np.float64).T
+    in_zone = np.abs(S) < zone
+    users = np.repeat(np.arange(3000), np.diff(tep))
+    early = np.bincount(users[in_zone[users, tei]], minlength=3000) > 0
+    cand = np.where(in_zone, 0.0, S)                       # (the zone's scores as one value: all that matters is whether one is among the best K)
+    cand[np.repeat(np.arange(3000), np.diff(trp)), tri] = -np.inf
+    top = np.argpartition(-cand, K, axis=1)[:, :K]
+    kth = np.take_along_axis(cand, top, axis=1).min(axis=1)
+    late = ~early & ((in_zone & (cand >= kth[:, None]) & np.isfinite(cand)).any(axis=1))
+    assert (np.diff(tep) > 0).all(), "every user has a test item"
+    assert early.sum() >= 200 and late.sum() >= 200, "flagged early: %d, late only: %d" % (early.sum(), late.sum())
+    seed = 2 ** 34 + 1
+    _check_against_oracle(hip, oracle, pr, K, noise=True, seed=seed)
+    monkeypatch.setenv("RM_BATCH_USERS", "1024")
+    _check_against_oracle(hip, oracle, pr, K, noise=True, seed=seed)
+
+
 @pytest.mark.parametrize("noise", [False, True])
 def test_k_metrics_beyond_the_lists_when_memory_sizes_the_batches(hip, monkeypatch, noise):
     """k_metrics > 256 with a memory budget that BINDS: RM_DEBUG_FREE_MB makes the library see a device with 3 GB (what its
