@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from _parity import NT, TOL, _check_against_oracle, _reference, hip_calc
-from _util import assert_close, assert_same_bits, same_bits
+from _util import assert_close, assert_roc, assert_same_bits, same_bits
 from oracle.ties import tie_pairs_per_user
 
 F32, F64 = np.float32, np.float64
@@ -276,13 +276,13 @@ def check_request(hip, oracle, pr, K, dtype, req, **kw):
     single = None
     for cum in (False, True):
         what = "%s K=%d %s %s cumulative=%s %s" % (pr.name, K, np.dtype(dtype).name, req_id(req), cum, kw)
-        # 1. the oracle, bitwise (ROC-AUC, formed in x87 long double by the reference and in fp64 here: the project's TOL)
+        # 1. the oracle, bitwise (ROC-AUC, formed in x87 long double by the reference and in fp64 here: an ulp, _util.roc_tol)
         want = oracle.calc(pr["A"], pr["B"], pr["train"], pr["test"], K, metrics=req, cumulative=cum, dtype=dtype, nthreads=NT, **kw)
         got = hip_calc(hip, pr["A"], pr["B"], pr["train"], pr["test"], K, metrics=req, cumulative=cum, dtype=dtype, **kw)
         assert set(got) == set(want) and len(got) == len(req), what
         for name in want:
             if name == "ROC_AUC":
-                assert_close(got[name], want[name], TOL, what + ": " + name)
+                assert_roc(got[name], want[name], dtype, what + ": " + name)
             else:
                 assert_same_bits(got[name], want[name], what + ": " + name)
         # 2. the compiled reference on what it defines: who is NaN -- always; the values -- where no exact ties are planted (the

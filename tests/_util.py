@@ -44,6 +44,24 @@ def assert_same_bits(got, want, what=""):
             what, (~ok).sum(), ok.size, [(tuple(i), got[tuple(i)], want[tuple(i)]) for i in bad]))
 
 
+def roc_tol(dtype):
+    """ROC-AUC of the device against the ORACLE on the same inputs: the machine epsilon of the output type.
+
+    Both sides form 1 - x / y from the same integers -- x = the rank sum less P (P + 1) / 2, y = P x negatives, exact on either
+    side -- the device in fp64, the oracle (as the reference) in x87 long double, rounded once to the output type.  fp64: the
+    device's quotient is within 1/2 ulp(q) <= 2^-54 of x / y (q <= 1) and its difference within another 1/2 ulp(result) <= 2^-54;
+    the oracle's single rounding of the 64-bit-mantissa result adds 1/2 ulp(result) <= 2^-54 (and 2^-64 before it): less than
+    2^-52 in all.  fp32: the two values, at most 2^-52 apart, are each rounded to float: one float ulp <= 2^-23 at the most.
+    Relative beyond magnitude 1 (assert_close): a user whose test items are all train items gets ~ -2e14 from the formula."""
+    return 2.0 ** -23 if np.dtype(dtype) == np.float32 else 2.0 ** -52
+
+
+def assert_roc(got, want, dtype, what=""):
+    """ROC-AUC against the oracle: the same users NaN, every other within roc_tol(dtype), relative beyond magnitude 1"""
+    assert got.dtype == np.dtype(dtype) and want.dtype == np.dtype(dtype), (what, got.dtype, want.dtype)
+    assert_close(got, want, roc_tol(dtype), what)
+
+
 def assert_close(got, want, tol, what=""):
     assert got.shape == want.shape, (what, got.shape, want.shape)
     nan_g, nan_w = np.isnan(got), np.isnan(want)

@@ -13,7 +13,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402
-from _util import assert_close  # noqa: E402
+from _util import assert_close, assert_roc  # noqa: E402
 
 
 def _blocks(m, K, dtype):
@@ -61,7 +61,7 @@ def test_the_benchmark_inputs_are_the_same_from_run_to_run():
 @pytest.mark.gpu
 def test_plain_run_dumps_what_the_timed_steps_computed(tmp_path):
     """A plain run: the headline line with --steps timed steps and nothing of --full; its dump holds the metric block of the
-    workload it timed, within 1e-5 of the oracle on the same inputs"""
+    workload it timed, within 1e-5 of the oracle on the same inputs (ROC-AUC: within a float ulp, _util.roc_tol)"""
     from oracle.oracle import NAMES, Oracle
     from recometrics_amd.synth import CONFIGS
     out = tmp_path / "dump"
@@ -85,4 +85,7 @@ def test_plain_run_dumps_what_the_timed_steps_computed(tmp_path):
         got = np.load(out / (name + ".npy"))
         w = want[NAMES[short]]
         assert got.dtype == np.float32, name
-        assert_close(got, w, 1e-5, name)
+        if short == "roc":
+            assert_roc(got, w, np.float32, name)
+        else:
+            assert_close(got, w, 1e-5, name)

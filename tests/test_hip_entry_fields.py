@@ -4,7 +4,7 @@ Every scalar of the request takes a value that is not its default -- cumulative 
 min_pos_test = 0, tie noise on with seed 12345 -- so that a field which does not reach HostRange::batch_call, or which a builder of
 csrc/rm_lib.hip resets, changes a bit somewhere.  Each family is run (a) through its host entry in one batch, (b) through its host entry
 in three batches and (c) through its device entry; the three must agree in every bit with each other and with the CPU oracle (ROC-AUC
-against the oracle at the project's TOL: x87 long double there).
+against the oracle within an ulp, _util.roc_tol: x87 long double there).
 
 The tie problem of tests/_requests.py (thousands of users whose lists only the noise orders), 2,500 users x 600 items x 16 factors,
 K = 5: the factor path rounds RM_BATCH_USERS to 1,024 users, so 2,500 is the smallest m that gives three batches; the score path
@@ -19,9 +19,9 @@ import functools
 import numpy as np
 import pytest
 
-from _parity import NT, TOL, hip_calc
+from _parity import NT, hip_calc
 from _requests import replace_rows, tie_problem
-from _util import assert_close, assert_same_bits, same_bits
+from _util import assert_roc, assert_same_bits, same_bits
 from test_hip_recommend import check_lists, expected_lists
 from test_hip_recommend_scores import canonical
 from test_hip_scores import oracle_on_scores, scores_calc
@@ -136,7 +136,7 @@ def assert_metrics(got, want, what, oracle=False):
     assert set(got) == set(want) and len(got) == 10, what
     for name in want:
         if oracle and name == "ROC_AUC":
-            assert_close(got[name], want[name], TOL, "%s: %s" % (what, name))
+            assert_roc(got[name], want[name], want[name].dtype, "%s: %s" % (what, name))
         else:
             assert_same_bits(got[name], want[name], "%s: %s" % (what, name))
 

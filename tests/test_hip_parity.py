@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from _util import assert_close, assert_same_bits, golden_cases, load_golden
+from _util import assert_close, assert_roc, assert_same_bits, golden_cases, load_golden
 from _util import same_bits as _util_same_bits
 from _parity import NT, TOL, _check_against_oracle, _reference, hip_calc
 from oracle.ties import tie_pairs_per_user
@@ -389,8 +389,9 @@ def test_tie_noise_rankings_equal_the_oracle(hip, oracle, dtype, budget, monkeyp
         want = oracle.calc(pr["A"], pr["B"], pr["train"], pr["test"], 10, cumulative=cumulative, dtype=dtype, nthreads=NT, noise=True, seed=seed)
         got = hip_calc(hip, pr["A"], pr["B"], pr["train"], pr["test"], 10, cumulative=cumulative, dtype=dtype, noise=True, seed=seed)
         for name in want:
-            assert_close(got[name], want[name], TOL, name)
-            if name != "ROC_AUC":
+            if name == "ROC_AUC":
+                assert_roc(got[name], want[name], dtype, name)
+            else:
                 assert_same_bits(got[name], want[name], "%s cumulative=%s (bitwise, noise on)" % (name, cumulative))
         ref = _reference()
         if ref is not None:
@@ -452,7 +453,11 @@ def test_random_shapes_and_options(hip, oracle):
             want = oracle.calc(pr["A"], pr["B"], pr["train"], pr["test"], K, cumulative=cumulative, dtype=dtype, nthreads=NT, **kw)
             got = hip_calc(hip, pr["A"], pr["B"], pr["train"], pr["test"], K, cumulative=cumulative, dtype=dtype, **kw)
             for name in want:
-                assert_close(got[name], want[name], TOL, "%s %s m=%d n=%d k=%d K=%d %s" % (name, dtype.__name__, m, n, k, K, kw))
+                what = "%s %s m=%d n=%d k=%d K=%d %s" % (name, dtype.__name__, m, n, k, K, kw)
+                if name == "ROC_AUC":
+                    assert_roc(got[name], want[name], dtype, what)
+                else:
+                    assert_close(got[name], want[name], TOL, what)
 
 
 def test_heavy_users_many_positives(hip, oracle):
@@ -471,7 +476,11 @@ def test_edge_users_block(hip, oracle):
                 want = oracle.calc(inp["A"], inp["B"], inp["train"], inp["test"], K, cumulative=cumulative, cold=cold)
                 got = hip_calc(hip, inp["A"], inp["B"], inp["train"], inp["test"], K, cumulative=cumulative, cold=cold)
                 for name in want:
-                    assert_close(got[name], want[name], TOL, "%s K=%d cold=%s cum=%s" % (name, K, cold, cumulative))
+                    what = "%s K=%d cold=%s cum=%s" % (name, K, cold, cumulative)
+                    if name == "ROC_AUC":
+                        assert_roc(got[name], want[name], np.float32, what)
+                    else:
+                        assert_same_bits(got[name], want[name], what)
 
 
 def test_metric_subsets(hip, oracle):
@@ -482,7 +491,10 @@ def test_metric_subsets(hip, oracle):
         got = hip_calc(hip, pr["A"], pr["B"], pr["train"], pr["test"], 6, metrics=metrics)
         assert set(got) == set(want)
         for name in want:
-            assert_close(got[name], want[name], TOL, "%s of %s" % (name, metrics))
+            if name == "ROC_AUC":
+                assert_roc(got[name], want[name], np.float32, "%s of %s" % (name, metrics))
+            else:
+                assert_same_bits(got[name], want[name], "%s of %s" % (name, metrics))
 
 
 def test_python_api_drop_in(hip, oracle):
@@ -502,7 +514,10 @@ def test_python_api_drop_in(hip, oracle):
     assert all(dt == np.float32 for dt in df.dtypes)
     want = oracle.calc(pr["A"], pr["B"], pr["train"], pr["test"], 3)
     for col, key in zip(df.columns, want):
-        assert_close(df[col].to_numpy(), want[key], TOL, col)
+        if key == "ROC_AUC":
+            assert_roc(df[col].to_numpy(), want[key], np.float32, col)
+        else:
+            assert_close(df[col].to_numpy(), want[key], TOL, col)
     d = calc_reco_metrics(Xtr, Xte, pr["A"], pr["B"], k=4, as_df=False, cumulative=True, break_ties_with_noise=False)
     assert d["K"] == 4 and set(d) == {"P@K", "AP@K", "NDCG@K", "K"} and d["P@K"].shape == (m, 4)
     bias = np.linspace(-1, 1, n).astype(np.float32)
@@ -548,7 +563,10 @@ def test_python_api_modes(hip, oracle):
     want = oracle.calc(pr["A"], pr["B"], pr["train"], pr["test"], 5, dtype=np.float64)
     assert d["P@K"].dtype == np.float64
     for key in want:
-        assert_close(d[key], want[key], TOL, "f64 strided " + key)
+        if key == "ROC_AUC":
+            assert_roc(d[key], want[key], np.float64, "f64 strided " + key)
+        else:
+            assert_close(d[key], want[key], TOL, "f64 strided " + key)
     # mixed dtypes => float64 (only float32 when BOTH are float32)
     d = calc_reco_metrics(Xtr, Xte, pr["A"].astype(np.float32), pr["B"], k=5, as_df=False, break_ties_with_noise=False)
     assert d["P@K"].dtype == np.float64
@@ -557,7 +575,10 @@ def test_python_api_modes(hip, oracle):
     empty = (np.zeros(m + 1, np.int32), np.zeros(0, np.int32))
     want = oracle.calc(pr["A"], pr["B"], empty, pr["test"], 5, metrics=("p", "ap", "roc"), dtype=np.float64)
     for key in want:
-        assert_close(d[key], want[key], TOL, "no train " + key)
+        if key == "ROC_AUC":
+            assert_roc(d[key], want[key], np.float64, "no train " + key)
+        else:
+            assert_close(d[key], want[key], TOL, "no train " + key)
     # non-personalised: scores = item biases
     bias = np.random.default_rng(1).standard_normal(n)
     d = calc_reco_metrics(Xtr, Xte, None, None, k=5, item_biases=bias, as_df=False, break_ties_with_noise=False)
@@ -589,7 +610,10 @@ def test_full_size_properties(hip, oracle):
     sub_te = slice_csr(pr["test"][0], pr["test"][1], pr["test"][2], 0, 384)
     want = oracle.calc(pr["A"][:384], pr["B"], sub_tr, sub_te, 10, nthreads=NT)
     for name in want:
-        assert_close(single[name][:384], want[name], TOL, "sub-sample " + name)
+        if name == "ROC_AUC":
+            assert_roc(single[name][:384], want[name], np.float32, "sub-sample " + name)
+        else:
+            assert_close(single[name][:384], want[name], TOL, "sub-sample " + name)
     cum = hip_calc(hip, pr["A"], pr["B"], pr["train"], pr["test"], 10, cumulative=True)
     for name in ("P@K", "TP@K", "R@K", "AP@K", "TAP@K", "Hit@K", "RR@K"):
         assert_same_bits(cum[name][:, -1], single[name], name + ": cumulative column K == single-K")

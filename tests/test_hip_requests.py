@@ -12,10 +12,10 @@ import inspect
 import numpy as np
 import pytest
 
-from _parity import NT, TOL, hip_calc
+from _parity import NT, hip_calc
 from _requests import (DEFAULT, F32, F64, REQUESTS, TIE_REQUESTS, TOPK8, check_request, edge_problem, equal_problem,
                        long_rows_problem, req_id, runs_problem, tie_problem, user_is_nan)
-from _util import assert_close, assert_same_bits
+from _util import assert_roc, assert_same_bits
 from test_hip_scores import scores_calc
 
 pytestmark = pytest.mark.gpu
@@ -208,7 +208,7 @@ def test_the_score_matrix_entry(hip, oracle, dtype, K, req):
         for name in want:
             assert_same_bits(got[name], factor[name], "%s cumulative=%s against the factor call" % (name, cum))
             if name == "ROC_AUC":
-                assert_close(got[name], want[name], TOL, name)
+                assert_roc(got[name], want[name], dtype, name)
             else:
                 assert_same_bits(got[name], want[name], "%s cumulative=%s against the oracle" % (name, cum))
         dead = user_is_nan(got)

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from _parity import NT, _check_against_oracle, hip_calc
-from _util import assert_close, assert_same_bits, same_bits
+from _util import assert_close, assert_roc, assert_same_bits, same_bits
 from oracle.ties import tie_pairs_per_user
 
 pytestmark = pytest.mark.gpu
@@ -302,8 +302,9 @@ def test_item_biases_sorted_by_popularity(hip, oracle, order, bias_dtype, noise)
     assert d["K"] == 10 and set(d) == set(want) | {"K"} and len(want) == 10
     for key in want:
         assert d[key].dtype == F64
-        assert_close(d[key], want[key], TOL, "item biases %s: %s" % (order, key))
-        if key != "ROC_AUC":
+        if key == "ROC_AUC":
+            assert_roc(d[key], want[key], F64, "item biases %s: %s" % (order, key))
+        else:
             assert_same_bits(d[key], want[key], "item biases %s: %s (bitwise)" % (order, key))
     ref = _reference()
     if ref is not None:                                       # (tie-free: strictly monotone float64 scores)

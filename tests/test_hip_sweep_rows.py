@@ -6,7 +6,7 @@ row nothing reaches is first executed by a user; every row is a compilation of i
 visits are the data of tests/_sweep_plan.py -- one per row, checked against the table by tests/test_sweep_coverage_cpu.py -- and
 the tests here are parametrised by translation unit.  Per metric visit: the switches, one cumulative call, the ledger (the
 visit's row, no other list row, no dump row), every output against the oracle by check_request's rule (bit for bit; ROC-AUC
-within TOL), and the lists -- hip.rank on the auc = 1 rows, recommend_topk on the auc = 0 rows, which must land on the same row.
+within an ulp: _util.roc_tol), and the lists -- hip.rank on the auc = 1 rows, recommend_topk on the auc = 0 rows, which must land on the same row.
 Per dump visit: debug_scores against oracle.scores, and the ledger shows the dump row alone.
 
 The problems are the smallest at which these kernels can still go wrong: 200 users (two user blocks in fp32, four in fp64, the
@@ -20,9 +20,9 @@ import numpy as np
 import pytest
 
 import _sweep_plan as plan
-from _parity import NT, TOL
+from _parity import NT
 from _requests import TOPK8
-from _util import assert_close, assert_same_bits
+from _util import assert_roc, assert_same_bits
 from test_hip_recommend import check_lists, expected_lists
 from test_sweep_table_cpu import ELEM
 
@@ -147,7 +147,7 @@ def metric_visit(hip, oracle, table, v, monkeypatch):
     assert set(got) == set(want) and len(got) == len(v.request), what
     for name in want:
         if name == "ROC_AUC":
-            assert_close(got[name], want[name], TOL, what + ": " + name)
+            assert_roc(got[name], want[name], dtype, what + ": " + name)
         else:
             assert_same_bits(got[name], want[name], what + ": " + name)
 

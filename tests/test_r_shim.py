@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from _util import assert_same_bits
+from _util import assert_roc, assert_same_bits
 
 NA_REAL_BITS = 0x7FF00000000007A2          # R_NaReal: high word 0x7FF00000, low word 1954 (R's arithmetic.c)
 ORDER = ("p", "tp", "r", "ap", "tap", "ndcg", "hit", "rr", "roc", "pr")
@@ -218,5 +218,4 @@ def test_random_roc_auc_with_float_carriers_like_test_auc_r():
     assert abs(np.nanmean(got) - 0.5) <= 0.03
     ref = Oracle().calc(A, B, pr["train"], (tep, tei, tev.astype(np.float32)), 5, metrics=("roc",), noise=True, seed=1, nthreads=1, dtype=np.float32)
     w = ref[NAMES["roc"]]
-    assert (np.isnan(w) == np.isnan(got)).all()
-    assert np.nanmax(np.abs(w.astype(np.float64) - got.astype(np.float64)), initial=0) <= 1e-5
+    assert_roc(got, w, np.float32, "ROC-AUC through the R entry")
