@@ -140,6 +140,96 @@ def _as_frame(out, k, cumulative, rename_k):
     return pd.concat(blocks, axis=1)
 
 
+def _requested_metrics(arguments):
+    """keyword -> bool out of a metric call's arguments (its `locals()`): the flag, or `all_metrics`"""
+    return {name: bool(arguments["all_metrics"] or arguments[name]) for name, _, _ in _METRICS}
+
+
+def _fail_if_no_ranking_metric(requested):
+    _fail_if(not (requested["precision"] or requested["average_precision"] or requested["ndcg"]
+                  or requested["hit"] or requested["rr"] or requested["roc_auc"]),
+             "Must pass at least one metric to calculate.")
+
+
+def _train_or_empty(X_train, X_test, dtype, consider_cold_start):
+    """(X_train, consider_cold_start): no train matrix is an empty one with cold start on"""
+    if X_train is not None:
+        return X_train, consider_cold_start
+    from scipy.sparse import csr_array
+    return csr_array(X_test.shape, dtype=dtype), True
+
+
+def _split_arrays(X_train, X_test, n_users, dtype):
+    """(train_p, train_i, test_p, test_i, test_v) for the binding: int32 CSR (the library validates and, if need be, sorts the rows),
+    a taller `X_train` trimmed to the test users, test values in `dtype`; nothing is copied that already has the right type and layout"""
+    X_train = _csr_int32(X_train)
+    if X_train.shape[0] > n_users:
+        X_train = _csr_int32(X_train[:n_users])
+    X_test = _csr_int32(X_test)
+    test_values = X_test.data if X_test.data.dtype == dtype else X_test.data.astype(dtype)
+    return tuple(np.ascontiguousarray(a) for a in (X_train.indptr, X_train.indices, X_test.indptr, X_test.indices, test_values))
+
+
+def _output_storage(requested, n_users, dtype, as_df, cumulative):
+    """(want, outs, block, keys) of a metric call.  For a plain DataFrame the storage is allocated up front: one column-major [users,
+    metrics] block whose columns ARE the output arrays of the call -- pandas wraps it without a copy (building the frame from ten
+    separate arrays consolidates them into such a block: 0.9 ms for BASELINE C2's 138k users, 8 % of the call)"""
+    want = {short: requested[name] for name, short, _ in _METRICS}
+    if not as_df or cumulative:
+        return want, None, None, None
+    keys = [key for (name, _, key) in _METRICS if requested[name]]
+    block = np.empty((n_users, len(keys)), dtype=dtype, order="F")
+    cols = iter(range(len(keys)))
+    return want, [block[:, next(cols)] if requested[name] else np.empty(0, dtype=dtype) for name, _, _ in _METRICS], block, keys
+
+
+def _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k):
+    """the block's frame, the dict with "K", or the frame of the dict"""
+    if block is not None:
+        import pandas as pd
+        if rename_k:
+            keys = [key[:-1] + str(k) if key.endswith("@K") else key for key in keys]
+        return pd.DataFrame(block, columns=keys, copy=False)
+    out = {key: arr for (_, _, key), arr in zip(_METRICS, arrays) if arr.shape[0]}
+    if not as_df:
+        out["K"] = k
+        return out
+    return _as_frame(out, k, bool(cumulative), bool(rename_k))
+
+
+def _list_length(k, n_items):
+    k = int(k)
+    _fail_if(k < 1, "'k' must be positive.")
+    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+    return k
+
+
+def _user_selection(users, n_users, source):
+    """`users` as an int64 array (or None); `source`: the argument whose rows it selects, for the message"""
+    if users is None:
+        return None
+    users = np.asarray(users)
+    _fail_if(users.ndim != 1 or (users.size and users.dtype.kind not in "iu"), "'users' must be a 1-d integer array.")
+    users = users.astype(np.int64, copy=False)
+    _fail_if(users.size and (users.min() < 0 or users.max() >= n_users), "'users' has entries outside the rows of '%s'." % source)
+    return users
+
+
+def _exclusion_csr(X_train, users):
+    """(excl_p, excl_i): the int32 CSR of the items to leave out, its rows gathered by `users`; (None, None) leaves nothing out"""
+    if X_train is None:
+        return None, None
+    if users is not None:
+        X_train = _csr_int32(X_train)[users]
+    X_train = _csr_int32(X_train)
+    return np.ascontiguousarray(X_train.indptr), np.ascontiguousarray(X_train.indices)
+
+
+def _no_lists(k, dtype, return_scores):
+    """the answer for no users at all"""
+    return (np.empty((0, k), np.int32), np.empty((0, k), dtype) if return_scores else None, np.empty(0, np.int32))
+
+
 def calc_reco_metrics(
     X_train, X_test,
     A, B,
@@ -181,12 +271,8 @@ def calc_reco_metrics(
     alone are computed (the reference leaves them uninitialised) and ``pr_auc`` without ``roc_auc`` is computed from
     the full ranking.
     """
-    from scipy.sparse import csr_array, issparse
-
-    requested = dict(precision=precision, trunc_precision=trunc_precision, recall=recall,
-                     average_precision=average_precision, trunc_average_precision=trunc_average_precision,
-                     ndcg=ndcg, hit=hit, rr=rr, roc_auc=roc_auc, pr_auc=pr_auc)
-    requested = {name: bool(all_metrics or flag) for name, flag in requested.items()}
+    requested = _requested_metrics(locals())
+    from scipy.sparse import issparse
 
     if hasattr(item_biases, "to_numpy"):                 # pandas.Series
         item_biases = item_biases.to_numpy()
@@ -210,18 +296,14 @@ def calc_reco_metrics(
     dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
 
     # ---- train matrix ----
-    if X_train is None:
-        X_train = csr_array(X_test.shape, dtype=dtype)
-        consider_cold_start = True
+    X_train, consider_cold_start = _train_or_empty(X_train, X_test, dtype, consider_cold_start)
     assert issparse(X_train)
     assert X_train.shape[1] == n_items
     _fail_if(X_train.shape[0] < n_users, "'X_train' and 'X_test' should have the same number of rows.")
     if X_train.shape[0] > n_users:
         warn("'X_train' mas more rows than 'X_test'.")
 
-    _fail_if(not (requested["precision"] or requested["average_precision"] or requested["ndcg"]
-                  or requested["hit"] or requested["rr"] or requested["roc_auc"]),
-             "Must pass at least one metric to calculate.")
+    _fail_if_no_ranking_metric(requested)
 
     # ---- scalars ----
     if isinstance(seed, np.random.RandomState):
@@ -241,43 +323,15 @@ def calc_reco_metrics(
     if item_biases is not None:
         A, B = _fold_item_biases(A, B, item_biases, n_items, dtype)
 
-    # ---- normalise storage: int32 CSR (the library validates and, if need be, sorts the rows), test values and factors in
-    # `dtype`, row-major factors; nothing is copied that already has the right type and layout ----
-    X_train = _csr_int32(X_train)
-    if X_train.shape[0] > n_users:
-        X_train = _csr_int32(X_train[:n_users])
-    X_test = _csr_int32(X_test)
-    test_values = X_test.data if X_test.data.dtype == dtype else X_test.data.astype(dtype)
+    # ---- normalise storage: factors in `dtype` and row-major; nothing is copied that already has the right type and layout ----
+    split = _split_arrays(X_train, X_test, n_users, dtype)
     A, lda = _row_major_with_ld(A.astype(dtype, copy=False))
     B, ldb = _row_major_with_ld(B.astype(dtype, copy=False))
-    c = np.ascontiguousarray
-
-    want = {short: requested[name] for name, short, _ in _METRICS}
-    outs = block = None
-    if as_df and not cumulative:
-        # the DataFrame's storage is allocated up front: one column-major [users, metrics] block whose columns ARE the output
-        # arrays of the call -- pandas wraps it without a copy (building the frame from ten separate arrays consolidates them into
-        # such a block: 0.9 ms for BASELINE C2's 138k users, 8 % of the call)
-        keys = [key for (name, _, key) in _METRICS if requested[name]]
-        block = np.empty((n_users, len(keys)), dtype=dtype, order="F")
-        cols = iter(range(len(keys)))
-        outs = [block[:, next(cols)] if requested[name] else np.empty(0, dtype=dtype) for name, _, _ in _METRICS]
-
+    want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
     arrays = _binding.calc_metrics(
-        A, lda, B, ldb, c(X_train.indptr), c(X_train.indices), c(X_test.indptr), c(X_test.indices), c(test_values),
-        k, want, bool(cumulative), bool(break_ties_with_noise),
+        A, lda, B, ldb, *split, k, want, bool(cumulative), bool(break_ties_with_noise),
         bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, seed, outs=outs)
-
-    if block is not None:
-        import pandas as pd
-        if rename_k:
-            keys = [key[:-1] + str(k) if key.endswith("@K") else key for key in keys]
-        return pd.DataFrame(block, columns=keys, copy=False)
-    out = {key: arr for (_, _, key), arr in zip(_METRICS, arrays) if arr.shape[0]}
-    if not as_df:
-        out["K"] = k
-        return out
-    return _as_frame(out, k, bool(cumulative), bool(rename_k))
+    return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
 
 
 def calc_reco_metrics_from_scores(
@@ -319,12 +373,8 @@ def calc_reco_metrics_from_scores(
     by item id, the rule ``calc_reco_metrics(..., break_ties_with_noise=False)`` uses, and for scores that ARE ``A @ B.T`` as the
     library forms it the two calls return the same bits.  There is no ``item_biases`` either: add them to ``scores``.
     """
-    from scipy.sparse import csr_array, issparse
-
-    requested = dict(precision=precision, trunc_precision=trunc_precision, recall=recall,
-                     average_precision=average_precision, trunc_average_precision=trunc_average_precision,
-                     ndcg=ndcg, hit=hit, rr=rr, roc_auc=roc_auc, pr_auc=pr_auc)
-    requested = {name: bool(all_metrics or flag) for name, flag in requested.items()}
+    requested = _requested_metrics(locals())
+    from scipy.sparse import issparse
 
     _fail_if(not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
     _fail_if(scores.ndim != 2, "'scores' must be a 2-dimensional array.")
@@ -338,18 +388,14 @@ def calc_reco_metrics_from_scores(
     _fail_if(scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
     dtype = np.float32 if scores.dtype == np.float32 else np.float64
 
-    if X_train is None:
-        X_train = csr_array(X_test.shape, dtype=dtype)
-        consider_cold_start = True
+    X_train, consider_cold_start = _train_or_empty(X_train, X_test, dtype, consider_cold_start)
     _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
     _fail_if(X_train.shape[1] != n_items, "'X_train' and 'X_test' should have the same number of columns.")
     _fail_if(X_train.shape[0] < n_users, "'X_train' and 'X_test' should have the same number of rows.")
     if X_train.shape[0] > n_users:
         warn("'X_train' mas more rows than 'X_test'.")
 
-    _fail_if(not (requested["precision"] or requested["average_precision"] or requested["ndcg"]
-                  or requested["hit"] or requested["rr"] or requested["roc_auc"]),
-             "Must pass at least one metric to calculate.")
+    _fail_if_no_ranking_metric(requested)
 
     k, nthreads = int(k), int(nthreads)
     min_pos_test, min_items_pool = int(min_pos_test), int(min_items_pool)
@@ -361,37 +407,12 @@ def calc_reco_metrics_from_scores(
     _fail_if(k > n_items, "'k' should be smaller than the number of items.")
 
     # ---- everything above raises before the library is touched ----
-    X_train = _csr_int32(X_train)
-    if X_train.shape[0] > n_users:
-        X_train = _csr_int32(X_train[:n_users])
-    X_test = _csr_int32(X_test)
-    test_values = X_test.data if X_test.data.dtype == dtype else X_test.data.astype(dtype)
+    split = _split_arrays(X_train, X_test, n_users, dtype)
     S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
-    c = np.ascontiguousarray
-
-    want = {short: requested[name] for name, short, _ in _METRICS}
-    outs = block = None
-    if as_df and not cumulative:
-        # (the DataFrame's storage up front, as in calc_reco_metrics: the columns ARE the output arrays of the call)
-        keys = [key for (name, _, key) in _METRICS if requested[name]]
-        block = np.empty((n_users, len(keys)), dtype=dtype, order="F")
-        cols = iter(range(len(keys)))
-        outs = [block[:, next(cols)] if requested[name] else np.empty(0, dtype=dtype) for name, _, _ in _METRICS]
-
+    want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
     arrays = _binding.calc_metrics_scores(
-        S, lds, c(X_train.indptr), c(X_train.indices), c(X_test.indptr), c(X_test.indices), c(test_values),
-        k, want, bool(cumulative), bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, outs=outs)
-
-    if block is not None:
-        import pandas as pd
-        if rename_k:
-            keys = [key[:-1] + str(k) if key.endswith("@K") else key for key in keys]
-        return pd.DataFrame(block, columns=keys, copy=False)
-    out = {key: arr for (_, _, key), arr in zip(_METRICS, arrays) if arr.shape[0]}
-    if not as_df:
-        out["K"] = k
-        return out
-    return _as_frame(out, k, bool(cumulative), bool(rename_k))
+        S, lds, *split, k, want, bool(cumulative), bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, outs=outs)
+    return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
 
 
 def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, return_scores=True):
@@ -425,19 +446,13 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
     n_users, n_items = A.shape[0], B.shape[0]
     _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
     _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
-    k = int(k)
-    _fail_if(k < 1, "'k' must be positive.")
-    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+    k = _list_length(k, n_items)
     if X_train is not None:
         from scipy.sparse import issparse
         _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
         _fail_if(X_train.shape[1] != n_items, "Number of items in 'B' and 'X_train' does not match.")
         _fail_if(X_train.shape[0] != n_users, "Number of users in 'A' and 'X_train' does not match.")
-    if users is not None:
-        users = np.asarray(users)
-        _fail_if(users.ndim != 1 or (users.size and users.dtype.kind not in "iu"), "'users' must be a 1-d integer array.")
-        users = users.astype(np.int64, copy=False)
-        _fail_if(users.size and (users.min() < 0 or users.max() >= n_users), "'users' has entries outside the rows of 'A'.")
+    users = _user_selection(users, n_users, "A")
     dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
     if item_biases is not None:
         A, B = _fold_item_biases(A, B, item_biases, n_items, dtype)
@@ -445,15 +460,9 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
     # ---- everything above raises before the library is touched ----
     if users is not None:
         A = A[users]
-        if X_train is not None:
-            X_train = _csr_int32(X_train)[users]
-    excl_p = excl_i = None
-    if X_train is not None:
-        X_train = _csr_int32(X_train)
-        excl_p, excl_i = np.ascontiguousarray(X_train.indptr), np.ascontiguousarray(X_train.indices)
-    m = A.shape[0]
-    if m == 0:
-        return (np.empty((0, k), np.int32), np.empty((0, k), dtype) if return_scores else None, np.empty(0, np.int32))
+    excl_p, excl_i = _exclusion_csr(X_train, users)
+    if A.shape[0] == 0:
+        return _no_lists(k, dtype, return_scores)
     A, lda = _row_major_with_ld(A.astype(dtype, copy=False))
     B, ldb = _row_major_with_ld(B.astype(dtype, copy=False))
     return _binding.recommend(A, lda, B, ldb, excl_p, excl_i, k, bool(return_scores))
@@ -480,31 +489,19 @@ def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_sc
     _fail_if(n_items == 0, "Input matrices cannot be empty.")
     _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
     _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
-    k = int(k)
-    _fail_if(k < 1, "'k' must be positive.")
-    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+    k = _list_length(k, n_items)
     if X_train is not None:
         from scipy.sparse import issparse
         _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
         _fail_if(tuple(X_train.shape) != (n_users, n_items), "'scores' and 'X_train' must have the same shape.")
-    if users is not None:
-        users = np.asarray(users)
-        _fail_if(users.ndim != 1 or (users.size and users.dtype.kind not in "iu"), "'users' must be a 1-d integer array.")
-        users = users.astype(np.int64, copy=False)
-        _fail_if(users.size and (users.min() < 0 or users.max() >= n_users), "'users' has entries outside the rows of 'scores'.")
+    users = _user_selection(users, n_users, "scores")
     dtype = np.float32 if scores.dtype == np.float32 else np.float64
 
     # ---- everything above raises before the library is touched ----
     if users is not None:
         scores = scores[users]                               # (the one gather: a new row-major array)
-        if X_train is not None:
-            X_train = _csr_int32(X_train)[users]
-    excl_p = excl_i = None
-    if X_train is not None:
-        X_train = _csr_int32(X_train)
-        excl_p, excl_i = np.ascontiguousarray(X_train.indptr), np.ascontiguousarray(X_train.indices)
-    m = scores.shape[0]
-    if m == 0:
-        return (np.empty((0, k), np.int32), np.empty((0, k), dtype) if return_scores else None, np.empty(0, np.int32))
+    excl_p, excl_i = _exclusion_csr(X_train, users)
+    if scores.shape[0] == 0:
+        return _no_lists(k, dtype, return_scores)
     S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
     return _binding.recommend_scores(S, lds, excl_p, excl_i, k, bool(return_scores))

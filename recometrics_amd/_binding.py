@@ -15,19 +15,58 @@ _LIB_PATH = os.environ.get("RECOMETRICS_HIP_LIB") or os.path.join(
 _lib = None
 
 METRIC_ORDER = ("p", "tp", "r", "ap", "tap", "ndcg", "hit", "rr", "roc", "pr")
-EXPORTS = (
-    "rm_calc_metrics_f32", "rm_calc_metrics_f64", "rm_calc_metrics_dev_f32", "rm_calc_metrics_dev_f64",
-    "rm_calc_metrics_scores_f32", "rm_calc_metrics_scores_f64", "rm_calc_metrics_scores_dev_f32", "rm_calc_metrics_scores_dev_f64",
-    "rm_rank_f32", "rm_rank_f64", "rm_recommend_f32", "rm_recommend_f64", "rm_recommend_dev_f32", "rm_recommend_dev_f64",
-    "rm_recommend_scores_f32", "rm_recommend_scores_f64", "rm_recommend_scores_dev_f32", "rm_recommend_scores_dev_f64",
-    "rm_debug_scores_f32", "rm_debug_scores_f64", "rm_has_openmp",
-    "rm_last_error", "rm_device_count", "rm_set_device", "rm_set_devices", "rm_get_devices", "rm_request_interrupt",
-    "rm_get_timings", "rm_release_workspace", "rm_debug_reload_switches",
-    "rm_debug_sweep_variants", "rm_debug_find_sweep", "rm_debug_supported_ng",
-    "rm_debug_sweep_launched", "rm_debug_sweep_launched_reset",
-    "rm_split_f32", "rm_split_f64", "rm_split_size", "rm_split_copy", "rm_split_free", "rm_split_last_error",
-    "rm_csr_rows_sorted", "rm_csr_sort_rows",
-)
+OUTPUTS = tuple(name + ("_auc" if name in ("roc", "pr") else "_at_k") for name in METRIC_ORDER)      # the header's names of the ten outputs
+
+_vp, _i32, _i64, _u64, _sz, _ci = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_int
+_FACTORS = (("A", _vp), ("lda", _sz), ("B", _vp), ("ldb", _sz), ("m", _i32), ("n", _i32), ("k", _i32))
+_SCORES = (("S", _vp), ("lds", _sz), ("m", _i32), ("n", _i32))
+
+
+def _csr(which, host, values=False):
+    """the CSR arrays `which` (train, test, excl) of an entry; the device form takes the length of the index array too"""
+    return ((("X%s_csr_p" % which, _vp), ("X%s_csr_i" % which, _vp)) + ((("X%s_csr" % which, _vp),) if values else ())
+            + (() if host else (("nnz_" + which, _i64),)))
+
+
+def _metrics(source, host):
+    return (source + _csr("train", host) + _csr("test", host, values=True) + (("k_metrics", _i32), ("cumulative", _ci))
+            + ((("break_ties_with_noise", _ci),) if source is _FACTORS else ()) + tuple((name, _vp) for name in OUTPUTS)
+            + (("consider_cold_start", _ci), ("min_items_pool", _i32), ("min_pos_test", _i32)) + ((("nthreads", _i32),) if host else ())
+            + ((("seed", _u64),) if source is _FACTORS else ()) + (() if host else (("stream", _vp),)))
+
+
+def _lists(source, host):
+    return (source + _csr("excl", host) + (("k_top", _i32), ("idx", _vp), ("score", _vp), ("status", _vp))
+            + ((("nthreads", _i32),) if host else (("stream", _vp),)))
+
+
+_RANK = (_FACTORS + _csr("train", True) + _csr("test", True)
+         + (("k_metrics", _i32), ("break_ties_with_noise", _ci), ("consider_cold_start", _ci), ("min_items_pool", _i32), ("min_pos_test", _i32),
+            ("seed", _u64), ("topk_idx", _vp), ("topk_score", _vp), ("pos_rank", _vp), ("status", _vp)))
+# one row for the _f32 and the _f64 symbol of a name: the parameters of include/recometrics_hip.h by name, every one returns an int
+_TYPED = {"rm_rank": _RANK, "rm_debug_scores": _FACTORS + (("out", _vp),),
+          "rm_split": (("X_csr_p", _vp), ("X_csr_i", _vp), ("X_csr", _vp), ("m", _i32), ("n", _i32), ("mode", _ci), ("n_users_test", _i32),
+                       ("test_fraction", C.c_double), ("consider_cold_start", _ci), ("min_items_pool", _i32), ("min_pos_test", _i32),
+                       ("seed", _u64), ("result", C.POINTER(_vp)))}
+_TYPED.update({"rm_" + request + source + form: pieces(params, host) for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists))
+               for source, params in (("", _FACTORS), ("_scores", _SCORES)) for form, host in (("", True), ("_dev", False))})
+# symbol -> (its (parameter name, ctype) pairs in the header's order, restype)
+SIGNATURES = {name + suffix: (params, _ci) for name, params in _TYPED.items() for suffix in ("_f32", "_f64")}
+SIGNATURES.update({
+    "rm_has_openmp": ((), _ci), "rm_last_error": ((), C.c_char_p), "rm_device_count": ((), _ci), "rm_set_device": ((("device", _ci),), _ci),
+    "rm_set_devices": ((("devices", C.POINTER(_i32)), ("n", _i32)), _ci), "rm_get_devices": ((("devices", C.POINTER(_i32)), ("cap", _i32)), _ci),
+    "rm_request_interrupt": ((), None), "rm_get_timings": ((("out", C.POINTER(C.c_double)), ("n", _ci)), _ci), "rm_release_workspace": ((), _ci),
+    "rm_debug_reload_switches": ((), None), "rm_debug_sweep_variants": ((("elem_bytes", _ci), ("out", C.POINTER(_ci)), ("cap", _ci)), _ci),
+    "rm_debug_find_sweep": (tuple((name, _ci) for name in ("elem_bytes", "ng", "ngt", "auc", "dump", "lmode", "nsub", "spec"))
+                            + (("out6", C.POINTER(_ci)),), _ci),
+    "rm_debug_supported_ng": ((("elem_bytes", _ci), ("k", _ci)), _ci),
+    "rm_debug_sweep_launched": ((("elem_bytes", _ci), ("counts", C.POINTER(_ci)), ("cap", _ci)), _ci), "rm_debug_sweep_launched_reset": ((), None),
+    "rm_split_size": ((("result", _vp), ("which", _ci)), _i64), "rm_split_copy": ((("result", _vp), ("which", _ci), ("dst", _vp)), _ci),
+    "rm_split_free": ((("result", _vp),), None), "rm_split_last_error": ((), C.c_char_p),
+    "rm_csr_rows_sorted": ((("indptr", _vp), ("indices", _vp), ("m", _i32), ("nthreads", _i32)), _ci),
+    "rm_csr_sort_rows": ((("indptr", _vp), ("indices", _vp), ("values", _vp), ("value_bytes", _i32), ("m", _i32), ("nthreads", _i32)), _ci),
+})
+EXPORTS = tuple(SIGNATURES)
 
 
 class HipLibraryMissing(ImportError):
@@ -38,97 +77,39 @@ def lib_path():
     return _LIB_PATH
 
 
+def _declare(lib, names):
+    """gives the symbols `names` of a loaded library the types SIGNATURES states"""
+    for name in names:
+        params, restype = SIGNATURES[name]
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = [ctype for _, ctype in params], restype
+    return lib
+
+
 def load():
     """Loads the HIP library (once).  Raises HipLibraryMissing if it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_LIB_PATH):
-        raise HipLibraryMissing(
-            "recometrics_amd: %s is missing -- build it with `python -m recometrics_amd.build` "
-            "(there is no CPU fallback)" % _LIB_PATH)
-    lib = C.CDLL(_LIB_PATH)
-    vp, i32, i64, u64, sz, ci = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_int
-    host = [vp, sz, vp, sz, i32, i32, i32, vp, vp, vp, vp, vp, i32, ci, ci] + [vp] * 10 + [ci, i32, i32, i32, u64]
-    dev = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, vp, vp, vp, i64, i32, ci, ci] + [vp] * 10 + [ci, i32, i32, u64, vp]
-    rank_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, vp, vp, i32, ci, ci, i32, i32, u64, vp, vp, vp, vp]
-    reco_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32]
-    scores_sig = [vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, ci] + [vp] * 10 + [ci, i32, i32, i32]
-    scores_dev_sig = [vp, sz, i32, i32, vp, vp, i64, vp, vp, vp, i64, i32, ci] + [vp] * 10 + [ci, i32, i32, vp]
-    reco_dev_sig = [vp, sz, vp, sz, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp]
-    reco_scores_sig = [vp, sz, i32, i32, vp, vp, i32, vp, vp, vp, i32]
-    reco_scores_dev_sig = [vp, sz, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp]
-    for suf in ("f32", "f64"):
-        getattr(lib, "rm_recommend_scores_" + suf).argtypes = reco_scores_sig
-        getattr(lib, "rm_recommend_scores_dev_" + suf).argtypes = reco_scores_dev_sig
-        getattr(lib, "rm_recommend_scores_" + suf).restype = getattr(lib, "rm_recommend_scores_dev_" + suf).restype = ci
-        getattr(lib, "rm_recommend_" + suf).argtypes = reco_sig
-        getattr(lib, "rm_recommend_dev_" + suf).argtypes = reco_dev_sig
-        getattr(lib, "rm_recommend_" + suf).restype = getattr(lib, "rm_recommend_dev_" + suf).restype = ci
-        getattr(lib, "rm_calc_metrics_scores_" + suf).argtypes = scores_sig
-        getattr(lib, "rm_calc_metrics_scores_dev_" + suf).argtypes = scores_dev_sig
-        getattr(lib, "rm_calc_metrics_scores_" + suf).restype = getattr(lib, "rm_calc_metrics_scores_dev_" + suf).restype = ci
-        getattr(lib, "rm_calc_metrics_" + suf).argtypes = host
-        getattr(lib, "rm_calc_metrics_dev_" + suf).argtypes = dev
-        getattr(lib, "rm_rank_" + suf).argtypes = rank_sig
-        getattr(lib, "rm_debug_scores_" + suf).argtypes = [vp, sz, vp, sz, i32, i32, i32, vp]
-        for fn in ("rm_calc_metrics_", "rm_calc_metrics_dev_", "rm_rank_", "rm_debug_scores_"):
-            getattr(lib, fn + suf).restype = ci
-    split_sig = [vp, vp, vp, i32, i32, ci, i32, C.c_double, ci, i32, i32, u64, C.POINTER(vp)]
-    lib.rm_split_f32.argtypes = split_sig
-    lib.rm_split_f64.argtypes = split_sig
-    lib.rm_split_f32.restype = lib.rm_split_f64.restype = ci
-    lib.rm_split_size.argtypes = [vp, ci]
-    lib.rm_split_size.restype = i64
-    lib.rm_split_copy.argtypes = [vp, ci, vp]
-    lib.rm_split_copy.restype = ci
-    lib.rm_split_free.argtypes = [vp]
-    lib.rm_split_free.restype = None
-    lib.rm_split_last_error.restype = C.c_char_p
-    lib.rm_csr_rows_sorted.argtypes = [vp, vp, i32, i32]
-    lib.rm_csr_rows_sorted.restype = ci
-    lib.rm_csr_sort_rows.argtypes = [vp, vp, vp, i32, i32, i32]
-    lib.rm_csr_sort_rows.restype = ci
-    lib.rm_last_error.restype = C.c_char_p
-    lib.rm_get_timings.argtypes = [C.POINTER(C.c_double), ci]
-    lib.rm_set_device.argtypes = [ci]
-    lib.rm_set_devices.argtypes = [C.POINTER(i32), i32]
-    lib.rm_get_devices.argtypes = [C.POINTER(i32), i32]
-    lib.rm_request_interrupt.restype = None
-    lib.rm_debug_reload_switches.restype = None
-    lib.rm_debug_sweep_variants.argtypes = [ci, C.POINTER(ci), ci]
-    lib.rm_debug_find_sweep.argtypes = [ci] * 8 + [C.POINTER(ci)]
-    lib.rm_debug_supported_ng.argtypes = [ci, ci]
-    lib.rm_debug_sweep_launched.argtypes = [ci, C.POINTER(ci), ci]
-    lib.rm_debug_sweep_launched_reset.restype = None
-    _lib = lib
-    return lib
+    if _lib is None:
+        if not os.path.exists(_LIB_PATH):
+            raise HipLibraryMissing(
+                "recometrics_amd: %s is missing -- build it with `python -m recometrics_amd.build` "
+                "(there is no CPU fallback)" % _LIB_PATH)
+        _lib = _declare(C.CDLL(_LIB_PATH), SIGNATURES)
+    return _lib
 
 
 _split_lib = None
 
 
 def _load_split():
-    """The library that provides rm_split_* (host-only code): librecometrics_hip.so, or -- RECOMETRICS_SPLIT_LIB -- another
-    build of csrc/rm_split.cpp alone (the sanitizer build of oracle/Makefile, which has no device code to link)."""
+    """The library that provides the host-only rm_split_* and rm_csr_*: librecometrics_hip.so, or -- RECOMETRICS_SPLIT_LIB -- another
+    build of csrc/rm_split.cpp and csrc/rm_csr.cpp alone (the sanitizer build of oracle/Makefile, which has no device code to link)."""
     global _split_lib
     alt = os.environ.get("RECOMETRICS_SPLIT_LIB")
     if not alt:
         return load()
     if _split_lib is None:
-        lib = C.CDLL(alt)
-        vp, i32, i64, u64, ci = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_int
-        sig = [vp, vp, vp, i32, i32, ci, i32, C.c_double, ci, i32, i32, u64, C.POINTER(vp)]
-        lib.rm_split_f32.argtypes = lib.rm_split_f64.argtypes = sig
-        lib.rm_split_f32.restype = lib.rm_split_f64.restype = ci
-        lib.rm_split_size.argtypes = [vp, ci]
-        lib.rm_split_size.restype = i64
-        lib.rm_split_copy.argtypes = [vp, ci, vp]
-        lib.rm_split_copy.restype = ci
-        lib.rm_split_free.argtypes = [vp]
-        lib.rm_split_free.restype = None
-        lib.rm_split_last_error.restype = C.c_char_p
-        _split_lib = lib
+        _split_lib = _declare(C.CDLL(alt), [name for name in SIGNATURES if name.startswith(("rm_split_", "rm_csr_"))])
     return _split_lib
 
 
@@ -222,22 +203,9 @@ def timings():
     return {k: buf[i] for i, k in enumerate(keys[:n])}
 
 
-def _csr_lib():
-    """librecometrics_hip.so, or -- RECOMETRICS_SPLIT_LIB -- the sanitizer build of the host-only units (oracle/Makefile)"""
-    lib = _load_split()
-    if not getattr(lib, "_csr_ready", False):
-        vp, i32, ci = C.c_void_p, C.c_int32, C.c_int
-        lib.rm_csr_rows_sorted.argtypes = [vp, vp, i32, i32]
-        lib.rm_csr_rows_sorted.restype = ci
-        lib.rm_csr_sort_rows.argtypes = [vp, vp, vp, i32, i32, i32]
-        lib.rm_csr_sort_rows.restype = ci
-        lib._csr_ready = True
-    return lib
-
-
 def csr_rows_sorted(indptr, indices, nthreads=0):
     """True when the column indices of every row of an int32 CSR ascend (rm_csr_rows_sorted: multi-threaded pass)."""
-    lib = _csr_lib()
+    lib = _load_split()
     assert indptr.dtype == np.int32 and indices.dtype == np.int32
     rc = lib.rm_csr_rows_sorted(_p(indptr), _p(indices), indptr.shape[0] - 1, int(nthreads))
     if rc < 0:
@@ -247,7 +215,7 @@ def csr_rows_sorted(indptr, indices, nthreads=0):
 
 def csr_sort_rows(indptr, indices, data, nthreads=0):
     """Sorts every row's (index, value) pairs by index, in place (rm_csr_sort_rows); `data` may be None."""
-    lib = _csr_lib()
+    lib = _load_split()
     assert indptr.dtype == np.int32 and indices.dtype == np.int32 and indices.flags.writeable
     vb = 0 if data is None else data.dtype.itemsize
     if vb not in (0, 4, 8):
@@ -257,8 +225,30 @@ def csr_sort_rows(indptr, indices, data, nthreads=0):
         raise (MemoryError if rc == 3 else ValueError)("rm_csr_sort_rows failed (status %d)" % rc)
 
 
-def _suffix(dtype):
-    return "f32" if dtype == np.float32 else "f64"
+def _invoke(entry, dtype, **values):
+    """Calls `entry`'s symbol for `dtype` with `values` given by the header's parameter names, in the order SIGNATURES states; a
+    status other than 0 raises (`_raise`).  A missing name is a KeyError and an unknown one a TypeError, both before the call."""
+    name = entry + ("_f32" if dtype == np.float32 else "_f64")
+    params = SIGNATURES[name][0]
+    args = [values[param] for param, _ in params]
+    if len(values) != len(params):
+        raise TypeError("%s has no parameter %s" % (name, ", ".join(sorted(set(values) - {param for param, _ in params}))))
+    lib = load()
+    rc = getattr(lib, name)(*args)
+    if rc:
+        _raise(lib, rc)
+
+
+def _metrics_values(ptr, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test):
+    """what the four metric entries share, by name; `ptr`: `_p` for host arrays, `_dp` for device addresses"""
+    return dict(zip(OUTPUTS, map(ptr, outs)), Xtrain_csr_p=ptr(train_p), Xtrain_csr_i=ptr(train_i), Xtest_csr_p=ptr(test_p), Xtest_csr_i=ptr(test_i),
+                Xtest_csr=ptr(test_v), k_metrics=k_metrics, cumulative=int(bool(cumulative)), consider_cold_start=int(bool(consider_cold_start)),
+                min_items_pool=min_items_pool, min_pos_test=min_pos_test)
+
+
+def _host_excl_p(excl_p):
+    """None: nothing is left out; an array goes over as it is, also an empty one (`_p` would make that NULL)"""
+    return None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p)
 
 
 def calc_metrics(A, lda, B, ldb, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
@@ -266,17 +256,12 @@ def calc_metrics(A, lda, B, ldb, train_p, train_i, test_p, test_i, test_v, k_met
     """Host-array entry.  `want`: dict metric-name -> bool in METRIC_ORDER.  Returns the 10-tuple of arrays the
     reference's cpp_funs.calc_reco_metrics returns (wrapper.pyx:306-323): size-0 arrays for metrics not requested,
     (m, k) arrays for cumulative top-K metrics."""
-    lib = load()
     dtype = A.dtype.type
     m, k = A.shape
-    n = B.shape[0]
     outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
-    fn = getattr(lib, "rm_calc_metrics_" + _suffix(dtype))
-    rc = fn(_p(A), lda, _p(B), ldb, m, n, k, _p(train_p), _p(train_i), _p(test_p), _p(test_i), _p(test_v),
-            k_metrics, int(bool(cumulative)), int(bool(break_ties_with_noise)), *[_p(o) for o in outs],
-            int(bool(consider_cold_start)), min_items_pool, min_pos_test, nthreads, seed)
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_calc_metrics", dtype, A=_p(A), lda=lda, B=_p(B), ldb=ldb, m=m, n=B.shape[0], k=k,
+            break_ties_with_noise=int(bool(break_ties_with_noise)), nthreads=nthreads, seed=seed,
+            **_metrics_values(_p, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
     return outs
 
 
@@ -285,29 +270,20 @@ def calc_metrics_device(dtype, A, lda, B, ldb, m, n, k, train_p, train_i, nnz_tr
                         min_items_pool=2, min_pos_test=1, seed=1, stream=0):
     """Device-pointer entry: every array argument is an integer device address (0 == NULL); `outs` is a sequence
     of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
-    lib = load()
-    fn = getattr(lib, "rm_calc_metrics_dev_" + _suffix(dtype))
-    rc = fn(_dp(A), lda, _dp(B), ldb, m, n, k, _dp(train_p), _dp(train_i), nnz_train, _dp(test_p), _dp(test_i), _dp(test_v), nnz_test,
-            k_metrics, int(bool(cumulative)), int(bool(break_ties_with_noise)), *[_dp(o) for o in outs],
-            int(bool(consider_cold_start)), min_items_pool, min_pos_test, seed, _dp(stream))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_calc_metrics_dev", dtype, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, nnz_train=nnz_train, nnz_test=nnz_test,
+            break_ties_with_noise=int(bool(break_ties_with_noise)), seed=seed, stream=_dp(stream),
+            **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
 
 
 def calc_metrics_scores(S, lds, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
                         consider_cold_start, min_items_pool, min_pos_test, nthreads, outs=None):
     """Host-array entry of the metrics from a score matrix (rm_calc_metrics_scores_*): `S` [m, n] row-major with leading
     dimension `lds` (elements), the rest as `calc_metrics` without tie noise and seed.  Returns the same 10-tuple."""
-    lib = load()
     dtype = S.dtype.type
     m, n = S.shape
     outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
-    fn = getattr(lib, "rm_calc_metrics_scores_" + _suffix(dtype))
-    rc = fn(_p(S), lds, m, n, _p(train_p), _p(train_i), _p(test_p), _p(test_i), _p(test_v),
-            k_metrics, int(bool(cumulative)), *[_p(o) for o in outs],
-            int(bool(consider_cold_start)), min_items_pool, min_pos_test, nthreads)
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_calc_metrics_scores", dtype, S=_p(S), lds=lds, m=m, n=n, nthreads=nthreads,
+            **_metrics_values(_p, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
     return outs
 
 
@@ -316,31 +292,22 @@ def calc_metrics_scores_device(dtype, S, lds, m, n, train_p, train_i, nnz_train,
                                min_items_pool=2, min_pos_test=1, stream=0):
     """Device-pointer entry (rm_calc_metrics_scores_dev_*): every array argument is an integer device address (0 == NULL);
     `outs` is a sequence of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
-    lib = load()
-    fn = getattr(lib, "rm_calc_metrics_scores_dev_" + _suffix(dtype))
-    rc = fn(_dp(S), lds, m, n, _dp(train_p), _dp(train_i), nnz_train, _dp(test_p), _dp(test_i), _dp(test_v), nnz_test,
-            k_metrics, int(bool(cumulative)), *[_dp(o) for o in outs],
-            int(bool(consider_cold_start)), min_items_pool, min_pos_test, _dp(stream))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_calc_metrics_scores_dev", dtype, S=_dp(S), lds=lds, m=m, n=n, nnz_train=nnz_train, nnz_test=nnz_test, stream=_dp(stream),
+            **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
 
 
 def rank(A, B, train_p, train_i, test_p, test_i, k_metrics, break_ties_with_noise=False, consider_cold_start=True,
          min_items_pool=2, min_pos_test=1, seed=1):
-    lib = load()
     dtype = A.dtype.type
     m, k = A.shape
-    n = B.shape[0]
     idx, sc, st = _list_outs(m, k_metrics, dtype)
     pr = np.zeros(max(int(test_i.shape[0]), 1), dtype=np.int64)
-    fn = getattr(lib, "rm_rank_" + _suffix(dtype))
     A = np.ascontiguousarray(A)                  # the raw pointer is passed with lda = k: rows must be dense
     B = np.ascontiguousarray(B)
-    rc = fn(_p(A), A.shape[1], _p(B), B.shape[1], m, n, k, _p(train_p), _p(train_i), _p(test_p), _p(test_i),
-            k_metrics, int(bool(break_ties_with_noise)), int(bool(consider_cold_start)), min_items_pool, min_pos_test, seed,
-            _p(idx), _p(sc), _p(pr), _p(st))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_rank", dtype, A=_p(A), lda=A.shape[1], B=_p(B), ldb=B.shape[1], m=m, n=B.shape[0], k=k,
+            Xtrain_csr_p=_p(train_p), Xtrain_csr_i=_p(train_i), Xtest_csr_p=_p(test_p), Xtest_csr_i=_p(test_i), k_metrics=k_metrics,
+            break_ties_with_noise=int(bool(break_ties_with_noise)), consider_cold_start=int(bool(consider_cold_start)),
+            min_items_pool=min_items_pool, min_pos_test=min_pos_test, seed=seed, topk_idx=_p(idx), topk_score=_p(sc), pos_rank=_p(pr), status=_p(st))
     return {"topk_idx": idx, "topk_score": sc, "pos_rank": pr[:test_i.shape[0]], "status": st}
 
 
@@ -348,64 +315,45 @@ def recommend(A, lda, B, ldb, excl_p, excl_i, k_top, return_scores=True, nthread
     """Host-array entry of the recommendation lists (rm_recommend_*): A [m, k] / B [n, k] row-major with leading dimensions
     lda / ldb, `excl_p` / `excl_i` the int32 CSR of the items to leave out per user (`excl_p` None: nothing is left out).
     Returns (ids [m, k_top] int32, scores [m, k_top] or None, status [m] int32); -1 / NaN where a row holds no entry."""
-    lib = load()
     dtype = A.dtype.type
     m, k = A.shape
-    n = B.shape[0]
     idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
-    fn = getattr(lib, "rm_recommend_" + _suffix(dtype))
-    rc = fn(_p(A), lda, _p(B), ldb, m, n, k, None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p), _p(excl_i), k_top,
-            _p(idx), _p(sc), _p(st), int(nthreads))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_recommend", dtype, A=_p(A), lda=lda, B=_p(B), ldb=ldb, m=m, n=B.shape[0], k=k, Xexcl_csr_p=_host_excl_p(excl_p), Xexcl_csr_i=_p(excl_i),
+            k_top=k_top, idx=_p(idx), score=_p(sc), status=_p(st), nthreads=int(nthreads))
     return idx, sc, st
 
 
 def recommend_device(dtype, A, lda, B, ldb, m, n, k, excl_p, excl_i, nnz_excl, k_top, idx, score, status, stream=0):
     """Device-pointer entry (rm_recommend_dev_*): every array argument is an integer device address (0 == NULL: `excl_p` = nothing
     is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
-    lib = load()
-    fn = getattr(lib, "rm_recommend_dev_" + _suffix(dtype))
-    rc = fn(_dp(A), lda, _dp(B), ldb, m, n, k, _dp(excl_p), _dp(excl_i), nnz_excl, k_top, _dp(idx), _dp(score), _dp(status), _dp(stream))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_recommend_dev", dtype, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
+            nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
 
 
 def recommend_scores(S, lds, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
     """Host-array entry of the recommendation lists from a score matrix (rm_recommend_scores_*): `S` [m, n] row-major with leading
     dimension `lds` (elements), the rest and the return value as `recommend`."""
-    lib = load()
     dtype = S.dtype.type
     m, n = S.shape
     idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
-    fn = getattr(lib, "rm_recommend_scores_" + _suffix(dtype))
-    rc = fn(_p(S), lds, m, n, None if excl_p is None else excl_p.ctypes.data_as(C.c_void_p), _p(excl_i), k_top,
-            _p(idx), _p(sc), _p(st), int(nthreads))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_recommend_scores", dtype, S=_p(S), lds=lds, m=m, n=n, Xexcl_csr_p=_host_excl_p(excl_p), Xexcl_csr_i=_p(excl_i),
+            k_top=k_top, idx=_p(idx), score=_p(sc), status=_p(st), nthreads=int(nthreads))
     return idx, sc, st
 
 
 def recommend_scores_device(dtype, S, lds, m, n, excl_p, excl_i, nnz_excl, k_top, idx, score, status, stream=0):
     """Device-pointer entry (rm_recommend_scores_dev_*): every array argument is an integer device address (0 == NULL: `excl_p` =
     nothing is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
-    lib = load()
-    fn = getattr(lib, "rm_recommend_scores_dev_" + _suffix(dtype))
-    rc = fn(_dp(S), lds, m, n, _dp(excl_p), _dp(excl_i), nnz_excl, k_top, _dp(idx), _dp(score), _dp(status), _dp(stream))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_recommend_scores_dev", dtype, S=_dp(S), lds=lds, m=m, n=n, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
+            nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
 
 
 def debug_scores(A, B):
-    lib = load()
     dtype = A.dtype.type
     A = np.ascontiguousarray(A)
     B = np.ascontiguousarray(B)
     out = np.empty((A.shape[0], B.shape[0]), dtype=dtype)
-    fn = getattr(lib, "rm_debug_scores_" + _suffix(dtype))
-    rc = fn(_p(A), A.shape[1], _p(B), B.shape[1], A.shape[0], B.shape[0], A.shape[1], _p(out))
-    if rc:
-        _raise(lib, rc)
+    _invoke("rm_debug_scores", dtype, A=_p(A), lda=A.shape[1], B=_p(B), ldb=B.shape[1], m=A.shape[0], n=B.shape[0], k=A.shape[1], out=_p(out))
     return out
 
 

@@ -133,29 +133,24 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+# parameter of include/recometrics_hip.h -> key of the state, where they differ (the lists' exclusion matrix is the state's train matrix)
+STATE_KEY = {"Xtrain_csr_p": "train_p", "Xtrain_csr_i": "train_i", "Xexcl_csr_p": "train_p", "Xexcl_csr_i": "train_i", "nnz_excl": "nnz_train",
+             "Xtest_csr_p": "test_p", "Xtest_csr_i": "test_i", "Xtest_csr": "test_v", "k_metrics": "K", "k_top": "K", "topk_idx": "idx", "topk_score": "score"}
+
+
 def call(lib, entry, suffix, defects):
-    """the spoiled call; returns (rc, message, the output arrays it was given)"""
-    scores, lists, rank, host = FAMILIES[entry]
+    """the spoiled call, its arguments ordered by the binding's table of signatures; returns (rc, message, the output arrays it was given)"""
+    from recometrics_amd import _binding
     st = base_state(entry, SUFFIXES[suffix])
     table = defects_of(entry)
     for d in defects:
         table[d](st)
-    src = [_p(st["S"]), st["lds"], st["m"], st["n"]] if scores else [_p(st["A"]), st["lda"], _p(st["B"]), st["ldb"], st["m"], st["n"], st["k"]]
-    train = [_p(st["train_p"]), _p(st["train_i"])] + ([] if host else [st["nnz_train"]])
-    test = [_p(st["test_p"]), _p(st["test_i"])]
-    if rank:
-        outs = [st["idx"], st["score"], st["pos_rank"], st["status"]]
-        args = src + train + test + [st["K"], 1, 1, 2, 1, 1] + [_p(o) for o in outs]
-    elif lists:
-        outs = [st["idx"], st["score"], st["status"]]
-        args = src + train + [st["K"]] + [_p(o) for o in outs] + [1 if host else None]
-    else:
-        outs = st["outs"]
-        test += [_p(st["test_v"])] + ([] if host else [st["nnz_test"]])
-        noise = [] if scores else [1]
-        tail = ([1] if host else []) + ([] if scores else [5]) + ([] if host else [None])        # nthreads, seed, stream
-        args = src + train + test + [st["K"], 0] + noise + [_p(o) for o in outs] + [1, 2, 1] + tail
-    rc = getattr(lib, entry + "_" + suffix)(*args)
+    outs = [st[name] for name in ("idx", "score", "pos_rank", "status") if name in st] + st.get("outs", [])
+    st.update(zip(_binding.OUTPUTS, st.pop("outs", [])))
+    st.update(cumulative=0, break_ties_with_noise=1, consider_cold_start=1, min_items_pool=2, min_pos_test=1, nthreads=1,
+              seed=1 if entry == "rm_rank" else 5, stream=None)
+    values = [st[STATE_KEY.get(name, name)] for name, _ in _binding.SIGNATURES[entry + "_" + suffix][0]]
+    rc = getattr(lib, entry + "_" + suffix)(*[_p(v) if v is None or isinstance(v, np.ndarray) else v for v in values])
     return rc, (lib.rm_last_error() or b"").decode(), [o for o in outs if o is not None]
 
 

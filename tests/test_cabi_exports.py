@@ -14,6 +14,64 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(rm_[a-z0-9_]+)\s*\(", text)))
 
 
+def _declarations():
+    """symbol -> (return type, [(parameter type, parameter name)]) of every rm_* declaration of the header"""
+    text = open(os.path.join(ROOT, "include", "recometrics_hip.h")).read()
+    text = re.sub(r"^\s*#.*$", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S), flags=re.M)
+    found = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(rm_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else [re.fullmatch(r"\s*(.*?)(\w+)\s*", p).groups() for p in params.split(",")]
+        found[name] = (" ".join(ret.split()), [(" ".join(t.split()), n) for t, n in params])
+    return found
+
+
+def _c_kind(ctype):
+    """a C type of the header by kind and width"""
+    if "*" in ctype:
+        return "char *" if ctype == "const char *" else "pointer"
+    return {"void": "void", "double": "double", "int": ("signed", 4), "int32_t": ("signed", 4), "int64_t": ("signed", 8),
+            "uint64_t": ("unsigned", 8), "size_t": ("unsigned", 8)}[ctype.replace("const ", "")]
+
+
+def _ctypes_kind(t):
+    """a ctypes type by kind and width, not by class: c_int32 is c_int and c_uint64 is c_size_t here"""
+    if t is None:
+        return "void"
+    if t is ctypes.c_char_p:
+        return "char *"
+    if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+        return "pointer"
+    if t is ctypes.c_double:
+        return "double"
+    assert issubclass(t, ctypes._SimpleCData) and t._type_ in "iIlLqQ", t
+    return ("unsigned" if t(-1).value > 0 else "signed", ctypes.sizeof(t))
+
+
+def test_the_binding_states_every_declaration_of_the_header():
+    """_binding.SIGNATURES against include/recometrics_hip.h: the same symbols, and per symbol the same parameter names in the same
+    order, every type of the same kind and width (an int32 where the header says int64_t, or two neighbours swapped, fails here)"""
+    from recometrics_amd import _binding
+    declared = _declarations()
+    assert len(declared) == 43 and sorted(declared) == _declared_symbols()
+    assert set(_binding.SIGNATURES) == set(declared) and _binding.EXPORTS == tuple(_binding.SIGNATURES)
+    for name, (ret, params) in declared.items():
+        mine, restype = _binding.SIGNATURES[name]
+        assert [n for n, _ in mine] == [n for _, n in params], name
+        assert [_ctypes_kind(t) for _, t in mine] == [_c_kind(t) for t, _ in params], name
+        assert _ctypes_kind(restype) == _c_kind(ret), name
+
+
+def test_the_invoker_refuses_a_missing_or_unknown_name_before_the_call(monkeypatch):
+    import numpy as np
+    from recometrics_amd import _binding
+    monkeypatch.setattr(_binding, "load", lambda: pytest.fail("the library was reached"))
+    values = dict(A=None, lda=4, B=None, ldb=4, m=2, n=8, k=4, out=None)
+    with pytest.raises(KeyError, match="ldb"):
+        _binding._invoke("rm_debug_scores", np.float32, **{name: v for name, v in values.items() if name != "ldb"})
+    with pytest.raises(TypeError, match="rm_debug_scores_f64 has no parameter lds, seed"):
+        _binding._invoke("rm_debug_scores", np.float64, seed=1, lds=8, **values)
+
+
 def test_header_declares_the_reference_boundary():
     syms = _declared_symbols()
     for must in ("rm_calc_metrics_f32", "rm_calc_metrics_f64", "rm_has_openmp", "rm_last_error"):
@@ -27,8 +85,6 @@ def test_library_builds_and_exports_every_declared_symbol():
     lib = ctypes.CDLL(path)
     for sym in _declared_symbols():
         assert hasattr(lib, sym), "missing export: " + sym
-    from recometrics_amd import _binding
-    assert set(_binding.EXPORTS) == set(_declared_symbols())
     # host-only calls that need no GPU
     lib.rm_last_error.restype = ctypes.c_char_p
     assert lib.rm_has_openmp() == 1
