@@ -306,8 +306,12 @@ void rm_debug_sweep_launched_reset(void);
  * out[8] = user lanes (slots) of the launch that out[1] brackets -- when the blocks of streamed users run beside the main
  * launch on a second stream, out[1] times the main launch only --, out[9] = user lanes of the whole call,
  * out[10] = 1 when the call ran on what the context kept of the previous call's train / test split (same arrays, same contents:
- * DESIGN.md section 1), 0 when it planned and validated the split itself, -1 for the calls that never reuse one.
- * Forces a synchronisation of that stream.  Returns the number of values written. */
+ * DESIGN.md section 1), 0 when it planned and validated the split itself, -1 for the calls that never reuse one,
+ * out[11] = users whose top-K bound that call seeded from the lists the call before it left on the kept split (k_hint_bounds,
+ * DESIGN.md section 2; 0 where there were none, or RM_DEBUG_NO_WARM_BOUNDS is set).
+ * Forces a synchronisation of that stream.  Returns the number of values written (at most 12).
+ * (Beside this API the library exports one hook for the tests of those bounds, not declared here: rm_debug_set_list_ids, stated in
+ * recometrics_amd/_binding.py TEST_HOOKS and csrc/rm_lib.hip.) */
 int rm_get_timings(double *out, int n);
 
 /* Releases the cached device workspace of the current device. */

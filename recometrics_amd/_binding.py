@@ -67,6 +67,8 @@ SIGNATURES.update({
     "rm_csr_sort_rows": ((("indptr", _vp), ("indices", _vp), ("values", _vp), ("value_bytes", _i32), ("m", _i32), ("nthreads", _i32)), _ci),
 })
 EXPORTS = tuple(SIGNATURES)
+# test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
+TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
 
 class HipLibraryMissing(ImportError):
@@ -95,6 +97,10 @@ def load():
                 "recometrics_amd: %s is missing -- build it with `python -m recometrics_amd.build` "
                 "(there is no CPU fallback)" % _LIB_PATH)
         _lib = _declare(C.CDLL(_LIB_PATH), SIGNATURES)
+        for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
+            fn = getattr(_lib, name, None)
+            if fn is not None:
+                fn.argtypes, fn.restype = [ctype for _, ctype in params], restype
     return _lib
 
 
@@ -201,6 +207,23 @@ def timings():
     keys = ("prep_ms", "sweep_ms", "finalize_ms", "device_ms", "sweep_launches", "item_splits", "sweep_blocks", "lds_bytes",
             "timed_slots", "total_slots", "split_reused")
     return {k: buf[i] for i, k in enumerate(keys[:n])}
+
+
+def hinted_users():
+    """Users whose top-K bound the most recent pass seeded from the lists the call before it left on the kept split (slot 12 of
+    rm_get_timings; 0 when the pass had no such lists, or a library from before there were any)."""
+    lib = load()
+    buf = (C.c_double * 12)()
+    return int(buf[11]) if lib.rm_get_timings(buf, 12) >= 12 else 0
+
+
+def set_list_ids(ids):
+    """Test hook (rm_debug_set_list_ids): overwrites the item ids of the lists the context keeps for its next pass with `ids` [m, K]."""
+    lib = load()
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    rc = lib.rm_debug_set_list_ids(ids.ctypes.data_as(C.POINTER(_i32)), ids.shape[0], ids.shape[1])
+    if rc:
+        _raise(lib, rc)
 
 
 def csr_rows_sorted(indptr, indices, nthreads=0):

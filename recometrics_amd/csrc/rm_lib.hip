@@ -55,7 +55,7 @@ struct RmError { int code; std::string msg; };
 // tests/test_switches_cpu.py compares this table with that list); nothing here turns a feature of the call off.
 struct Switches {
     bool no_train_bits, no_spec, no_side, ext_topk, no_test_mask, hbm_lists, nsub2, no_pending, no_pos_beside, no_seed, rank_generic,
-         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk, no_split_cache;
+         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk, no_split_cache, no_warm_bounds;
     long long free_mb, stream_budget_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed, split_cache_mb;      // -1 = not set
     unsigned long long epoch = 0;                                              // counts load(): what a context keeps of a split was decided under one set of switches
     double batch_users;                                                        // 0 = not set
@@ -81,6 +81,7 @@ struct Switches {
         lane_cap_min = num("RM_DEBUG_LANE_CAP_MIN");          // the smallest lane buffers that work: a selection every few tiles (tests)
         no_split_cache = on("RM_DEBUG_NO_SPLIT_CACHE");        // every call plans, validates and builds its split's tables itself (A/B timing, the tests' reference path)
         split_cache_mb = num("RM_SPLIT_CACHE_MB");              // the largest split (bytes of its five arrays) a context keeps copies of; 0 = none
+        no_warm_bounds = on("RM_DEBUG_NO_WARM_BOUNDS");        // a call on the kept split seeds its top-K bounds as a first call does: no k_hint_bounds (A/B timing, the tests' reference path)
         epoch++;
         const char *b = getenv("RM_BATCH_USERS"); batch_users = b ? atof(b) : 0.0;
         const char *s = getenv("RM_DEBUG_SPLITS"); splits = s ? s : "";
@@ -185,7 +186,30 @@ struct SplitCache {
     static constexpr const char *copy_names[SPLIT_ARRAYS] = {"split_train_p", "split_train_i", "split_test_p", "split_test_i", "split_test_v"};
     bool valid = false; SplitKey key{}; Plan hp{}; bool check_nan = false, dense_masked = false;
     std::vector<std::pair<std::string, unsigned long long>> stamps;       // the buffers the record speaks of, as allocated then
-    void invalidate() { valid = false; }
+    // "merged" as allocated when the last plain pass on this split enqueued its k_finalize: the buffer then holds that pass's ordered
+    // top-K lists, the advice of the next pass (k_hint_bounds).  Taken (and so voided) when a pass starts, set again when it has
+    // enqueued everything: a pass that fails or is interrupted leaves none.  0 = no lists.
+    unsigned long long lists_stamp = 0;
+    // Whether that advice is worth its kernel is the model's business, not the split's: a pass whose bounds mostly stayed BELOW what the
+    // positives gave anyway (fewer than half of them raised a word: the model has little to do with the last one) makes the next
+    // `hint_skip` passes run without the kernel -- 1, then 2, 4, ... up to HINT_BACKOFF_MAX for every further such pass, back to none
+    // after a pass whose bounds did raise.  `hint_judge`: the last pass launched the kernel and its counts have not been looked at yet.
+    static constexpr int HINT_BACKOFF_MAX = 16;
+    int hint_skip = 0, hint_backoff = 0; bool hint_judge = false;
+    void invalidate() { valid = false; lists_stamp = 0; hint_skip = hint_backoff = 0; hint_judge = false; }
+    // the counts of the last launch (accepted, raised), then: does this pass launch?
+    bool hints_due(const int *counts)
+    {
+        if (hint_judge) {
+            hint_judge = false;
+            if (2LL * counts[1] < counts[0]) { hint_backoff = hint_backoff ? std::min(2 * hint_backoff, HINT_BACKOFF_MAX) : 1; hint_skip = hint_backoff; }
+            else hint_backoff = 0;
+        }
+        if (hint_skip > 0) { hint_skip--; return false; }
+        return true;
+    }
+    bool take_lists(const Workspace &ws) { const unsigned long long s = lists_stamp; lists_stamp = 0; return s != 0 && s == ws.peek("merged").stamp; }
+    void keep_lists(const Workspace &ws) { lists_stamp = ws.peek("merged").stamp; }
     void keep(const Workspace &ws, const char *name) { stamps.emplace_back(name, ws.peek(name).stamp); }
     bool holds(const Workspace &ws, const SplitKey &k) const
     {
@@ -254,6 +278,9 @@ struct Ctx {
     PackedItems packed; DenseRows dense; DiscountTable discounts;    // what "Bp", "train_bits" and "log2tab" of `ws` hold
     SplitCache split;                                                // ... and what the plan stage's buffers hold of the last call's split
     int split_reused = -1;               // the most recent pass: 1 = it ran on what `split` kept, 0 = it planned itself, -1 = a pass that never reuses
+    // the warm bounds of the most recent pass that launched k_hint_bounds: page-locked, the users that got a bound and those whose bound
+    // raised the positives' (copied behind the sweep's launch; read behind a later host wait: rm_get_timings, the next pass's verdict)
+    int *hint_counts = nullptr; bool hints_ran = false;
     bool high_priority = false;          // streams of this context are created with the highest priority (the exact passes of the tie noise)
     Plan *pinned_plan = nullptr;                                                    // page-locked landing place of the plan read-back
     void stage_ms(float ms[4]) const       // prep / sweep / finalize / total of the most recent pass, from its four events (which have completed)
@@ -975,6 +1002,7 @@ struct Pipeline {
     bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
     // the split the context kept (SplitCache): may this pass run on it, does it, may the next one run on this pass's
     bool allow_reuse = true, reused = false, keepable = false; SplitKey split_key{};
+    bool hints = false; int *hint_counts_dev = nullptr;  // ... and its previous lists give this pass bounds (k_hint_bounds)
     Plan hp{};
     int n_slots = 0, n_stream = 0, stream_slot0 = 0; bool check_nan = false;
     // geometry
@@ -1104,6 +1132,12 @@ struct Pipeline {
         cx.split_reused = keepable ? 0 : -1;
         reused = keepable && allow_reuse && cx.split.holds(ws, split_key) &&
                  (!dense_ok || cx.dense.fits(ws, m, dense_row_words(n), cx.split.dense_masked));
+        // The lists the last pass on the kept split left in `merged` are this pass's advice (k_hint_bounds), whichever pass this is takes the
+        // record away: export_ranks() of a plain pass on the kept or newly kept split makes the next one.  (Same key = same m, K,
+        // precision and list scheme; the calls whose lists are the replace-the-minimum ones, seeded by k_seed_thresholds.)
+        const bool lists_kept = cx.split.take_lists(ws);
+        cx.hints_ran = false;
+        hints = reused && lists_kept && !g_sw.no_warm_bounds && !g_sw.no_seed && want_auc && !want_lane && !ext_topk && K <= HINT_MAX_K;
         if (reused) {
             c.train_p = (const int *)cx.split.copy(ws, 0); c.train_i = (const int *)cx.split.copy(ws, 1);
             c.test_p = (const int *)cx.split.copy(ws, 2); c.test_i = (const int *)cx.split.copy(ws, 3);
@@ -1280,10 +1314,33 @@ struct Pipeline {
             hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, ent_masked);      // (`ent_masked`: kept)
             pos.mark(POS_SCORES_DONE);
         }
+        hints = hints && kept.hp.n_slots > 0;
+        if (hints) {
+            // (the kernel's two counters, zeroed here where the call's stream is idle; the launch itself follows the verdict: sweep())
+            try { hint_counts_dev = (int *)ws.get("hint_counts", 2 * sizeof(int)); } catch (const RmError &) { hints = false; }
+            if (hints && !cx.hint_counts) { HIP_CHECK(hipHostMalloc((void **)&cx.hint_counts, 64, hipHostMallocDefault)); cx.hint_counts[0] = cx.hint_counts[1] = 0; }
+            if (hints) HIP_CHECK(hipMemsetAsync(hint_counts_dev, 0, 2 * sizeof(int), stream));
+        }
         check_launch(hipGetLastError());
         hp = kept.hp; check_nan = kept.check_nan;
         bits_early = dense_ok; bits_early_masked = kept.dense_masked; masked_from_bits = true;
         RM_TRACE_POINT("run: kept split, comparison + positives enqueued");
+    }
+    // The bounds the previous pass's lists give this one (k_hint_bounds, rm_prep.hpp): on the call's stream behind the preparation --
+    // k_seed_thresholds has written thr_shared, the kernel raises it -- and in front of the sweep, in the sweep's stage of the timings: the
+    // positives' chain, which fills the device until then, is left alone.  The finalisation, which overwrites the lists the kernel
+    // reads, follows on the same stream.
+    // Behind verdict(): the host has waited for this pass's comparison, which the stream runs behind the whole pass before -- that pass's
+    // counts have landed, and SplitCache::hints_due says whether its advice was worth repeating.
+    void launch_hints()
+    {
+        if (!cx.split.hints_due(cx.hint_counts)) { hints = false; return; }
+        const int users_per_wave = K <= WAVE ? WAVE / K : 1;
+        const long long waves = cdiv(m, users_per_wave);
+        HintArgs<T, ThrT> ha{m, n, k, K, c.A, c.lda, c.B, c.ldb, c.train_p, c.train_i, flags, user_nslots, uslot_base, slot_index,
+                             (const Entry<T> *)merged, thr_shared, hint_counts_dev};
+        hipLaunchKernelGGL((k_hint_bounds<T, ThrT>), dim3(cdiv(waves, HINT_WAVES)), dim3(HINT_WAVES * WAVE), 0, stream, ha);
+        cx.split.hint_judge = true; cx.hints_ran = true;
     }
     // The host's wait of a pass on the kept split, in front of the sweep's launch (the device is busy with the positives' chain):
     // are the caller's arrays the kept ones, and does the sweep variant that was prepared fit this call's factors?  If not, the pass is
@@ -1539,6 +1596,7 @@ struct Pipeline {
             return;
         }
         const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
+        if (hints && merged && thr_shared) launch_hints();
         if (g.u_split > 0) {
             // Depth split: the two launches run side by side on two streams so that neither pays a partially filled last round of its own.
             const int u_split = g.u_split, n_ublocks = g.n_ublocks;
@@ -1566,6 +1624,7 @@ struct Pipeline {
         }
         RM_TRACE_POINT("run: sweep enqueued");
         HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
+        if (hints) HIP_CHECK(hipMemcpyAsync(cx.hint_counts, hint_counts_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
         if (lane_lists) {
             collect = true;
             collect_g = CollectGeom{sa.ublock0, sa.n_ublocks, g.n_splits, g.tail_ublocks, g.tail_splits, g.nsub, GU, P::lanes_per_user, sa.lane_cap, g.part_extra ? g.n_part - 1 : -1};
@@ -1721,6 +1780,8 @@ struct Pipeline {
                                (want_auc && n_slots > 0) ? 1 : 0, c.status);
         RM_TRACE_POINT("run: finalisation enqueued");
         if (side.marked(SIDE_SPLIT_KEPT)) { side.await(SIDE_SPLIT_KEPT, stream); cx.split.valid = true; }      // (keep_split's copies)
+        // (`merged` now holds this pass's lists, or will when the stream gets there: the advice of the next pass on this split)
+        if (keepable && cx.split.valid && merged && !c.reco && n_slots > 0) cx.split.keep_lists(ws);
         HIP_CHECK(hipEventRecord(cx.ev[EV_END], stream));
         HIP_CHECK(hipEventRecord(cx.done, stream));
         cx.ev_recorded = true;
@@ -3116,6 +3177,40 @@ extern "C" void rm_debug_sweep_launched_reset(void)
     for (auto &prec : g_sweep_launched) for (auto &c : prec) c.store(0, std::memory_order_relaxed);
 }
 
+// Test hook of the warm bounds (tests only; stated in _binding.TEST_HOOKS, not part of the header's API): the item ids of the lists the
+// current device's context keeps for its next pass on the kept split are overwritten with ids[m][K] (host) -- the scores stay --, so
+// that a test can hand k_hint_bounds advice no pass would leave.  RM_ERR_INVALID when the context keeps no lists of that shape.
+template <class T> __global__ void k_set_list_ids(long long count, Entry<T> *lists, const int *ids)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) lists[i].idx = ids[i];
+}
+extern "C" int rm_debug_set_list_ids(const int32_t *ids, int32_t m, int32_t K)
+{
+    return guarded([&] {
+        Ctx &cx = context(0);
+        std::lock_guard<std::mutex> lk(cx.mu);
+        const SplitCache &kept = cx.split;
+        const Workspace::Buf buf = cx.ws.peek("merged");
+        const long long count = (long long)m * K;
+        if (!ids || m <= 0 || K <= 0 || !kept.valid || kept.lists_stamp == 0 || kept.lists_stamp != buf.stamp || kept.key.m != m || kept.key.K != K ||
+            (size_t)count * (kept.key.elem == 4 ? sizeof(Entry<float>) : sizeof(Entry<double>)) > buf.bytes)
+            throw RmError{RM_ERR_INVALID, "rm_debug_set_list_ids: the context keeps no lists of " + std::to_string(m) + " x " + std::to_string(K) + " entries"};
+        HIP_CHECK(hipDeviceSynchronize());
+        int *dev = nullptr;
+        HIP_CHECK(hipMalloc((void **)&dev, sizeof(int) * (size_t)count));
+        hipError_t e = hipMemcpy(dev, ids, sizeof(int) * (size_t)count, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            if (kept.key.elem == 4) hipLaunchKernelGGL(k_set_list_ids<float>, dim3(cdiv(count, 256)), dim3(256), 0, nullptr, count, (Entry<float> *)buf.ptr, (const int *)dev);
+            else hipLaunchKernelGGL(k_set_list_ids<double>, dim3(cdiv(count, 256)), dim3(256), 0, nullptr, count, (Entry<double> *)buf.ptr, (const int *)dev);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        (void)hipFree(dev);
+        HIP_CHECK(e);
+    });
+}
+
 extern "C" int rm_get_timings(double *out, int n)
 {
     Ctx *cx = g_last_ctx;
@@ -3126,11 +3221,12 @@ extern "C" int rm_get_timings(double *out, int n)
         cx->stage_ms(ms);
     }
     for (int i = 0; i < 4; i++) cx->timings[i] = cx->acc[i] + ms[i];
-    const int cnt = n < 11 ? n : 11;
+    const int cnt = n < 12 ? n : 12;
     for (int i = 0; i < cnt && i < 8; i++) out[i] = cx->timings[i];
     if (cnt > 8) out[8] = cx->timed_slots;
     if (cnt > 9) out[9] = cx->total_slots;
     if (cnt > 10) out[10] = cx->split_reused;
+    if (cnt > 11) out[11] = (cx->hints_ran && cx->ev_recorded && cx->hint_counts) ? cx->hint_counts[0] : 0;      // (EV_END is behind the counts' copy)
     return cnt;
 }
 

@@ -1053,18 +1053,92 @@ __global__ __launch_bounds__(256) void k_test_masked(int m, const int *test_p, c
     }
 }
 
+// The scores of a wavefront's 64 (user, item) pairs, one pair per lane: k_pos_scores_flat's test entries and k_hint_bounds' advised
+// items go through this one routine, so both are the sweep's scores to the bit.  `live`: the ballot of `mine`, not zero; a lane that
+// is not `mine` reads nothing and returns 0.  `rows`: the wavefront's own [WAVE][LD] of LDS.
+template <class T> struct FlatDot {
+    static constexpr int PB = 64;                               // bytes of a row per staged piece
+    static constexpr int CH = PB / (int)sizeof(T);              // factors per piece: 16 floats / 8 doubles
+    static constexpr int VE = 16 / (int)sizeof(T);              // factors per 16-byte vector
+    static constexpr int LPR = PB / 16;                         // lanes per row piece
+    static constexpr int RPI = WAVE / LPR;                      // rows covered by one load instruction: 16
+    static constexpr int LD = CH + VE;                          // padded row stride in LDS
+    typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
+    static __device__ __forceinline__ T run(const T *A, size_t lda, const T *B, size_t ldb, int k, int u, int item, bool mine,
+                                            unsigned long long live, T (*rows)[LD], int lane)
+    {
+        const int rsub = lane / LPR, piece = lane % LPR;
+        const bool vec_ok = ((((size_t)B) | (ldb * sizeof(T))) & 15) == 0, avec_ok = ((((size_t)A) | (lda * sizeof(T))) & 15) == 0;
+        const T *brow[WAVE / RPI];
+        #pragma unroll
+        for (int q = 0; q < WAVE / RPI; q++) brow[q] = B + (size_t)__shfl(item, q * RPI + rsub) * ldb;
+        const T *Au = A + (size_t)u * lda;
+        T s = 0;
+        for (int k0 = 0; k0 < k; k0 += CH) {
+            const int e0 = k0 + piece * VE;                         // first factor of this lane's 16 bytes
+            VT bv[WAVE / RPI];
+            #pragma unroll
+            for (int q = 0; q < WAVE / RPI; q++) {
+                const int p = q * RPI + rsub;
+                VT x;
+                #pragma unroll
+                for (int i = 0; i < VE; i++) x[i] = (T)0;
+                if (((live >> p) & 1) && e0 < k) {
+                    if (vec_ok && e0 + VE <= k) x = *(const VT *)(brow[q] + e0);
+                    else {
+                        #pragma unroll
+                        for (int i = 0; i < VE; i++) if (e0 + i < k) x[i] = brow[q][e0 + i];
+                    }
+                }
+                bv[q] = x;
+            }
+            VT av[CH / VE];
+            #pragma unroll
+            for (int j = 0; j < CH / VE; j++) {
+                VT x;
+                #pragma unroll
+                for (int i = 0; i < VE; i++) x[i] = (T)0;
+                const int f0 = k0 + j * VE;
+                if (mine && f0 < k) {
+                    if (avec_ok && f0 + VE <= k) x = *(const VT *)(Au + f0);
+                    else {
+                        #pragma unroll
+                        for (int i = 0; i < VE; i++) if (f0 + i < k) x[i] = Au[f0 + i];
+                    }
+                }
+                av[j] = x;
+            }
+            #pragma unroll
+            for (int q = 0; q < WAVE / RPI; q++) *(VT *)&rows[q * RPI + rsub][piece * VE] = bv[q];
+            // (the pieces change lanes through LDS: fenced like k_train_bits / k_pos_place, not left to the compiler's alias analysis)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+            const T *r = rows[lane];
+            if (k0 + CH <= k) {
+                #pragma unroll
+                for (int j = 0; j < CH / VE; j++) {
+                    const VT b = *(const VT *)(r + j * VE);
+                    #pragma unroll
+                    for (int i = 0; i < VE; i++) s = fma_chain_step(av[j][i], b[i], s);
+                }
+            } else {
+                #pragma unroll
+                for (int j = 0; j < CH / VE; j++) {
+                    const VT b = *(const VT *)(r + j * VE);
+                    #pragma unroll
+                    for (int i = 0; i < VE; i++) if (k0 + j * VE + i < k) s = fma_chain_step(av[j][i], b[i], s);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // the rows are rewritten by the next chunk
+        }
+        return s;
+    }
+};
+
 constexpr int POSF_WAVES = 4;
 template <class T>
 __global__ __launch_bounds__(POSF_WAVES * WAVE) void k_pos_scores_flat(PosArgs<T> a, const int *ent_user)
 {
-    constexpr int PB = 64;                                      // bytes of a row per staged piece
-    constexpr int CH = PB / (int)sizeof(T);                     // factors per piece: 32 floats / 16 doubles
-    constexpr int VE = 16 / (int)sizeof(T);                     // factors per 16-byte vector
-    constexpr int LPR = PB / 16;                                // lanes per row piece
-    constexpr int RPI = WAVE / LPR;                             // rows covered by one load instruction: 8
-    constexpr int LD = CH + VE;                                 // padded row stride in LDS (144 B)
-    typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
-    __shared__ __attribute__((aligned(16))) T rows[POSF_WAVES][WAVE][LD];
+    __shared__ __attribute__((aligned(16))) T rows[POSF_WAVES][WAVE][FlatDot<T>::LD];
     if (a.plan->csr_bad & (CSR_BAD_INDPTR | CSR_BAD_INDEX)) return;       // (the test items index the item factors)
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const long long e = (long long)a.test_p[0] + ((long long)blockIdx.x * POSF_WAVES + wv) * WAVE + lane;
@@ -1075,69 +1149,7 @@ __global__ __launch_bounds__(POSF_WAVES * WAVE) void k_pos_scores_flat(PosArgs<T
     const bool mine = in && (f & UF_ACTIVE) && !(f & UF_ONLY_NDCG);
     const unsigned long long live = __ballot(mine);
     if (!live) return;
-    const int rsub = lane / LPR, piece = lane % LPR;
-    const bool vec_ok = ((((size_t)a.B) | (a.ldb * sizeof(T))) & 15) == 0, avec_ok = ((((size_t)a.A) | (a.lda * sizeof(T))) & 15) == 0;
-    const T *brow[WAVE / RPI];
-    #pragma unroll
-    for (int q = 0; q < WAVE / RPI; q++) brow[q] = a.B + (size_t)__shfl(item, q * RPI + rsub) * a.ldb;
-    const T *Au = a.A + (size_t)u * a.lda;
-    T s = 0;
-    for (int k0 = 0; k0 < a.k; k0 += CH) {
-        const int e0 = k0 + piece * VE;                         // first factor of this lane's 16 bytes
-        VT bv[WAVE / RPI];
-        #pragma unroll
-        for (int q = 0; q < WAVE / RPI; q++) {
-            const int p = q * RPI + rsub;
-            VT x;
-            #pragma unroll
-            for (int i = 0; i < VE; i++) x[i] = (T)0;
-            if (((live >> p) & 1) && e0 < a.k) {
-                if (vec_ok && e0 + VE <= a.k) x = *(const VT *)(brow[q] + e0);
-                else {
-                    #pragma unroll
-                    for (int i = 0; i < VE; i++) if (e0 + i < a.k) x[i] = brow[q][e0 + i];
-                }
-            }
-            bv[q] = x;
-        }
-        VT av[CH / VE];
-        #pragma unroll
-        for (int j = 0; j < CH / VE; j++) {
-            VT x;
-            #pragma unroll
-            for (int i = 0; i < VE; i++) x[i] = (T)0;
-            const int f0 = k0 + j * VE;
-            if (mine && f0 < a.k) {
-                if (avec_ok && f0 + VE <= a.k) x = *(const VT *)(Au + f0);
-                else {
-                    #pragma unroll
-                    for (int i = 0; i < VE; i++) if (f0 + i < a.k) x[i] = Au[f0 + i];
-                }
-            }
-            av[j] = x;
-        }
-        #pragma unroll
-        for (int q = 0; q < WAVE / RPI; q++) *(VT *)&rows[wv][q * RPI + rsub][piece * VE] = bv[q];
-        // (the pieces change lanes through LDS: fenced like k_train_bits / k_pos_place, not left to the compiler's alias analysis)
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        const T *r = rows[wv][lane];
-        if (k0 + CH <= a.k) {
-            #pragma unroll
-            for (int j = 0; j < CH / VE; j++) {
-                const VT b = *(const VT *)(r + j * VE);
-                #pragma unroll
-                for (int i = 0; i < VE; i++) s = fma_chain_step(av[j][i], b[i], s);
-            }
-        } else {
-            #pragma unroll
-            for (int j = 0; j < CH / VE; j++) {
-                const VT b = *(const VT *)(r + j * VE);
-                #pragma unroll
-                for (int i = 0; i < VE; i++) if (k0 + j * VE + i < a.k) s = fma_chain_step(av[j][i], b[i], s);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // the rows are rewritten by the next chunk
-    }
+    T s = FlatDot<T>::run(a.A, a.lda, a.B, a.ldb, a.k, u, item, mine, live, rows[wv], lane);
     // (whether the train row holds the item is not known here: k_pos_apply_masked overwrites those entries afterwards.  A user
     // flagged for one of them goes through an exact pass it did not need -- same results.)
     if (mine && a.noise_E) {
@@ -1162,6 +1174,87 @@ __global__ void k_pos_apply_masked(PosArgs<T> a, const unsigned char *ent_masked
     const T inf = (T)__int_as_float(0x7f800000);
     a.pos_tmp[e] = inf;
     if (sizeof(T) == 4 && a.pos_key) a.pos_key[e] = ((unsigned long long)ord_key((float)inf) << 32) | (unsigned)~a.test_i[e];
+}
+
+// WARM BOUNDS (calls on a kept split, replace-the-minimum lists).  The workspace still holds the ordered top-K lists of the previous
+// call on this split (`lists`, [m][K]); ANY K distinct candidates of a user bound its K-th best score from below (the argument of
+// k_seed_thresholds and k_seed_from_sample), so the K item ids of that list, scored with THIS call's factors, give a bound that is
+// the final K-th best itself when the model has not moved and a weak one when it is unrelated.  Only the ids are taken as advice,
+// and nothing about them is trusted: a user gets a hint when it is evaluated for ranks in one primary slot, has at least K
+// candidates, and all K ids lie in [0, n), are pairwise distinct and are no train items of the user (binary search in the sparse
+// row: the dense rows may mark the test items too, which are candidates); every one of the K scores must be finite.  The scores come from
+// FlatDot -- a bound ABOVE the true K-th best would drop list entries, so "close" is not good enough.  The bound, ord_key(the smallest
+// of the K scores), RAISES the user's word of thr_shared (atomicMax) behind k_seed_thresholds, which wrote the positives' bound there:
+// the larger of the two is the seed.  The kernel runs on the call's stream between the preparation and the sweep -- its time is the
+// sweep stage's, whose candidates it removes, not the positives' chain's.
+// counts[0]: the users that got a bound; counts[1]: those whose bound RAISED the word, i.e. lay above what the positives gave -- the
+// host's measure of whether the advice was worth the kernel (SplitCache::hint_*): a model unrelated to the last one raises few.  One
+// atomic per block and counter, into two words the pass zeroed.
+// Layout: a wavefront takes 64 / K users, a lane one (user, place) pair; K > 64: one user, a round per 64 places.
+constexpr int HINT_WAVES = 4, HINT_MAX_K = 256;
+template <class T, class KeyT> struct HintArgs {
+    int m, n, k, K;
+    const T *A; size_t lda; const T *B; size_t ldb;
+    const int *train_p, *train_i, *flags, *user_nslots, *uslot_base, *slot_index;
+    const Entry<T> *lists;
+    KeyT *thr_shared; int *counts;
+};
+template <class T, class KeyT>
+__global__ __launch_bounds__(HINT_WAVES * WAVE) void k_hint_bounds(HintArgs<T, KeyT> a)
+{
+    __shared__ __attribute__((aligned(16))) T rows[HINT_WAVES][WAVE][FlatDot<T>::LD];
+    __shared__ int ids[HINT_WAVES][HINT_MAX_K];
+    __shared__ T low[HINT_WAVES][WAVE];
+    __shared__ int refused[HINT_WAVES][WAVE];
+    __shared__ int tally[2];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int K = a.K;
+    const int upw = K <= WAVE ? WAVE / K : 1, rounds = (K + WAVE - 1) / WAVE;
+    const int ul = K <= WAVE ? lane / K : 0;                      // the lane's user of the wavefront, its first place
+    const int j0 = K <= WAVE ? lane - ul * K : lane;
+    const long long ub = ((long long)blockIdx.x * HINT_WAVES + wv) * upw;
+    if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+    __syncthreads();
+    const bool own = ul < upw && ub + ul < a.m;                   // (a wavefront behind the last user: nobody's, it only meets the barriers)
+    const int u = own ? (int)(ub + ul) : 0;
+    // (the user's flags first: whoever is not evaluated for ranks in one slot reads neither its rows nor its list)
+    const int f = own ? a.flags[u] : 0;
+    const bool ranked = own && (f & UF_ACTIVE) && !(f & (UF_ONLY_NDCG | UF_NAN | UF_SKIP)) && a.user_nslots[u] == 1;
+    const int tr0 = ranked ? a.train_p[u] : 0, ntr = ranked ? a.train_p[u + 1] - tr0 : 0;
+    const bool wanted = ranked && a.n - ntr >= K;
+    const int base = K <= WAVE ? ul * K : 0;                      // the user's ids in `ids`
+    for (int r = 0; r < rounds; r++) {
+        const int j = r * WAVE + j0;
+        if (wanted && j < K) ids[wv][base + j] = a.lists[(size_t)u * K + j].idx;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    T mn = (T)__int_as_float(0x7f800000); int bad = own && !wanted;
+    for (int r = 0; r < rounds; r++) {
+        const int j = r * WAVE + j0;
+        const bool has = wanted && j < K;
+        const int id = has ? ids[wv][base + j] : 0;
+        bool ok = has && id >= 0 && id < a.n;
+        for (int t = 0; t < K; t++) if (ok && t != j && ids[wv][base + t] == id) ok = false;
+        if (ok && ntr && in_sorted_row(a.train_i + tr0, ntr, id)) ok = false;
+        if (has && !ok) bad = 1;
+        const unsigned long long live = __ballot(ok);
+        if (!live) continue;
+        const T s = FlatDot<T>::run(a.A, a.lda, a.B, a.ldb, a.k, u, ok ? id : 0, ok, live, rows[wv], lane);
+        if (ok) { if (s != s || isinf(s)) bad = 1; else mn = s < mn ? s : mn; }
+    }
+    low[wv][lane] = mn; refused[wv][lane] = bad;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    bool bound = false, raised = false;
+    if (wanted && j0 == 0) {                                      // the user's first lane: over the lanes that hold its places
+        const int span = K <= WAVE ? K : WAVE;
+        for (int t = 1; t < span; t++) { const T x = low[wv][lane + t]; mn = x < mn ? x : mn; bad |= refused[wv][lane + t]; }
+        bound = !bad;
+        if (bound) { const KeyT key = (KeyT)ord_key(mn); raised = atomicMax(a.thr_shared + a.slot_index[a.uslot_base[u]], key) < key; }
+    }
+    const int n_bound = __popcll(__ballot(bound)), n_raised = __popcll(__ballot(raised));
+    if (lane == 0 && n_bound) { atomicAdd(&tally[0], n_bound); atomicAdd(&tally[1], n_raised); }
+    __syncthreads();
+    if (threadIdx.x < 2 && tally[threadIdx.x]) atomicAdd(a.counts + threadIdx.x, tally[threadIdx.x]);
 }
 
 // One wavefront per SLOT (= up to 63 test entries of one user, by row position): rank of each of them among ALL the
