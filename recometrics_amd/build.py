@@ -1,10 +1,11 @@
 """Builds recometrics_amd/csrc/librecometrics_hip.so for gfx950 (in-tree; hipcc cross-compiles without a GPU).
 
-The library is several translation units compiled in parallel: the host side with the preparation and finalisation kernels
-(rm_lib.hip), and the sweep kernels.  Every instantiation of the two sweep kernels lives in ONE source, csrc/rm_sweep_units.hip,
-compiled once per unit of SWEEP_UNITS with the unit's family and specialisation as -D defines (the file's header lists the
-families), and once without them: the table that walks the units' rows.  A unit is spelled "source" or "source:unit" in SOURCES
-and in the stamp's `translation_units`; its object is csrc/<source stem>[.<unit>].o."""
+The library is several translation units compiled in parallel: the host side (rm_lib.hip), the sweep kernels and the other
+kernels.  Every instantiation of the two sweep kernels lives in ONE source, csrc/rm_sweep_units.hip, compiled once per unit of
+SWEEP_UNITS with the unit's family and specialisation as -D defines (the file's header lists the families), and once without
+them: the table that walks the units' rows.  The kernels before and behind the sweep are instantiated by csrc/rm_kernel_units.hip
+in the same way, once per unit of KERNEL_UNITS.  A unit is spelled "source" or
+"source:unit" in SOURCES and in the stamp's `translation_units`; its object is csrc/<source stem>[.<unit>].o."""
 import concurrent.futures
 import glob
 import os
@@ -18,7 +19,19 @@ SWEEP_SRC = "rm_sweep_units.hip"
 SWEEP_UNITS = {"sweep32_dump": (4, 0), "sweep32_large": (3, 0)}
 SWEEP_UNITS.update({"sweep64_%s_s%d" % (name, spec): (fam, spec) for name, fam in (("small", 5), ("large", 6)) for spec in range(2)})
 SWEEP_UNITS.update({"sweep32_%s_s%d" % (name, spec): (fam, spec) for name, fam in (("n3", 0), ("lds", 1), ("hbm", 2)) for spec in range(3)})
-SOURCES = ["rm_lib.hip"] + [SWEEP_SRC + ":" + u for u in SWEEP_UNITS] + [SWEEP_SRC, "rm_split.cpp", "rm_csr.cpp"]
+KERNEL_SRC = "rm_kernel_units.hip"
+# unit -> (its -D defines, the kernel headers it includes: what an incremental build recompiles it for); the slowest first
+KERNEL_UNITS = {"collect4096_f32": (["-DRM_KERNELS=4", "-DRM_F64=0"], ("rm_finalize.hpp",)),
+                "collect4096_f64": (["-DRM_KERNELS=4", "-DRM_F64=1"], ("rm_finalize.hpp",)),
+                "collect_f32": (["-DRM_KERNELS=3", "-DRM_F64=0"], ("rm_finalize.hpp",)),
+                "collect_f64": (["-DRM_KERNELS=3", "-DRM_F64=1"], ("rm_finalize.hpp",)),
+                "prep": (["-DRM_KERNELS=0"], ("rm_prep.hpp",)),
+                "finalize": (["-DRM_KERNELS=1"], ("rm_finalize.hpp",)),
+                "rows": (["-DRM_KERNELS=2"], ("rm_noise.hpp", "rm_scores.hpp", "rm_rowtopk.hpp", "rm_prep.hpp", "rm_finalize.hpp"))}
+KERNEL_HEADERS = sorted({h for _, hdrs in KERNEL_UNITS.values() for h in hdrs} | {"rm_kernel_units.hpp"})
+# (the pool starts the units in this order: the longest compiles first)
+SOURCES = ([KERNEL_SRC + ":" + u for u in KERNEL_UNITS] + ["rm_lib.hip"] + [SWEEP_SRC + ":" + u for u in SWEEP_UNITS]
+           + [SWEEP_SRC, "rm_split.cpp", "rm_csr.cpp"])
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-inline-asm"]   # m0 is clobbered by the LDS-DMA asm on purpose
 
 
@@ -45,7 +58,7 @@ def sources_digest():
     for p in sorted(_deps()):
         h.update(os.path.basename(p).encode() + b"\0")
         h.update(open(p, "rb").read())
-    h.update(repr((SOURCES, SWEEP_UNITS, FLAGS, SWEEP_FLAGS)).encode())
+    h.update(repr((SOURCES, SWEEP_UNITS, KERNEL_UNITS, FLAGS, SWEEP_FLAGS)).encode())
     return h.hexdigest()
 
 
@@ -85,17 +98,21 @@ def _headers():
 def _compile(tu, extra, incremental=False):
     src, _, unit = tu.partition(":")
     obj = os.path.join(CSRC, os.path.splitext(src)[0] + ("." + unit if unit else "") + ".o")
-    if unit:
+    if src == SWEEP_SRC and unit:
         extra = list(extra) + ["-DRM_FAMILY=%d" % SWEEP_UNITS[unit][0], "-DRM_SPEC=%d" % SWEEP_UNITS[unit][1]]
+    if src == KERNEL_SRC:
+        extra = list(extra) + KERNEL_UNITS[unit][0]
     # (development only, `build(incremental=True)`: an object newer than its source and every header is kept; the library's own
     # stamp stays content-based)
     if incremental and os.path.exists(obj):
         hdrs = _headers()
-        if src.startswith("rm_sweep"):       # the sweeps' units include neither the preparation nor the finalisation kernels
-            hdrs = [h for h in hdrs if os.path.basename(h) not in ("rm_finalize.hpp", "rm_prep.hpp", "rm_noise.hpp")]
+        if src == SWEEP_SRC:                 # the sweeps' units include none of the other kernels' headers, a kernel unit its group's
+            hdrs = [h for h in hdrs if os.path.basename(h) not in KERNEL_HEADERS]
+        elif src == KERNEL_SRC:
+            hdrs = [h for h in hdrs if os.path.basename(h) in ("rm_device.hpp", "rm_kernel_units.hpp") + KERNEL_UNITS[unit][1]]
         if os.path.getmtime(obj) > max(os.path.getmtime(p) for p in [os.path.join(CSRC, src)] + hdrs):
             return obj, ""
-    if src.startswith("rm_sweep"):
+    if src == SWEEP_SRC:
         extra = list(extra) + SWEEP_FLAGS
     if src.endswith(".cpp"):        # host-only translation unit
         cmd = [shutil.which("g++") or "g++", "-O2", "-std=c++17", "-fPIC", "-pthread", "-c", os.path.join(CSRC, src), "-o", obj]
@@ -114,12 +131,14 @@ def build(force=False, verbose=False, extra_flags=(), out=None, incremental=Fals
     import time
     t_start = time.time()
     digest_at_start = sources_digest()        # (what the objects are compiled FROM: an edit during the build must not be stamped as built)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as ex:
+    jobs = int(os.environ.get("MAX_JOBS") or 0) or os.cpu_count() or 4        # (MAX_JOBS: what the machine allows, where that is less than it shows)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(SOURCES), jobs)) as ex:
         results = list(ex.map(lambda s: _compile(s, extra_flags, incremental), SOURCES))
     if verbose:
         for _, err in results:
             print(err)
-    res = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-shared", "-o", out] + [o for o, _ in results],
+    # (--no-undefined: a kernel that rm_lib.hip launches and no kernel unit instantiates fails here, not at the first call)
+    res = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-shared", "-Wl,--no-undefined", "-o", out] + [o for o, _ in results],
                          capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("link failed:\n" + res.stdout + res.stderr)

@@ -6,6 +6,7 @@
 // the CPU path uses.  ROC-AUC is formed in fp64 where the reference uses x87 long double (<= 1 ulp(fp64) apart).
 #pragma once
 #include "rm_device.hpp"
+#include "rm_kernel_units.hpp"
 #include <type_traits>
 
 namespace rm {
@@ -1348,5 +1349,19 @@ __global__ __launch_bounds__(RECO_THREADS) void k_finalize_reco(RecoArgs<S> a)
         __syncthreads();
     }
 }
+
+// ---- every instantiation of this header's kernel templates (rm_kernel_units.hpp); ThrT as Sweep*Args::thr_shared --------
+// (k_collect_topk has lists of its own: its instantiations take nine tenths of this header's compile time, CAPW 4096 alone three quarters)
+#define RM_FINALIZE_KERNELS(X, T) \
+    X(k_auc_slots<T, T>) X(k_merge_positives<T, T>) X(k_rank_streamed<T, T>) X(k_select_topk<T, T>) X(k_auc_streamed<T, T>) \
+    X(k_top_values<T, T>) X(k_finalize_skipped<T, T>) X(k_finalize_auc<T, T>) X(k_finalize<T, T>) X(k_finalize_reco<T>)
+#define RM_FINALIZE_KERNELS_F32(X) RM_FINALIZE_KERNELS(X, float)
+#define RM_FINALIZE_KERNELS_F64(X) RM_FINALIZE_KERNELS(X, double)
+#define RM_COLLECT_KERNELS_F32(X) X(k_collect_topk<float, float, unsigned, 512>) X(k_collect_topk<float, float, unsigned, 1024>)
+#define RM_COLLECT_KERNELS_F64(X) X(k_collect_topk<double, double, unsigned long long, 512>) X(k_collect_topk<double, double, unsigned long long, 1024>)
+#define RM_COLLECT4096_KERNELS_F32(X) X(k_collect_topk<float, float, unsigned, 4096>)
+#define RM_COLLECT4096_KERNELS_F64(X) X(k_collect_topk<double, double, unsigned long long, 4096>)
+RM_FINALIZE_KERNELS_F32(RM_EXTERN_KERNEL) RM_COLLECT_KERNELS_F32(RM_EXTERN_KERNEL) RM_COLLECT4096_KERNELS_F32(RM_EXTERN_KERNEL)
+RM_FINALIZE_KERNELS_F64(RM_EXTERN_KERNEL) RM_COLLECT_KERNELS_F64(RM_EXTERN_KERNEL) RM_COLLECT4096_KERNELS_F64(RM_EXTERN_KERNEL)
 
 } // namespace rm

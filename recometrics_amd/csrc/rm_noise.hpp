@@ -13,6 +13,7 @@
 // train items, which draw nothing) that the sweep and the positives kernel add to their scores.
 #pragma once
 #include "rm_device.hpp"
+#include "rm_kernel_units.hpp"
 
 namespace rm {
 
@@ -35,6 +36,7 @@ __device__ __forceinline__ unsigned mt_temper(unsigned y)
 // draws[row][0 .. need) of the users row_user[row]: need = (candidates of the user) * per_item draws, rounded up to blocks
 __global__ __launch_bounds__(MT_WAVES * WAVE) void k_mt_draws(const int *row_user, int n_rows, unsigned long long seed, long long user0,
                                                                 const int *train_p, int n, int per_item, unsigned *draws, long long ld)
+#ifdef RM_NOISE_PLAIN_KERNELS
 {
     __shared__ unsigned state[MT_WAVES][MT_N];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -71,6 +73,9 @@ __global__ __launch_bounds__(MT_WAVES * WAVE) void k_mt_draws(const int *row_use
         for (int i = lane; i < MT_N; i += WAVE) if (b0 + i < need) out[b0 + i] = mt_temper(x[i]);
     }
 }
+#else
+;
+#endif
 
 template <class T> __device__ __forceinline__ T noise_from_draws(const unsigned *d, long long c);
 // NO fused multiply-add here: the reference rounds r * (b - a) before it adds a, and HIP's __fmul_rn / __fadd_rn are plain
@@ -186,6 +191,7 @@ __global__ __launch_bounds__(NOISE_ROWS_THREADS) void k_noise_rows_bits(const in
 // tier 1 of the fp32 path: the users flagged in the first pass get rows (order irrelevant)
 // (`skip`, optional: users that have been evaluated exactly already -- the exact pass beside the first sweep)
 __global__ void k_noise_assign_rows(int m, const int *flag, const int *skip, int *noise_row, int *row_user, int *counter)
+#ifdef RM_NOISE_PLAIN_KERNELS
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= m) return;
@@ -193,6 +199,9 @@ __global__ void k_noise_assign_rows(int m, const int *flag, const int *skip, int
     if (flag[u] && !(skip && skip[u])) { r = atomicAdd(counter, 1); row_user[r] = u; }
     noise_row[u] = r;
 }
+#else
+;
+#endif
 // results of the exact pass that ran beside the first sweep (into buffers of its own) -> the caller's outputs, for its users
 template <class T> struct ScatterArgs { const T *src[10]; T *dst[10]; int width[10]; };
 template <class T>
@@ -224,9 +233,20 @@ __global__ void k_noise_gather(int count, const int *row_user, GatherArgs<T> a, 
     }
 }
 __global__ void k_noise_select(int m, const int *noise_row, int r0, int r1, unsigned char *only)
+#ifdef RM_NOISE_PLAIN_KERNELS
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u < m) only[u] = noise_row[u] >= r0 && noise_row[u] < r1;
 }
+#else
+;
+#endif
+
+// ---- every instantiation of this header's kernel templates (rm_kernel_units.hpp) ----------------------------------------
+#define RM_NOISE_KERNELS(X, T) X(k_noise_rows<T>) X(k_noise_rows_bits<T>) X(k_noise_gather<T>)
+#define RM_NOISE_KERNELS_F32(X) RM_NOISE_KERNELS(X, float) X(k_noise_scatter<float>)      // (the fp32 tie-noise call alone launches it)
+#define RM_NOISE_KERNELS_F64(X) RM_NOISE_KERNELS(X, double)
+RM_NOISE_KERNELS_F32(RM_EXTERN_KERNEL)
+RM_NOISE_KERNELS_F64(RM_EXTERN_KERNEL)
 
 } // namespace rm

@@ -5,6 +5,7 @@
 // sweep's epilogue.
 #pragma once
 #include "rm_device.hpp"
+#include "rm_kernel_units.hpp"
 
 namespace rm {
 
@@ -41,12 +42,16 @@ __device__ __forceinline__ int chunk_depth(int pc)      // smallest j with 2^j -
 // would index by what these arrays hold (k_assign_slots, k_block_tables, k_train_bits) returns when INDPTR / INDEX is set.
 // (the index pointers alone, for check_csr_now: the validation in front of the fp64 tie noise, which indexes by the rows before the plan runs)
 __global__ void k_check_csr_ptr(int m, const int *train_p, long long nnz_train, const int *test_p, long long nnz_test, Plan *plan)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= m) return;
     const int a0 = train_p[u], a1 = train_p[u + 1], b0 = test_p[u], b1 = test_p[u + 1];
     if (a0 < 0 || a1 < a0 || (long long)a1 > nnz_train || b0 < 0 || b1 < b0 || (long long)b1 > nnz_test) { atomicOr(&plan->csr_bad, CSR_BAD_INDPTR); plan->csr_where = u; }
 }
+#else
+;
+#endif
 // The indices themselves, FLAT: one thread per four entries of the index array (16-byte loads, fully coalesced: the 80 MB of
 // BASELINE C2 in ~25 us; a walk row by row -- 16 lanes per row, two dependent loads per step -- took 177 us).  Range: every
 // entry in [0, n).  Order: every DESCENT idx[e] > idx[e + 1] of the flat array is counted; a descent is legitimate exactly when
@@ -54,6 +59,7 @@ __global__ void k_check_csr_ptr(int m, const int *train_p, long long nnz_train, 
 // (the host compares them in the plan read-back).  Entries [p[0], p[m]) of this call's rows only.
 constexpr int CHECK_FLAT_THREADS = 256, CHECK_FLAT_BLOCKS = 1024;      // (a grid of at most that many blocks: one atomic per block at the end)
 __global__ __launch_bounds__(CHECK_FLAT_THREADS) void k_check_csr_flat(int m, int n, const int *indptr, const int *idx, Plan *plan, int which)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     if (plan->csr_bad & CSR_BAD_INDPTR) return;
     const long long e0 = indptr[0], e1 = indptr[m];
@@ -92,8 +98,12 @@ __global__ __launch_bounds__(CHECK_FLAT_THREADS) void k_check_csr_flat(int m, in
     __syncthreads();
     if (threadIdx.x == 0 && blk) atomicAdd(&plan->csr_desc_all[which], (unsigned long long)blk);
 }
+#else
+;
+#endif
 // the legitimate descents: one thread per row boundary (the smallest u with p[u] = s names each distinct start s once)
 __global__ __launch_bounds__(1024) void k_check_csr_starts(int m, const int *train_p, const int *train_i, const int *test_p, const int *test_i, Plan *plan)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     if (plan->csr_bad & CSR_BAD_INDPTR) return;
     __shared__ unsigned blk[2];
@@ -117,11 +127,15 @@ __global__ __launch_bounds__(1024) void k_check_csr_starts(int m, const int *tra
     __syncthreads();
     if (threadIdx.x < 2 && blk[threadIdx.x]) atomicAdd(&plan->csr_desc_legit[threadIdx.x], (unsigned long long)blk[threadIdx.x]);
 }
+#else
+;
+#endif
 
 // reference recometrics.hpp:439-448, :479-486  (one thread per user)
 // Also, in the same pass over the index pointers: their validation (check_ptr), the number of users with more than POS_CHUNK test
 // items and the longest such row (plan->n_long, max_npos: eligibility is not looked at, as an upper bound of the streamed class).
 __global__ void k_classify(ClassifyArgs a)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     const bool skip = u < a.m && a.only && !a.only[u];
@@ -194,10 +208,14 @@ __global__ void k_classify(ClassifyArgs a)
     if (threadIdx.x == N_CLASSES && blk_count[N_CLASSES]) atomicAdd(&a.plan->n_active, blk_count[N_CLASSES]);
     if (threadIdx.x == N_CLASSES + 1 && blk_count[N_CLASSES + 1]) { atomicAdd(&a.plan->n_long, blk_count[N_CLASSES + 1]); atomicMax(&a.plan->max_npos, blk_count[N_CLASSES + 2]); }
 }
+#else
+;
+#endif
 
 // Long arrays are scanned in two launches: k_scan_tiles (every block scans its own 1024 entries and reports its total) and
 // k_scan_exclusive over the block totals; the consumer (k_assign_slots) adds its tile's offset itself.
 __global__ __launch_bounds__(1024) void k_scan_tiles(const int *in, int *out, int count, int *tile_total)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     __shared__ int wsum[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -213,6 +231,9 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(const int *in, int *out, in
     if (i < count) out[i] = woff + x - v;
     if (tid == 1023) tile_total[blockIdx.x] = woff + x;
 }
+#else
+;
+#endif
 // exclusive scan of int array by ONE block of 1024 threads (m <= 2^31; a few hundred iterations at m = 1M)
 __device__ inline void plan_classes(Plan *p, int gu, int n_slots)      // one thread; gu = users per group (32 fp32, 16 fp64)
 {
@@ -230,6 +251,7 @@ __device__ inline void plan_classes(Plan *p, int gu, int n_slots)      // one th
 
 // (`classes`, optional: the thread that holds the total also lays out the depth classes -- what used to be a launch of one thread)
 __global__ void k_scan_exclusive(const int *in, int *out, int count, int *total_out, Plan *classes, int gu)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     __shared__ int wsum[16];
     __shared__ int carry_s;
@@ -255,6 +277,9 @@ __global__ void k_scan_exclusive(const int *in, int *out, int count, int *total_
     if (tid == 0 && total_out) *total_out = carry_s;
     if (tid == 0 && classes) plan_classes(classes, gu, carry_s);
 }
+#else
+;
+#endif
 
 struct AssignArgs {
     int m;
@@ -273,6 +298,7 @@ struct AssignArgs {
 // returning atomic per wave and class serialised the whole kernel behind that line.
 constexpr int ASSIGN_THREADS = 1024;
 __global__ __launch_bounds__(ASSIGN_THREADS) void k_assign_slots(AssignArgs a)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     __shared__ int blk_count[N_CLASSES], blk_base[N_CLASSES], blk_chunks, blk_chunk_base;
     if (a.plan->csr_bad & CSR_BAD_INDPTR) return;                 // (row lengths that cannot be trusted would index out of the slot arrays)
@@ -333,11 +359,15 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void k_assign_slots(AssignArgs a)
         a.slot_index[ubase + c] = pos;
     }
 }
+#else
+;
+#endif
 
 // per sweep block (4 groups): uniform tree depth jb = depth of its last slot (slots are sorted by depth); the block's positive
 // tables take 2^jb - 1 rows per group.  ONE block of 1024 threads walks the sweep blocks 1024 at a time: depth and rows of each,
 // their running sum, and from it gj / grow of the block's groups (what used to be k_block_rows -> a scan -> k_group_rows).
 __global__ __launch_bounds__(1024) void k_block_tables(Plan *p, const unsigned char *slot_j, int *gj, long long *grow, int gu)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     __shared__ int wsum[16];
     __shared__ long long carry_s;
@@ -384,6 +414,9 @@ __global__ __launch_bounds__(1024) void k_block_tables(Plan *p, const unsigned c
     }
     if (tid == 0) p->total_rows = carry_s;
 }
+#else
+;
+#endif
 
 // max |x| over a row-major matrix (rows x k, leading dimension ld) + a non-finite flag: lets the host prove that no
 // score can overflow, in which case the sweep skips its NaN scan.
@@ -446,6 +479,7 @@ __global__ void k_absmax(const T *X, size_t ld, long long rows, int k, unsigned 
 constexpr int SPLIT_ARRAYS = 5, SPLIT_SAME_THREADS = 256, SPLIT_SAME_BLOCKS = 2048;
 struct SplitSameArgs { const unsigned *theirs[SPLIT_ARRAYS], *ours[SPLIT_ARRAYS]; long long words[SPLIT_ARRAYS]; Plan *plan; };
 __global__ __launch_bounds__(SPLIT_SAME_THREADS) void k_split_same(SplitSameArgs a)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     unsigned diff = 0;
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
@@ -470,6 +504,9 @@ __global__ __launch_bounds__(SPLIT_SAME_THREADS) void k_split_same(SplitSameArgs
     }
     if (__syncthreads_or(diff != 0) && threadIdx.x == 0) a.plan->split_differs = 1;
 }
+#else
+;
+#endif
 
 // A head start for the streaming top-K: the user's test items are candidates themselves, so the K-th best of THEIR scores (known
 // before the sweep: k_pos_scores) is a valid lower bound of the K-th best score overall.  It seeds thr_shared, the bound every
@@ -593,6 +630,7 @@ __global__ __launch_bounds__(TRAIN_BITS_WAVES * WAVE) void k_train_bits(int m, i
                                                                         const int *test_p, const int *test_i, unsigned *bits,
                                                                         const Plan *plan, const unsigned char *only,
                                                                         unsigned char *ent_masked, int mark_test)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     extern __shared__ unsigned tb_lds[];                      // [TRAIN_BITS_WAVES][words]
     if (plan && (plan->csr_bad & (CSR_BAD_INDPTR | CSR_BAD_INDEX))) return;
@@ -674,6 +712,9 @@ __global__ __launch_bounds__(TRAIN_BITS_WAVES * WAVE) void k_train_bits(int m, i
         if (!step(r2, r0, r1)) break;
     }
 }
+#else
+;
+#endif
 // (`test_p` with `mark_test` = 0: the test rows are read for `ent_masked` only)
 inline void launch_train_bits(hipStream_t stream, int m, int n, int words, const int *train_p, const int *train_i, const int *test_p, const int *test_i,
                               unsigned *bits, const Plan *plan, const unsigned char *only, unsigned char *ent_masked = nullptr, bool mark_test = true)
@@ -971,6 +1012,7 @@ __global__ __launch_bounds__(POSS_WAVES * WAVE) void k_pos_scores(PosArgs<T> a, 
 // (the lanes of one user ask for the same addresses: one request per distinct user of the 64 entries).
 // Same arithmetic: k-ordered fma chain from +0.  Users that are not evaluated (or need no ranks) are skipped per lane.
 __global__ __launch_bounds__(256) void k_entry_users(int m, const int *test_p, int *ent_user, const Plan *plan)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     if (plan->csr_bad & CSR_BAD_INDPTR) return;
     const int lane = threadIdx.x & 63;
@@ -984,6 +1026,9 @@ __global__ __launch_bounds__(256) void k_entry_users(int m, const int *test_p, i
         for (int x = sj + lane; x < ej; x += WAVE) ent_user[x] = ub + j;
     }
 }
+#else
+;
+#endif
 // k_test_masked: a block owns TM_USERS consecutive users.  Their train rows are CONSECUTIVE rows of the CSR, i.e. one contiguous
 // piece of the index array: it is staged in LDS with coalesced loads and the binary searches run there (a search in memory is seven
 // or eight DEPENDENT loads per entry at BASELINE C2: the kernel was 0.23 ms of latency).  The users are taken in runs whose rows fit
@@ -993,6 +1038,7 @@ __global__ __launch_bounds__(256) void k_entry_users(int m, const int *test_p, i
 constexpr int TM_CAP = 9984, TM_USERS = 64;
 __global__ __launch_bounds__(256) void k_test_masked(int m, const int *test_p, const int *test_i, const int *train_p, const int *train_i,
                                                      const int *ent_user, unsigned char *ent_masked, const Plan *plan)
+#ifdef RM_PREP_PLAIN_KERNELS
 {
     __shared__ int seg[TM_CAP];
     __shared__ int tp[TM_USERS + 1], trp[TM_USERS + 1];
@@ -1052,6 +1098,9 @@ __global__ __launch_bounds__(256) void k_test_masked(int m, const int *test_p, c
         a = b;
     }
 }
+#else
+;
+#endif
 
 // The scores of a wavefront's 64 (user, item) pairs, one pair per lane: k_pos_scores_flat's test entries and k_hint_bounds' advised
 // items go through this one routine, so both are the sweep's scores to the bit.  `live`: the ballot of `mine`, not zero; a lane that
@@ -1342,5 +1391,16 @@ __global__ __launch_bounds__(PLACE_THREADS) void k_pos_place(PosArgs<T> a, const
         a.pos_item[at] = item;
     }
 }
+
+// ---- every instantiation of this header's kernel templates (rm_kernel_units.hpp); ThrT as Sweep*Args::thr_shared --------
+#define RM_PREP_KERNELS(X, T, ThrT) \
+    X(k_absmax<T>) X(k_seed_thresholds<T, ThrT>) X(k_init_tables<T>) \
+    X(k_seed_from_sample<T, ThrT, 1>) X(k_seed_from_sample<T, ThrT, 4>) X(k_seed_from_sample<T, ThrT, 16>) \
+    X(k_seed_from_sample<T, ThrT, 32>) X(k_seed_from_sample<T, ThrT, 64>) \
+    X(k_pos_scores<T>) X(k_pos_scores_flat<T>) X(k_pos_apply_masked<T>) X(k_hint_bounds<T, ThrT>) X(k_pos_place<T>)
+#define RM_PREP_KERNELS_F32(X) RM_PREP_KERNELS(X, float, unsigned) X(k_pack_items<float>) X(k_pack_items_tile<float>) X(k_pack_users<float>)
+#define RM_PREP_KERNELS_F64(X) RM_PREP_KERNELS(X, double, unsigned long long) X(k_pack_items64<double>) X(k_pack_users64<double>)
+RM_PREP_KERNELS_F32(RM_EXTERN_KERNEL)
+RM_PREP_KERNELS_F64(RM_EXTERN_KERNEL)
 
 } // namespace rm

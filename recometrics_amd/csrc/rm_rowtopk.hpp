@@ -18,6 +18,7 @@
 #pragma once
 #include "rm_scores.hpp"
 #include "rm_finalize.hpp"
+#include "rm_kernel_units.hpp"
 
 namespace rm {
 
@@ -155,5 +156,11 @@ __global__ __launch_bounds__(SCORE_ROW_THREADS) void k_topk_rows(RowTopkArgs<T> 
     }
     if (tid == 0) a.status[u] = status;
 }
+
+// ---- every instantiation of this header's kernel template (rm_kernel_units.hpp) -----------------------------------------
+#define RM_ROWTOPK_KERNELS_F32(X) X(k_topk_rows<float>)
+#define RM_ROWTOPK_KERNELS_F64(X) X(k_topk_rows<double>)
+RM_ROWTOPK_KERNELS_F32(RM_EXTERN_KERNEL)
+RM_ROWTOPK_KERNELS_F64(RM_EXTERN_KERNEL)
 
 } // namespace rm

@@ -10,6 +10,7 @@
 // keys of k_select_topk / k_pos_place tell the two zeros apart.  Both kernels store +0 for -0 (the contract: +0 == -0, ties by item id).
 #pragma once
 #include "rm_device.hpp"
+#include "rm_kernel_units.hpp"
 #include "rm_prep.hpp"
 
 namespace rm {
@@ -194,5 +195,12 @@ __global__ __launch_bounds__(SCORE_ROW_THREADS) void k_score_rows(ScoreRowArgs<T
         a.pst[(size_t)slot * a.n_part] = ps;
     }
 }
+
+// ---- every instantiation of this header's kernel templates (rm_kernel_units.hpp) ----------------------------------------
+#define RM_SCORES_KERNELS(X, T) X(k_pos_scores_given<T>) X(k_score_rows<T>)
+#define RM_SCORES_KERNELS_F32(X) RM_SCORES_KERNELS(X, float)
+#define RM_SCORES_KERNELS_F64(X) RM_SCORES_KERNELS(X, double)
+RM_SCORES_KERNELS_F32(RM_EXTERN_KERNEL)
+RM_SCORES_KERNELS_F64(RM_EXTERN_KERNEL)
 
 } // namespace rm

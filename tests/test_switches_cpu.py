@@ -53,9 +53,10 @@ def test_the_environment_is_read_in_one_place_only():
 
 
 def test_python_side_reads_only_the_library_path_overrides():
-    """the Python package looks at the environment for two things: where the library is (RECOMETRICS_HIP_LIB) and, in the
-    sanitizer test, which build of the host-only units to load (RECOMETRICS_SPLIT_LIB)"""
+    """the Python package looks at the environment for three things: where the library is (RECOMETRICS_HIP_LIB), in the
+    sanitizer test which build of the host-only units to load (RECOMETRICS_SPLIT_LIB), and how many compilers the build may run
+    at once (MAX_JOBS, build.py: no result depends on it)"""
     names = set()
     for path in glob.glob(os.path.join(ROOT, "recometrics_amd", "*.py")):
         names |= set(re.findall(r'environ(?:\.get)?\(?\[?\s*"([^"]+)"', open(path).read()))
-    assert names <= {"RECOMETRICS_HIP_LIB", "RECOMETRICS_SPLIT_LIB"}, names
+    assert names <= {"RECOMETRICS_HIP_LIB", "RECOMETRICS_SPLIT_LIB", "MAX_JOBS"}, names
