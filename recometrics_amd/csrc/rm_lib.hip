@@ -110,62 +110,165 @@ RunTrace g_run_trace;
 // Every ALLOCATION of a buffer carries a stamp from a process-wide counter: what is remembered about a buffer's contents (PackedItems,
 // DenseRows, DiscountTable) is void once the buffer is allocated anew -- grown, or released and asked for again -- at whatever address.
 std::atomic<unsigned long long> g_ws_stamp{1};
+// EVERY buffer of a workspace: X(id, the name error messages print) -- what it holds, its shape, who writes it.  (T: the call's
+// precision; GU: users per group; DESIGN.md section 1 "Data layout in HBM" describes the large ones.)
+#define RM_WS_BUFFERS(X) \
+    /* ---- the plan stage (Pipeline::plan_stage); a kept split (SplitCache) vouches for most of these ---- */ \
+    X(WS_FLAGS, "flags")                        /* int[m]: the users' flags (k_classify) */ \
+    X(WS_USER_NSLOTS, "user_nslots")            /* int[m]: sweep slots of each user (k_classify) */ \
+    X(WS_USLOT_BASE, "uslot_base")              /* int[m]: exclusive scan of user_nslots, a user's place in slot_index (k_scan_exclusive) */ \
+    X(WS_PLAN, "plan")                          /* Plan: the device Plan -- counts, class offsets, the CSR checks' verdicts, the maxima (zeroed by the plan stage; its kernels) */ \
+    X(WS_HEAVY_USERS, "heavy_users")            /* int[m]: the users with more than `heavy_npos` test items, listed (k_classify) */ \
+    X(WS_SLOT_USER, "slot_user")                /* int[m + nnz_test / POS_CHUNK + 1]: the user of each slot (k_assign_slots; debug_scores: k_iota) */ \
+    X(WS_SLOT_CHUNK, "slot_chunk")              /* int[same]: the chunk of its user's test row each slot takes (k_assign_slots) */ \
+    X(WS_SLOT_INDEX, "slot_index")              /* int[same]: at uslot_base[u] + c, the slot of user u's chunk c (k_assign_slots) */ \
+    X(WS_SLOT_J, "slot_j")                      /* unsigned char[same]: table depth j of each slot (k_assign_slots, for k_block_tables) */ \
+    X(WS_GJ, "gj")                              /* int[slots / GU + 2]: table depth of each group (k_block_tables) */ \
+    X(WS_GROW, "grow")                          /* long long[slots / GU + 2]: group g owns the table rows from grow[g] + g (k_block_tables; debug_scores: zeros) */ \
+    X(WS_SC_USER, "sc_user")                    /* int[slots]: the streamed users' chunk list, the user ... (k_assign_slots) */ \
+    X(WS_SC_CHUNK, "sc_chunk")                  /* int[slots]: ... and the chunk (k_assign_slots) */ \
+    X(WS_SCAN_TILE_TOTAL, "scan_tile_total")    /* int[ceil(m / 1024)]: m > 8,192: slots per tile of 1,024 users (k_scan_tiles) */ \
+    X(WS_SCAN_TILE_OFFSET, "scan_tile_offset")  /* int[ceil(m / 1024)]: their exclusive scan (k_scan_exclusive) */ \
+    X(WS_LOG2TAB, "log2tab")                    /* double[K]: log2(i + 2), the DCG discounts (uploaded by the plan stage; DiscountTable) */ \
+    X(WS_ENT_USER, "ent_user")                  /* int[nnz_test]: the user of every test entry (k_entry_users) */ \
+    X(WS_ENT_MASKED, "ent_masked")              /* unsigned char[nnz_test]: the entry's item is a train item (the dense train rows' kernel, or k_test_masked) */ \
+    X(WS_POS_TMP, "pos_tmp")                    /* T[nnz_test]: score of each test entry, +inf when masked by the train row (k_pos_scores_flat / _given / k_pos_scores) */ \
+    X(WS_POS_KEY, "pos_key")                    /* fp32: unsigned long long[nnz_test + 8]: the entry's packed key, score bits << 32 | ~item (the same kernels; PosArgs) */ \
+    X(WS_HINT_COUNTS, "hint_counts")            /* int[2]: users k_hint_bounds gave a bound, users whose bound raised the positives' (zeroed by plan_reused; k_hint_bounds) */ \
+    X(WS_TRAIN_BITS, "train_bits")              /* unsigned[m][dense_row_words(n)]: the dense train rows, a bit per item and user (launch_train_bits; DenseRows) */ \
+    X(WS_HEAVY_TOPV, "heavy_topv")              /* T[m][heavy_ld]: largest test values, descending, of the users in heavy_users (k_top_values) */ \
+    X(WS_HEAVY_NAN, "heavy_nan")                /* unsigned char[m]: ... and whether any of their values is NaN (k_top_values) */ \
+    /* the context's copies of the kept split's five arrays, in SPLIT_ARRAYS order: 32-bit words as SplitKey::words counts them (keep_split) */ \
+    X(WS_SPLIT_TRAIN_P, "split_train_p")        /* int[m + 1] */ \
+    X(WS_SPLIT_TRAIN_I, "split_train_i")        /* int[nnz_train] */ \
+    X(WS_SPLIT_TEST_P, "split_test_p")          /* int[m + 1] */ \
+    X(WS_SPLIT_TEST_I, "split_test_i")          /* int[nnz_test] */ \
+    X(WS_SPLIT_TEST_V, "split_test_v")          /* T[nnz_test], when the call has test values */ \
+    /* ---- preparation, sweep, finalisation (Pipeline::prep, positives, select_lists) ---- */ \
+    X(WS_MERGED, "merged")                      /* Entry<T>[m][K]: every user's final ordered top-K (the finalisation); the next pass's advice on a kept split (SplitCache::lists) */ \
+    X(WS_RANK_SORTED, "rank_sorted")            /* long long[nnz_test]: 1-based full-ranking position per sorted positive, 0 = masked (zeroed by prep; the finalisation's rank kernels) */ \
+    X(WS_AUC_PART, "auc_part")                  /* AucPart[n_slots]: a slot's sums for the two AUC values (k_auc_slots, the streamed users' rank kernels) */ \
+    X(WS_STREAM_SCORES, "stream_scores")        /* T[n_stream][stream_ld]: masked candidate scores of the streamed users (the sweep; k_score_rows) */ \
+    X(WS_PST, "pst")                            /* PartialStat<T>[n_slots][n_part]: the candidates' statistics in parts (the sweep; k_score_rows) */ \
+    X(WS_BP, "Bp")                              /* 16 B x items_units: the packed item image (pack_operands; PackedItems) */ \
+    X(WS_AP, "Ap")                              /* 16 B x users_units: the packed user image, per user group (pack_operands) */ \
+    X(WS_PL, "pl")                              /* Entry<T>[n_slots][n_part][K]: the top-K lists in parts (the sweep) */ \
+    X(WS_GLISTS, "glists")                      /* per sweep block and wave: [lane_cap][64 lanes] lane buffers of (sizeof(T) + 4)-byte entries, or ListT[GU][2K + 32] replace-the-minimum lists in HBM (the sweep) */ \
+    X(WS_LANE_CNT, "lane_cnt")                  /* int[block][wave][64]: entries each lane left in its buffer (the sweep) */ \
+    X(WS_THR_SHARED, "thr_shared")              /* ThrT[n_slots]: order-preserving key of the user's bound (k_seed_thresholds or zeroed; raised by k_seed_from_sample, k_hint_bounds, the sweep) */ \
+    X(WS_SAMPLE_SCORES, "sample_scores")        /* T[n_slots][S]: every slot's scores of the first S items (the sweep's DUMP variant, seed_from_sample) */ \
+    X(WS_SAMPLE_ITEMS, "sample_items")          /* 16 B x items_units: an image of the sample in 64-item tiles, for a sweep with three sub-tiles (pack_operands) */ \
+    X(WS_SAMPLE_LISTS, "sample_lists")          /* ListT[n_ublocks][8][GU][2 + 32]: the lists of that DUMP sweep, K = 1 (seed_from_sample hands them to it) */ \
+    X(WS_POS_SCORE, "pos_score")                /* T[total_rows + n_groups + 1][GU]: the positives' tables, 2^j rows per group, last row +inf (k_init_tables, k_pos_place) */ \
+    X(WS_POS_ITEM, "pos_item")                  /* int[same]: item id of each sorted positive (k_pos_place) */ \
+    X(WS_HIST, "hist")                          /* unsigned[same]: candidates ranking between two positives (k_init_tables; the sweep) */ \
+    X(WS_POS_ORDER, "pos_order")                /* int[nnz_test]: ascending rank of the entry inside its row (k_pos_place) */ \
+    X(WS_SPOS_SCORE, "spos_score")              /* T[nnz_test]: streamed users, at test_p[u] + rank: scores ascending (k_init_tables, k_pos_place) */ \
+    X(WS_SPOS_ITEM, "spos_item")                /* int[nnz_test]: ... their item ids (k_pos_place) */ \
+    X(WS_SHIST, "shist")                        /* unsigned[nnz_test]: ... candidates above positive j but not above j + 1 (k_init_tables; k_rank_streamed) */ \
+    X(WS_SEL_HI, "sel_hi")                      /* unsigned long long[n_slots][sel_ld]: k_select_topk's scratch, sel_ld = K rounded up to a power of two */ \
+    X(WS_SEL_LO, "sel_lo")                      /* unsigned[n_slots][sel_ld]: ... the same */ \
+    /* ---- the tie noise (ExactPass, run_call) ---- */ \
+    X(WS_NOISE_ROW, "noise_row")                /* int[m]: the noise row of each flagged user (k_noise_assign_rows) */ \
+    X(WS_NOISE_ROW_USER, "noise_row_user")      /* int[flagged users, or m]: the user of each row (k_noise_assign_rows) */ \
+    X(WS_NOISE_COUNTER, "noise_counter")        /* int: rows given out (zeroed by assign; k_noise_assign_rows) */ \
+    X(WS_NOISE_ONLY, "noise_only")              /* unsigned char[m]: the users of the rows of one step (k_noise_select) */ \
+    X(WS_O_EXACT, "o_exact")                    /* T[block_size(m)]: metric block of an exact pass, [metric][users x width] (that pass's finalisation) */ \
+    X(WS_NOISE_DRAWS, "noise_draws")            /* unsigned[rows][d_ld]: mt19937(seed + user) draws (k_mt_draws) */ \
+    X(WS_NOISE_ROWS, "noise_rows")              /* T[rows][e_ld]: the per-item noise rows (k_noise_rows / k_noise_rows_bits) */ \
+    X(WS_NOISE_FLAG, "noise_flag")              /* int[m]: users the first pass flags (zeroed by run_call; the positives' scores, k_finalize) */ \
+    X(WS_NOISE_FLAG_SNAP, "noise_flag_snap")    /* int[m]: the flags when that pass launches its sweep (Pipeline::sweep, a copy) */ \
+    /* ---- the host-pointer entry (HostRange): uploads, outputs on the device ---- */ \
+    X(WS_IN_B, "in_B")                          /* T[n][k]: the item factors, dense rows (HostRange's uploads; debug_scores) */ \
+    X(WS_IN_A, "in_A")                          /* T[m][k]: the range's user factors (HostRange's uploads; debug_scores) */ \
+    X(WS_IN_TRP, "in_trp")                      /* int[m + 1]: train index pointers, rebased to the range (stage_inputs) */ \
+    X(WS_IN_TEP, "in_tep")                      /* int[m + 1]: test index pointers, rebased (stage_inputs) */ \
+    X(WS_IN_TRI, "in_tri")                      /* int[nnz_train of the range] (HostRange's uploads) */ \
+    X(WS_IN_TEI, "in_tei")                      /* int[nnz_test of the range] (HostRange's uploads) */ \
+    X(WS_IN_TEV, "in_tev")                      /* T[nnz_test of the range] (HostRange's uploads) */ \
+    X(WS_O_TOPK_IDX, "o_topk_idx")              /* int[m][K]: the ranking outputs of rm_rank_* and of the lists, for copy_out (the batches' passes, through Call::topk_idx ...) */ \
+    X(WS_O_TOPK_SCORE, "o_topk_score")          /* T[m][K] */ \
+    X(WS_O_POS_RANK, "o_pos_rank")              /* long long[nnz_test of the range] */ \
+    X(WS_O_STATUS, "o_status")                  /* int[m] */ \
+    X(WS_O_BLOCK, "o_block")                    /* T[block_size(largest batch)]: the metric block of a batch, [metric][users x width] (the finalisation) */ \
+    X(WS_IN_S0, "in_S0")                        /* T[largest batch][n]: the caller's score rows of a batch ... (HostRange's uploads) */ \
+    X(WS_IN_S1, "in_S1")                        /* ... and of the next one, which travels meanwhile */ \
+    X(WS_NOISE_FLAG_RANGE, "noise_flag_range")  /* int[m]: fp32 tie noise over several batches: the flags of the range (zeroed by plan_batches; the batches' first passes) */ \
+    X(WS_NOISE_FLAG_RANGE_SNAP, "noise_flag_range_snap")  /* int[m]: ... when the LAST batch launches its sweep */ \
+    X(WS_O_EXACT_PACKED, "o_exact_packed")      /* T[count][rec_w]: an exact pass's results, a record per evaluated user (k_noise_gather) */ \
+    /* ---- the device-pointer entry (run_dev), debug_scores ---- */ \
+    X(WS_RECO_ZERO_P, "reco_zero_p")            /* int[m + 1]: zeros, the index pointers of lists without an exclusion matrix (run_dev) */ \
+    X(WS_SORTED_TRI, "sorted_tri")              /* int[nnz_train]: the caller's unsorted CSR rows, sorted by the host (run_dev) */ \
+    X(WS_SORTED_TEI, "sorted_tei")              /* int[nnz_test] */ \
+    X(WS_SORTED_TEV, "sorted_tev")              /* T[nnz_test] */ \
+    X(WS_DBG_ZEROS, "dbg_zeros")                /* int[m + 1 + n_groups]: zeros for slot_chunk, train_p, train_i and gj (debug_scores) */ \
+    X(WS_DBG_DUMP, "dbg_dump")                  /* T[m][n]: every score (the sweep's DUMP variant, debug_scores) */
+#define RM_WS_ID(id, name) id,
+#define RM_WS_NAME(id, name) name,
+enum WsBuf { RM_WS_BUFFERS(RM_WS_ID) WS_COUNT };
+constexpr const char *WS_NAMES[WS_COUNT] = { RM_WS_BUFFERS(RM_WS_NAME) };
+#undef RM_WS_ID
+#undef RM_WS_NAME
 struct Workspace {
     struct Buf { void *ptr = nullptr; size_t bytes = 0; unsigned long long stamp = 0; };
-    std::map<std::string, Buf> bufs;
-    void *get(const std::string &name, size_t bytes)
+    Buf bufs[WS_COUNT];
+    void *get(WsBuf id, size_t bytes)
     {
         bytes = std::max<size_t>(bytes, 256);
-        Buf &b = bufs[name];
+        Buf &b = bufs[id];
         if (b.bytes < bytes) {
             if (b.ptr) { (void)hipFree(b.ptr); g_ws_bytes -= (long long)b.bytes; b = Buf{}; }
             const size_t cap = bytes + bytes / 8;
             const long long sim = debug_free_cap();
             if (sim >= 0 && g_ws_bytes.load() + (long long)cap > sim)
-                throw RmError{RM_ERR_NOMEM, "hipMalloc(" + name + ", " + std::to_string(cap) + " B): beyond RM_DEBUG_FREE_MB"};
+                throw RmError{RM_ERR_NOMEM, std::string("hipMalloc(") + WS_NAMES[id] + ", " + std::to_string(cap) + " B): beyond RM_DEBUG_FREE_MB"};
             hipError_t e = hipMalloc(&b.ptr, cap);
-            if (e != hipSuccess) { b.ptr = nullptr; throw RmError{RM_ERR_NOMEM, "hipMalloc(" + name + ", " + std::to_string(cap) + " B): " + hipGetErrorString(e)}; }
+            if (e != hipSuccess) { b.ptr = nullptr; throw RmError{RM_ERR_NOMEM, std::string("hipMalloc(") + WS_NAMES[id] + ", " + std::to_string(cap) + " B): " + hipGetErrorString(e)}; }
             b.bytes = cap; b.stamp = g_ws_stamp.fetch_add(1);
             g_ws_bytes += (long long)cap;
         }
         return b.ptr;
     }
+    template <class T> T *array(WsBuf id, size_t count) { return (T *)get(id, sizeof(T) * count); }
     // the buffer as it stands (never asked for, or released: null and stamp 0, which no valid record carries)
-    Buf peek(const char *name) const { auto it = bufs.find(name); return it == bufs.end() ? Buf{} : it->second; }
-    void release()
-    {
-        for (auto &kv : bufs) if (kv.second.ptr) { (void)hipFree(kv.second.ptr); g_ws_bytes -= (long long)kv.second.bytes; }
-        bufs.clear();
-    }
+    const Buf &peek(WsBuf id) const { return bufs[id]; }
+    void release() { for (Buf &b : bufs) { if (b.ptr) { (void)hipFree(b.ptr); g_ws_bytes -= (long long)b.bytes; } b = Buf{}; } }      // (every slot: no stamp outlives its memory)
 };
 // What a workspace buffer was last filled with, for the callers that may find it filled already.  A record is valid only for the
-// allocation it was made in (Workspace::Buf::stamp); each question a caller asks is a member.
-struct PackedItems {                         // "Bp": the packed item image, shared by the passes / batches of one call (Call::items_tag)
-    unsigned long long stamp = 0, tag = 0; int tile = 0, ng = 0;
+// allocation it was made in (Workspace::Buf::stamp): `Filled<ID>` is that half of every record, bound to its buffer; each question a
+// caller asks is a member of the record.
+template <WsBuf ID> struct Filled {
+    unsigned long long stamp = 0;                                // of the allocation the record was made in; 0 = no record
+    bool current(const Workspace &ws) const { return stamp != 0 && stamp == ws.peek(ID).stamp; }
+    void bind(const Workspace &ws) { stamp = ws.peek(ID).stamp; }
+    void unbind() { stamp = 0; }
+    const void *ptr(const Workspace &ws) const { return ws.peek(ID).ptr; }
+};
+struct PackedItems : Filled<WS_BP> {         // the packed item image, shared by the passes / batches of one call (Call::items_tag)
+    unsigned long long tag = 0; int tile = 0, ng = 0;
     unsigned long long amax_b = 0; int nonfinite_b = 0;      // max |B| and its non-finite count as that call's plan found them
     bool of_call(unsigned long long t) const { return t != 0 && t == tag; }      // (the bound on |B| holds for the call; `holds`: so does the image, at this geometry)
-    bool holds(const Workspace &ws, unsigned long long t, int tile_items, int NG) const { return of_call(t) && stamp == ws.peek("Bp").stamp && tile == tile_items && ng == NG; }
-    void set(const Workspace &ws, unsigned long long t, int tile_items, int NG) { stamp = ws.peek("Bp").stamp; tag = t; tile = tile_items; ng = NG; }
-    void invalidate() { stamp = 0; tag = 0; }
+    bool holds(const Workspace &ws, unsigned long long t, int tile_items, int NG) const { return of_call(t) && current(ws) && tile == tile_items && ng == NG; }      // (a tag comes with a stamp: set)
+    void set(const Workspace &ws, unsigned long long t, int tile_items, int NG) { bind(ws); tag = t; tile = tile_items; ng = NG; }
+    void invalidate() { unbind(); tag = 0; }
 };
-struct DenseRows {                           // "train_bits": the dense train rows (set_train_bits)
-    unsigned long long stamp = 0; long long words = 0; int m = 0;
+struct DenseRows : Filled<WS_TRAIN_BITS> {   // the dense train rows (set_train_bits)
+    long long words = 0; int m = 0;
     bool masked = false, partial = false;                      // the test items marked too; a subset of the users only (Call::only_users)
     unsigned long long tag = 0; const int *train_p = nullptr;  // built by which call (Call::items_tag), over which rows
-    bool valid(const Workspace &ws) const { return stamp != 0 && stamp == ws.peek("train_bits").stamp; }
     // rows of this buffer for `m_` users, `words_` words, masked as asked, built for all users (a later pass of the same call)
-    bool fits(const Workspace &ws, int m_, long long words_, bool masked_) const { return valid(ws) && !partial && words == words_ && m == m_ && masked == masked_; }
+    bool fits(const Workspace &ws, int m_, long long words_, bool masked_) const { return current(ws) && !partial && words == words_ && m == m_ && masked == masked_; }
     // rows built by call `t` over `train_p_` for `m_` users, not partial (the tie noise's exact pass beside that call's sweep)
-    bool built_by(const Workspace &ws, unsigned long long t, const int *train_p_, int m_) const { return valid(ws) && t != 0 && t == tag && train_p == train_p_ && m == m_ && !partial; }
-    const unsigned *rows(const Workspace &ws) const { return (const unsigned *)ws.peek("train_bits").ptr; }
+    bool built_by(const Workspace &ws, unsigned long long t, const int *train_p_, int m_) const { return current(ws) && t != 0 && t == tag && train_p == train_p_ && m == m_ && !partial; }
+    const unsigned *rows(const Workspace &ws) const { return (const unsigned *)ptr(ws); }
     void set(const Workspace &ws, long long words_, int m_, bool masked_, bool partial_, unsigned long long t, const int *train_p_)
-    { stamp = ws.peek("train_bits").stamp; words = words_; m = m_; masked = masked_; partial = partial_; tag = t; train_p = train_p_; }
-    void invalidate() { stamp = 0; tag = 0; }
+    { bind(ws); words = words_; m = m_; masked = masked_; partial = partial_; tag = t; train_p = train_p_; }
+    void invalidate() { unbind(); tag = 0; }
 };
-struct DiscountTable {                       // "log2tab": log2(i + 2), the DCG discounts
-    unsigned long long stamp = 0; int K = 0;
-    bool holds(const Workspace &ws, int K_) const { return stamp != 0 && stamp == ws.peek("log2tab").stamp && K >= K_; }
-    void set(const Workspace &ws, int K_) { stamp = ws.peek("log2tab").stamp; K = K_; }
+struct DiscountTable : Filled<WS_LOG2TAB> {  // log2(i + 2), the DCG discounts
+    int K = 0;
+    bool holds(const Workspace &ws, int K_) const { return current(ws) && K >= K_; }
+    void set(const Workspace &ws, int K_) { bind(ws); K = K_; }
 };
 // What a context keeps of the train / test split of its last metric call, for the next call on the same split (one model after
 // another on one split: a hyper-parameter search, an evaluation per epoch): copies of the five arrays, in buffers of their own, and
@@ -183,20 +286,20 @@ struct SplitKey {
     unsigned long long switches;                                // Switches::epoch
 };
 struct SplitCache {
-    static constexpr const char *copy_names[SPLIT_ARRAYS] = {"split_train_p", "split_train_i", "split_test_p", "split_test_i", "split_test_v"};
+    static constexpr WsBuf copies[SPLIT_ARRAYS] = {WS_SPLIT_TRAIN_P, WS_SPLIT_TRAIN_I, WS_SPLIT_TEST_P, WS_SPLIT_TEST_I, WS_SPLIT_TEST_V};
     bool valid = false; SplitKey key{}; Plan hp{}; bool check_nan = false, dense_masked = false;
-    std::vector<std::pair<std::string, unsigned long long>> stamps;       // the buffers the record speaks of, as allocated then
-    // "merged" as allocated when the last plain pass on this split enqueued its k_finalize: the buffer then holds that pass's ordered
+    std::vector<std::pair<WsBuf, unsigned long long>> stamps;             // the buffers the record speaks of, as allocated then
+    // WS_MERGED as allocated when the last plain pass on this split enqueued its k_finalize: the buffer then holds that pass's ordered
     // top-K lists, the advice of the next pass (k_hint_bounds).  Taken (and so voided) when a pass starts, set again when it has
-    // enqueued everything: a pass that fails or is interrupted leaves none.  0 = no lists.
-    unsigned long long lists_stamp = 0;
+    // enqueued everything: a pass that fails or is interrupted leaves none.
+    Filled<WS_MERGED> lists;
     // Whether that advice is worth its kernel is the model's business, not the split's: a pass whose bounds mostly stayed BELOW what the
     // positives gave anyway (fewer than half of them raised a word: the model has little to do with the last one) makes the next
     // `hint_skip` passes run without the kernel -- 1, then 2, 4, ... up to HINT_BACKOFF_MAX for every further such pass, back to none
     // after a pass whose bounds did raise.  `hint_judge`: the last pass launched the kernel and its counts have not been looked at yet.
     static constexpr int HINT_BACKOFF_MAX = 16;
     int hint_skip = 0, hint_backoff = 0; bool hint_judge = false;
-    void invalidate() { valid = false; lists_stamp = 0; hint_skip = hint_backoff = 0; hint_judge = false; }
+    void invalidate() { valid = false; lists.unbind(); hint_skip = hint_backoff = 0; hint_judge = false; }
     // the counts of the last launch (accepted, raised), then: does this pass launch?
     bool hints_due(const int *counts)
     {
@@ -208,16 +311,16 @@ struct SplitCache {
         if (hint_skip > 0) { hint_skip--; return false; }
         return true;
     }
-    bool take_lists(const Workspace &ws) { const unsigned long long s = lists_stamp; lists_stamp = 0; return s != 0 && s == ws.peek("merged").stamp; }
-    void keep_lists(const Workspace &ws) { lists_stamp = ws.peek("merged").stamp; }
-    void keep(const Workspace &ws, const char *name) { stamps.emplace_back(name, ws.peek(name).stamp); }
+    bool take_lists(const Workspace &ws) { const bool kept = lists.current(ws); lists.unbind(); return kept; }
+    void keep_lists(const Workspace &ws) { lists.bind(ws); }
+    void keep(const Workspace &ws, WsBuf id) { stamps.emplace_back(id, ws.peek(id).stamp); }
     bool holds(const Workspace &ws, const SplitKey &k) const
     {
         if (!valid || std::memcmp(&key, &k, sizeof(SplitKey)) != 0) return false;
-        for (const auto &s : stamps) if (s.second == 0 || ws.peek(s.first.c_str()).stamp != s.second) return false;
+        for (const auto &s : stamps) if (s.second == 0 || ws.peek(s.first).stamp != s.second) return false;
         return true;
     }
-    const void *copy(const Workspace &ws, int i) const { return ws.peek(copy_names[i]).ptr; }
+    const void *copy(const Workspace &ws, int i) const { return ws.peek(copies[i]).ptr; }
 };
 // The roles of the events that order a context's two streams beside the call's against it: who records each and who waits is the
 // table in DESIGN.md section 1.  One event per role; `Beside` (below) is the only code that touches them.
@@ -275,7 +378,7 @@ struct Ctx {
     double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int timed_slots = 0, total_slots = 0;     // slots (user lanes) of the sweep launch the "sweep" timing brackets / of the call
     double acc[4] = {0, 0, 0, 0};            // prep / sweep / finalize / total ms of the batches already read back (host entry)
-    PackedItems packed; DenseRows dense; DiscountTable discounts;    // what "Bp", "train_bits" and "log2tab" of `ws` hold
+    PackedItems packed; DenseRows dense; DiscountTable discounts;    // what WS_BP, WS_TRAIN_BITS and WS_LOG2TAB of `ws` hold
     SplitCache split;                                                // ... and what the plan stage's buffers hold of the last call's split
     int split_reused = -1;               // the most recent pass: 1 = it ran on what `split` kept, 0 = it planned itself, -1 = a pass that never reuses
     // the warm bounds of the most recent pass that launched k_hint_bounds: page-locked, the users that got a bound and those whose bound
@@ -598,14 +701,14 @@ constexpr size_t SYNC_BYTES = 32;          // end of the sweep's LDS: arrival co
 // RM_STREAM_BUDGET_MB (tests)
 // (what the workspace already holds of exactly these buffers counts as free: a later batch of the same size must get the
 // same answer as the first one, whose rows are still cached -- otherwise its budget shrinks and an equal-sized batch fails)
-inline long long free_plus_owned(const Workspace &ws, std::initializer_list<const char *> names)
+inline long long free_plus_owned(const Workspace &ws, std::initializer_list<WsBuf> ids)
 {
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     const long long sim = debug_free_cap();
     if (sim >= 0) fr = (size_t)std::max<long long>(0, std::min<long long>((long long)fr, sim - g_ws_bytes.load()));
     long long owned = 0;
-    for (const char *nm : names) { auto it = ws.bufs.find(nm); if (it != ws.bufs.end()) owned += (long long)it->second.bytes; }
+    for (WsBuf id : ids) owned += (long long)ws.peek(id).bytes;
     return (long long)fr + owned;
 }
 // elements between two stored score rows of n items (stream_scores, the tie noise's rows): whole tiles of either size of the sweep (64 / 96 items)
@@ -613,7 +716,7 @@ inline long long score_row_stride(long long n) { return (n + 191) / 192 * 192; }
 inline long long stream_budget_bytes(const Workspace &ws)
 {
     if (g_sw.stream_budget_mb >= 0) return g_sw.stream_budget_mb << 20;
-    return free_plus_owned(ws, {"stream_scores", "sel_hi", "sel_lo"}) / 3;
+    return free_plus_owned(ws, {WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO}) / 3;
 }
 
 // Which top-K scheme a pass takes (rm_sweep.hpp LMODE):
@@ -640,7 +743,7 @@ template <class T> inline bool lane_lists_possible(int K, bool three_subtiles = 
 }
 // (the grid of the sweep is only known behind the plan: user blocks of the call, or a few rounds of 256 blocks when there are few)
 template <class T> inline long long lane_blocks_bound(long long m) { return (m + 4 * Prec<T>::GU - 1) / (4 * Prec<T>::GU) + 1024; }
-inline long long lane_budget_bytes(const Workspace &ws) { return free_plus_owned(ws, {"glists", "stream_scores", "sel_hi", "sel_lo"}) / 3; }
+inline long long lane_budget_bytes(const Workspace &ws) { return free_plus_owned(ws, {WS_GLISTS, WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO}) / 3; }
 template <class T> inline bool lane_lists_fit(const Workspace &ws, int K, long long m, bool three_subtiles)
 {
     return lane_lists_possible<T>(K, three_subtiles) && lane_list_bytes<T>(K, lane_blocks_bound<T>(m)) <= lane_budget_bytes(ws);
@@ -663,7 +766,7 @@ inline bool dense_rows_fit(const Workspace &ws, int m, long long n)
     const unsigned long long bytes = (unsigned long long)m * (unsigned long long)words * 4ull;
     if (bytes <= (1ull << 30)) return true;
     if (bytes > (8ull << 30)) return false;
-    return (long long)bytes <= free_plus_owned(ws, {"train_bits", "stream_scores", "sel_hi", "sel_lo"}) / 4;
+    return (long long)bytes <= free_plus_owned(ws, {WS_TRAIN_BITS, WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO}) / 4;
 }
 // `mask_test`: the rows mark the users' TEST items as well (k_merge_positives puts them back after the sweep; rm_noise.hpp clears
 // the test items' bits in its own copy of a row)
@@ -677,12 +780,12 @@ template <class C> inline void set_train_bits(SweepArgs &sa, Ctx &cx, const C &c
     const size_t bytes = (size_t)m * (size_t)words * 4;
     sa.train_bits = nullptr; sa.train_words = 0;
     if (!fit) { cx.dense.invalidate(); return; }
-    unsigned *bits = (unsigned *)ws.get("train_bits", bytes);
+    unsigned *bits = (unsigned *)ws.get(WS_TRAIN_BITS, bytes);
     // (the exact second pass of the tie noise evaluates a subset of the same users: the rows of the first pass are still there)
     const bool ready = (early && early_masked == mask_test) || (c.same_train_rows && cx.dense.fits(ws, m, words, mask_test));
     if (!ready)
         launch_train_bits(stream, m, n, (int)words, c.train_p, c.train_i, (mask_test || ent_masked) ? c.test_p : nullptr, c.test_i, bits,
-                          (const Plan *)ws.get("plan", sizeof(Plan)), c.only_users, ent_masked, mask_test);
+                          ws.array<Plan>(WS_PLAN, 1), c.only_users, ent_masked, mask_test);
     cx.dense.set(ws, words, m, mask_test, ready ? cx.dense.partial : c.only_users != nullptr, c.items_tag, c.train_p);
     sa.train_bits = bits; sa.train_words = (int)words;
 }
@@ -724,7 +827,7 @@ template <class T> inline int sample_seed_items(const Workspace &ws, int K, int 
         if (sizeof(T) == 8 && K < 16) return 0;
     }
     if (S > n || K > S) return 0;
-    if ((long long)sizeof(T) * n_slots * S > free_plus_owned(ws, {"sample_scores"}) / 8) return 0;
+    if ((long long)sizeof(T) * n_slots * S > free_plus_owned(ws, {WS_SAMPLE_SCORES}) / 8) return 0;
     return S;
 }
 template <class T, class Args>
@@ -732,7 +835,7 @@ inline void seed_from_sample(const Args &sa, Workspace &ws, int S, int NG, int n
 {
     typedef Prec<T> P;
     typedef typename std::remove_pointer<decltype(Args{}.thr_shared)>::type ThrT;
-    T *sample = (T *)ws.get("sample_scores", sizeof(T) * (size_t)n_slots * (size_t)S);
+    T *sample = ws.array<T>(WS_SAMPLE_SCORES, (size_t)n_slots * (size_t)S);
     Args sd = sa;
     sd.n = S; sd.tiles_total = S / TILE_ITEMS; sd.K = 1; sd.n_splits = 1; sd.tail_ublocks = 0; sd.tail_splits = 1; sd.part_splits = 1;
     sd.buffered_lists = 0; sd.ext_topk = 0; sd.lane_cap = 0; sd.lane_cnt = nullptr; sd.spec = 0; sd.dump = sample;
@@ -789,7 +892,7 @@ inline void launch_csr_checks(int m, int n, const int *train_p, const int *train
 template <class T>
 void check_csr_now(const Call<T> &c, hipStream_t stream, Ctx &cx)
 {
-    Plan *plan = (Plan *)cx.ws.get("plan", sizeof(Plan));
+    Plan *plan = cx.ws.array<Plan>(WS_PLAN, 1);
     cx.split.invalidate();                                         // (the Plan is zeroed below)
     if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));
     HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
@@ -1051,11 +1154,11 @@ struct Pipeline {
     // ---- plan: classify the users, slots and groups; beside it the CSR checks, the maxima, the early dense rows; read back ----
     void plan_stage()
     {
-        flags = (int *)ws.get("flags", sizeof(int) * (size_t)m);
-        user_nslots = (int *)ws.get("user_nslots", sizeof(int) * (size_t)m);
-        uslot_base = (int *)ws.get("uslot_base", sizeof(int) * (size_t)m);
-        plan = (Plan *)ws.get("plan", sizeof(Plan));
-        heavy_users = (int *)ws.get("heavy_users", sizeof(int) * (size_t)m);
+        flags = ws.array<int>(WS_FLAGS, (size_t)m);
+        user_nslots = ws.array<int>(WS_USER_NSLOTS, (size_t)m);
+        uslot_base = ws.array<int>(WS_USLOT_BASE, (size_t)m);
+        plan = ws.array<Plan>(WS_PLAN, 1);
+        heavy_users = ws.array<int>(WS_HEAVY_USERS, (size_t)m);
         ca = ClassifyArgs{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
                           flags, user_nslots, heavy_users, plan};
         ca.only = c.only_users; ca.reco = c.reco ? 1 : 0;
@@ -1091,25 +1194,25 @@ struct Pipeline {
         }
         const long long slot_bound = (long long)m + c.nnz_test / POS_CHUNK + 1;
         const long long group_bound = slot_bound / GU + 2;
-        slot_user = (int *)ws.get("slot_user", sizeof(int) * (size_t)slot_bound);
-        slot_chunk = (int *)ws.get("slot_chunk", sizeof(int) * (size_t)slot_bound);
-        slot_index = (int *)ws.get("slot_index", sizeof(int) * (size_t)slot_bound);
-        unsigned char *slot_j = (unsigned char *)ws.get("slot_j", (size_t)slot_bound);
-        gj = (int *)ws.get("gj", sizeof(int) * (size_t)group_bound);
-        grow = (long long *)ws.get("grow", sizeof(long long) * (size_t)group_bound);
-        sc_user = (int *)ws.get("sc_user", sizeof(int) * (size_t)slot_bound);
-        sc_chunk = (int *)ws.get("sc_chunk", sizeof(int) * (size_t)slot_bound);
+        slot_user = ws.array<int>(WS_SLOT_USER, (size_t)slot_bound);
+        slot_chunk = ws.array<int>(WS_SLOT_CHUNK, (size_t)slot_bound);
+        slot_index = ws.array<int>(WS_SLOT_INDEX, (size_t)slot_bound);
+        unsigned char *slot_j = ws.array<unsigned char>(WS_SLOT_J, (size_t)slot_bound);
+        gj = ws.array<int>(WS_GJ, (size_t)group_bound);
+        grow = ws.array<long long>(WS_GROW, (size_t)group_bound);
+        sc_user = ws.array<int>(WS_SC_USER, (size_t)slot_bound);
+        sc_chunk = ws.array<int>(WS_SC_CHUNK, (size_t)slot_bound);
         int *tile_total = nullptr, *tile_offset = nullptr;
         const int n_tiles = (int)cdiv(m, 1024);
         if (m > 8192) {                                          // one block walking the whole array costs ~0.5 us per 1024 entries
-            tile_total = (int *)ws.get("scan_tile_total", sizeof(int) * (size_t)n_tiles);
-            tile_offset = (int *)ws.get("scan_tile_offset", sizeof(int) * (size_t)n_tiles);
+            tile_total = ws.array<int>(WS_SCAN_TILE_TOTAL, (size_t)n_tiles);
+            tile_offset = ws.array<int>(WS_SCAN_TILE_OFFSET, (size_t)n_tiles);
         }
         items_known = cx.packed.of_call(c.items_tag);                          // a later batch of the same host call
         // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
         // depends on K alone: it stays in the workspace, and only a longer one (or one for a new allocation) is uploaded again -- the
         // copy comes from pageable memory, which blocks the host and waits for the stream
-        if (!c.reco) log2tab = (double *)ws.get("log2tab", sizeof(double) * (size_t)K);
+        if (!c.reco) log2tab = ws.array<double>(WS_LOG2TAB, (size_t)K);
         if (!c.reco && !cx.discounts.holds(ws, K)) {
             std::vector<double> lt((size_t)K);
             for (int i = 0; i < K; i++) lt[i] = std::log2(i + 2);
@@ -1145,12 +1248,12 @@ struct Pipeline {
         } else cx.split.invalidate();                                 // (the kernels below overwrite what the record speaks of)
         PosArgs<T> pf{};
         if (flat_early) {
-            ent_user = (int *)ws.get("ent_user", sizeof(int) * (size_t)c.nnz_test);
-            ent_masked = (unsigned char *)ws.get("ent_masked", (size_t)c.nnz_test);
+            ent_user = ws.array<int>(WS_ENT_USER, (size_t)c.nnz_test);
+            ent_masked = ws.array<unsigned char>(WS_ENT_MASKED, (size_t)c.nnz_test);
             pf.m = m; pf.n = n; pf.k = k; pf.A = c.A; pf.lda = c.lda; pf.B = c.B; pf.ldb = c.ldb;
             pf.train_p = c.train_p; pf.train_i = c.train_i; pf.test_p = c.test_p; pf.test_i = c.test_i; pf.flags = flags;
-            pf.pos_tmp = (T *)ws.get("pos_tmp", sizeof(T) * (size_t)c.nnz_test);
-            if (sizeof(T) == 4) pf.pos_key = (unsigned long long *)ws.get("pos_key", 8 * ((size_t)c.nnz_test + 8));
+            pf.pos_tmp = ws.array<T>(WS_POS_TMP, (size_t)c.nnz_test);
+            if (sizeof(T) == 4) pf.pos_key = (unsigned long long *)ws.get(WS_POS_KEY, 8 * ((size_t)c.nnz_test + 8));
             pf.noise_row = c.noise_row; pf.noise_row0 = c.noise_row0; pf.noise_E = c.noise_E; pf.noise_ld = c.noise_ld;
             pf.noise_flag = c.noise_flag; pf.plan = plan;
         }
@@ -1200,7 +1303,7 @@ struct Pipeline {
             if (attempt == 0 && std::is_same<T, float>::value && use_side && !c.ext_bits && dense_ok) {
                 SweepArgs probe{};
                 const bool guess = want_auc && !ext_topk && !g_sw.no_test_mask;
-                (void)ws.get("train_bits", (size_t)m * (size_t)dense_row_words(n) * 4);
+                (void)ws.get(WS_TRAIN_BITS, (size_t)m * (size_t)dense_row_words(n) * 4);
                 if (!(c.same_train_rows && cx.dense.fits(ws, m, dense_row_words(n), guess))) {
                     set_train_bits(probe, cx, c, m, n, dense_ok, side.on(), guess, false, false, flat_early ? ent_masked : nullptr);
                     side.mark(SIDE_ROWS_AND_PACKS); side.mark(SIDE_ROWS_FOR_POS);
@@ -1317,7 +1420,7 @@ struct Pipeline {
         hints = hints && kept.hp.n_slots > 0;
         if (hints) {
             // (the kernel's two counters, zeroed here where the call's stream is idle; the launch itself follows the verdict: sweep())
-            try { hint_counts_dev = (int *)ws.get("hint_counts", 2 * sizeof(int)); } catch (const RmError &) { hints = false; }
+            try { hint_counts_dev = ws.array<int>(WS_HINT_COUNTS, 2); } catch (const RmError &) { hints = false; }
             if (hints && !cx.hint_counts) { HIP_CHECK(hipHostMalloc((void **)&cx.hint_counts, 64, hipHostMallocDefault)); cx.hint_counts[0] = cx.hint_counts[1] = 0; }
             if (hints) HIP_CHECK(hipMemsetAsync(hint_counts_dev, 0, 2 * sizeof(int), stream));
         }
@@ -1365,7 +1468,7 @@ struct Pipeline {
         if (!keepable || reused) return;
         SplitCache &kept = cx.split;
         void *dst[SPLIT_ARRAYS] = {};
-        try { for (int i = 0; i < SPLIT_ARRAYS; i++) if (split_key.words[i] > 0) dst[i] = ws.get(SplitCache::copy_names[i], (size_t)split_key.words[i] * 4); }
+        try { for (int i = 0; i < SPLIT_ARRAYS; i++) if (split_key.words[i] > 0) dst[i] = ws.get(SplitCache::copies[i], (size_t)split_key.words[i] * 4); }
         catch (const RmError &) { keepable = false; return; }          // (no memory for the copies: nothing is kept)
         const hipStream_t st = side.on();
         for (int i = 0; i < SPLIT_ARRAYS; i++)
@@ -1374,12 +1477,12 @@ struct Pipeline {
         std::memcpy(&kept.key, &split_key, sizeof(SplitKey));
         kept.hp = hp; kept.check_nan = check_nan; kept.dense_masked = dense_ok && cx.dense.masked;
         kept.stamps.clear();
-        for (const char *name : {"flags", "user_nslots", "uslot_base", "plan", "heavy_users", "slot_user", "slot_chunk", "slot_index", "slot_j", "gj", "grow", "sc_user", "sc_chunk"})
-            kept.keep(ws, name);
-        if (flat_early) { kept.keep(ws, "ent_user"); kept.keep(ws, "ent_masked"); }
-        if (dense_ok) kept.keep(ws, "train_bits");
-        if (fa.heavy_topv) { kept.keep(ws, "heavy_topv"); kept.keep(ws, "heavy_nan"); }
-        for (int i = 0; i < SPLIT_ARRAYS; i++) if (dst[i]) kept.keep(ws, SplitCache::copy_names[i]);
+        for (WsBuf id : {WS_FLAGS, WS_USER_NSLOTS, WS_USLOT_BASE, WS_PLAN, WS_HEAVY_USERS, WS_SLOT_USER, WS_SLOT_CHUNK, WS_SLOT_INDEX, WS_SLOT_J, WS_GJ, WS_GROW, WS_SC_USER, WS_SC_CHUNK})
+            kept.keep(ws, id);
+        if (flat_early) { kept.keep(ws, WS_ENT_USER); kept.keep(ws, WS_ENT_MASKED); }
+        if (dense_ok) kept.keep(ws, WS_TRAIN_BITS);
+        if (fa.heavy_topv) { kept.keep(ws, WS_HEAVY_TOPV); kept.keep(ws, WS_HEAVY_NAN); }
+        for (int i = 0; i < SPLIT_ARRAYS; i++) if (dst[i]) kept.keep(ws, SplitCache::copies[i]);
     }
 
     // ideal-DCG values of the users with very long test rows (k_top_values: a wavefront per such user, a chain of K dependent
@@ -1393,8 +1496,8 @@ struct Pipeline {
         // (min(K, longest test row) values per user: with a cap of 256 the rows beyond it fell back to k_finalize's repeated selection on
         // one thread -- L x positives dependent loads: 160 of the 190 ms of a K = 300 step at BASELINE C2's shape)
         fa.heavy_ld = std::max(1, std::min(K, hp.max_npos));
-        fa.heavy_topv = (T *)ws.get("heavy_topv", sizeof(T) * (size_t)m * (size_t)fa.heavy_ld);
-        fa.heavy_nan = (unsigned char *)ws.get("heavy_nan", (size_t)m);
+        fa.heavy_topv = ws.array<T>(WS_HEAVY_TOPV, (size_t)m * (size_t)fa.heavy_ld);
+        fa.heavy_nan = ws.array<unsigned char>(WS_HEAVY_NAN, (size_t)m);
         fa.heavy_users = heavy_users; fa.n_heavy = hp.n_heavy;
         if (reused) return;                                          // (the values depend on the test rows and k_metrics alone: kept)
         hipLaunchKernelGGL((k_top_values<T, T>), dim3(cdiv((long long)hp.n_heavy * WAVE, 256)), dim3(256), 0, side.fork(SIDE_FORK), fa);
@@ -1405,8 +1508,8 @@ struct Pipeline {
     void prep()
     {
         // (recommendation lists: only k_collect_topk / k_select_topk go through `merged`; the lists in parts are merged into the caller's arrays)
-        if (!c.reco || want_lane || ext_topk) merged = (Entry<T> *)ws.get("merged", sizeof(Entry<T>) * (size_t)m * K);
-        if (c.pos_rank) rank_sorted = (long long *)ws.get("rank_sorted", sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1));
+        if (!c.reco || want_lane || ext_topk) merged = ws.array<Entry<T>>(WS_MERGED, (size_t)m * K);
+        if (c.pos_rank) rank_sorted = ws.array<long long>(WS_RANK_SORTED, (size_t)std::max<long long>(c.nnz_test, 1));
         if (rank_sorted) HIP_CHECK(hipMemsetAsync(rank_sorted, 0, sizeof(long long) * (size_t)std::max<long long>(c.nnz_test, 1), stream));
         // the argument block of the finalisation kernels is filled in as the pieces come into being
         fa.m = m; fa.n = n; fa.K = K; fa.req = req; fa.cumulative = c.cumulative ? 1 : 0; fa.noise = c.noise ? 1 : 0; fa.gu = GU;
@@ -1419,7 +1522,7 @@ struct Pipeline {
         fa.noise_flag = c.noise_flag; fa.plan = plan;
         fa.n_slots = n_slots; fa.slot_user = slot_user; fa.slot_chunk = slot_chunk;
         fa.stream_slot0 = stream_slot0;
-        if (want_auc && n_slots > 0) fa.auc_part = (AucPart *)ws.get("auc_part", sizeof(AucPart) * (size_t)n_slots);
+        if (want_auc && n_slots > 0) fa.auc_part = ws.array<AucPart>(WS_AUC_PART, (size_t)n_slots);
         fa.heavy_npos = ca.heavy_npos;
         stream_ld = (long long)g.tiles_total * g.tile_items;
         if (n_slots == 0) return;
@@ -1428,8 +1531,8 @@ struct Pipeline {
             // the preparation is the ideal-DCG values, the positives' tables and the two buffers k_score_rows fills
             launch_top_values();
             if (want_auc) positives();
-            stream_scores = (T *)ws.get("stream_scores", sizeof(T) * (size_t)std::max(n_stream, 1) * (size_t)stream_ld);
-            pst = (PartialStat<T> *)ws.get("pst", sizeof(PartialStat<T>) * (size_t)n_slots * g.n_part);
+            stream_scores = ws.array<T>(WS_STREAM_SCORES, (size_t)std::max(n_stream, 1) * (size_t)stream_ld);
+            pst = ws.array<PartialStat<T>>(WS_PST, (size_t)n_slots * g.n_part);
             RM_TRACE_POINT("run: preparation enqueued");
             return;
         }
@@ -1437,8 +1540,8 @@ struct Pipeline {
 
         // ---- pack operands into the MFMA images ----
         const long long bp_units = P::items_units(tiles_total, NG, tile_items), ap_units = P::users_units(n_groups, NG);
-        typename P::PackT *Bp = (typename P::PackT *)ws.get("Bp", 16 * (size_t)bp_units);
-        typename P::PackT *Ap = (typename P::PackT *)ws.get("Ap", 16 * (size_t)ap_units);
+        typename P::PackT *Bp = (typename P::PackT *)ws.get(WS_BP, 16 * (size_t)bp_units);
+        typename P::PackT *Ap = (typename P::PackT *)ws.get(WS_AP, 16 * (size_t)ap_units);
         // the packed item image survives between the batches of one host call (same B, same geometry)
         const bool items_packed = cx.packed.holds(ws, c.items_tag, tile_items, NG);
         // Only the sweep reads the packed images: with a side stream they are made there, behind the dense train rows and beside the
@@ -1459,9 +1562,9 @@ struct Pipeline {
 
         if (want_auc) positives();
 
-        if (n_stream > 0) stream_scores = (T *)ws.get("stream_scores", sizeof(T) * (size_t)n_stream * (size_t)stream_ld);
-        if (!ext_topk) pl = (Entry<T> *)ws.get("pl", sizeof(Entry<T>) * (size_t)n_slots * g.n_part * K);
-        pst = (PartialStat<T> *)ws.get("pst", sizeof(PartialStat<T>) * (size_t)n_slots * g.n_part);
+        if (n_stream > 0) stream_scores = ws.array<T>(WS_STREAM_SCORES, (size_t)n_stream * (size_t)stream_ld);
+        if (!ext_topk) pl = ws.array<Entry<T>>(WS_PL, (size_t)n_slots * g.n_part * K);
+        pst = ws.array<PartialStat<T>>(WS_PST, (size_t)n_slots * g.n_part);
         const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
         lane_lists = want_lane && !ext_topk;                     // per-lane append buffers + k_collect_topk (rm_list.hpp)
         int lane_cap = lane_lists ? P::lane_cap(K) : 0;
@@ -1469,13 +1572,13 @@ struct Pipeline {
         if (lane_lists && g_sw.lane_cap_min >= 0)        // K + slack survivors and one tile's appends (16: both precisions' bound) in one lane
             lane_cap = std::min(lane_cap, (K + lane_sel_slack(K) + 16 + 1 + 15) / 16 * 16);
         if (lane_lists) {
-            glists = (typename P::ListT *)ws.get("glists", (size_t)n_blocks * g.n_waves * WAVE * (size_t)lane_cap * (sizeof(T) + 4));
-            lane_cnt = (int *)ws.get("lane_cnt", sizeof(int) * (size_t)n_blocks * g.n_waves * WAVE);
+            glists = (typename P::ListT *)ws.get(WS_GLISTS, (size_t)n_blocks * g.n_waves * WAVE * (size_t)lane_cap * (sizeof(T) + 4));
+            lane_cnt = ws.array<int>(WS_LANE_CNT, (size_t)n_blocks * g.n_waves * WAVE);
         } else if (!g.list_in_lds && !ext_topk) {
-            glists = (typename P::ListT *)ws.get("glists", sizeof(typename P::ListT) * (size_t)n_blocks * g.n_waves * GU * (2 * K + 32));
+            glists = ws.array<typename P::ListT>(WS_GLISTS, (size_t)n_blocks * g.n_waves * GU * (2 * K + 32));
         }
 
-        thr_shared = (ThrT *)ws.get("thr_shared", sizeof(ThrT) * (size_t)n_slots);
+        thr_shared = ws.array<ThrT>(WS_THR_SHARED, (size_t)n_slots);
         if (want_auc && !ext_topk && !g_sw.no_seed)
             hipLaunchKernelGGL((k_seed_thresholds<T, ThrT>), dim3(cdiv(n_slots, 256)), dim3(256), 0, stream, n_slots, stream_slot0, K, GU, slot_user, slot_chunk,
                                user_nslots, flags, c.test_p, grow, pos_score, spos_score, thr_shared);
@@ -1503,8 +1606,8 @@ struct Pipeline {
         if (sample_S > 0 && !sample_lists) seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, g.n_ublocks, stream);
         else if (sample_S > 0) {
             const long long units = P::items_units(sample_S / TILE_ITEMS, NG);
-            typename P::PackT *Bs = (typename P::PackT *)ws.get("sample_items", 16 * (size_t)units);
-            void *Ls = ws.get("sample_lists", sizeof(typename P::ListT) * (size_t)g.n_ublocks * 8 * GU * (2 + 32));
+            typename P::PackT *Bs = (typename P::PackT *)ws.get(WS_SAMPLE_ITEMS, 16 * (size_t)units);
+            void *Ls = ws.array<typename P::ListT>(WS_SAMPLE_LISTS, (size_t)g.n_ublocks * 8 * GU * (2 + 32));
             pack_operands(c.A, c.lda, c.B, c.ldb, sample_S, k, NG, TILE_ITEMS, slot_user, 0, Ap, 0, Bs, units, stream, true);
             seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, g.n_ublocks, stream, Bs, Ls);
         }
@@ -1516,17 +1619,17 @@ struct Pipeline {
     {
         const int n_groups = hp.n_groups;
         const long long rows = hp.total_rows + n_groups;       // 2^j rows per group (one +inf pad row each)
-        pos_score = (T *)ws.get("pos_score", sizeof(T) * (size_t)(rows + 1) * GU);
-        pos_item = (int *)ws.get("pos_item", sizeof(int) * (size_t)(rows + 1) * GU);
-        hist = (unsigned *)ws.get("hist", sizeof(unsigned) * (size_t)(rows + 1) * GU);
-        T *pos_tmp = (T *)ws.get("pos_tmp", sizeof(T) * (size_t)std::max<long long>(c.nnz_test, 1));
-        pos_order = (int *)ws.get("pos_order", sizeof(int) * (size_t)std::max<long long>(c.nnz_test, 1));
+        pos_score = ws.array<T>(WS_POS_SCORE, (size_t)(rows + 1) * GU);
+        pos_item = ws.array<int>(WS_POS_ITEM, (size_t)(rows + 1) * GU);
+        hist = ws.array<unsigned>(WS_HIST, (size_t)(rows + 1) * GU);
+        T *pos_tmp = ws.array<T>(WS_POS_TMP, (size_t)std::max<long long>(c.nnz_test, 1));
+        pos_order = ws.array<int>(WS_POS_ORDER, (size_t)std::max<long long>(c.nnz_test, 1));
         PosArgs<T> pa{m, n, k, c.A, c.lda, c.B, c.ldb, c.train_p, c.train_i, c.test_p, c.test_i,
                       flags, user_nslots, uslot_base, slot_index, grow, pos_tmp, pos_order, pos_score, pos_item, GU};
         pa.noise_row = c.noise_row; pa.noise_row0 = c.noise_row0; pa.noise_E = c.noise_E; pa.noise_ld = c.noise_ld;
         pa.noise_flag = c.noise_flag; pa.plan = plan;
         if (sizeof(T) == 4)
-            pa.pos_key = (unsigned long long *)ws.get("pos_key", 8 * ((size_t)std::max<long long>(c.nnz_test, 1) + 8));
+            pa.pos_key = (unsigned long long *)ws.get(WS_POS_KEY, 8 * ((size_t)std::max<long long>(c.nnz_test, 1) + 8));
         // Scores of the test entries: by entry (k_pos_scores_flat, launched beside the plan chain: every lane busy) unless the call
         // evaluates a few of its users only -- then a wavefront per slot is less work.
         const bool flat = flat_early;
@@ -1541,9 +1644,9 @@ struct Pipeline {
         const hipStream_t fill = (flat && pos_beside) ? stream : ps;
         if (n_stream > 0) {
             const size_t nz = (size_t)std::max<long long>(c.nnz_test, 1);
-            spos_score = (T *)ws.get("spos_score", sizeof(T) * nz);
-            spos_item = (int *)ws.get("spos_item", sizeof(int) * nz);
-            shist = (unsigned *)ws.get("shist", sizeof(unsigned) * nz);
+            spos_score = ws.array<T>(WS_SPOS_SCORE, nz);
+            spos_item = ws.array<int>(WS_SPOS_ITEM, nz);
+            shist = ws.array<unsigned>(WS_SHIST, nz);
             pb.stream = 1; pb.spos_score = spos_score; pb.spos_item = spos_item;
             // (+inf in every rank: entries that repeat an item -- a non-canonical CSR row -- share a rank and leave one unused)
             hipLaunchKernelGGL(k_init_tables<T>, dim3(cdiv((long long)nz, 256)), dim3(256), 0, fill, spos_score, shist, (long long)nz);
@@ -1693,8 +1796,8 @@ struct Pipeline {
         int sel_ld = 2;
         while (sel_ld < K) sel_ld <<= 1;
         fa.ext_topk = 1; fa.sel_ld = sel_ld;
-        fa.sel_hi = (unsigned long long *)ws.get("sel_hi", sizeof(unsigned long long) * (size_t)n_slots * sel_ld);
-        fa.sel_lo = (unsigned *)ws.get("sel_lo", sizeof(unsigned) * (size_t)n_slots * sel_ld);
+        fa.sel_hi = ws.array<unsigned long long>(WS_SEL_HI, (size_t)n_slots * sel_ld);
+        fa.sel_lo = ws.array<unsigned>(WS_SEL_LO, (size_t)n_slots * sel_ld);
         hipLaunchKernelGGL((k_select_topk<T, T>), dim3(n_slots), dim3(SELECT_THREADS), 0, stream, fa);
     }
 
@@ -1832,7 +1935,7 @@ template <class T> struct NoiseGeom {
         const long long row_bytes = e_ld * (long long)sizeof(T) + d_ld * 4;
         long long budget;
         if (g_sw.noise_budget_mb >= 0) budget = g_sw.noise_budget_mb << 20;
-        else budget = free_plus_owned(ws, {"noise_draws", "noise_rows"}) / 3;
+        else budget = free_plus_owned(ws, {WS_NOISE_DRAWS, WS_NOISE_ROWS}) / 3;
         cap = std::max<long long>(1, std::min<long long>(budget / row_bytes, 1 << 20));
     }
 };
@@ -1889,10 +1992,10 @@ template <class T> struct ExactPass {
     int assign(int m, const int *flags, const int *skip, int known, int *word)
     {
         Workspace &pw = pc->ws;
-        noise_row = (int *)pw.get("noise_row", sizeof(int) * (size_t)m);
-        row_user = (int *)pw.get("noise_row_user", sizeof(int) * (size_t)(known >= 0 ? std::max(known, 1) : m));
-        int *counter = (int *)pw.get("noise_counter", sizeof(int));
-        only = (unsigned char *)pw.get("noise_only", (size_t)m);
+        noise_row = pw.array<int>(WS_NOISE_ROW, (size_t)m);
+        row_user = pw.array<int>(WS_NOISE_ROW_USER, (size_t)(known >= 0 ? std::max(known, 1) : m));
+        int *counter = pw.array<int>(WS_NOISE_COUNTER, 1);
+        only = pw.array<unsigned char>(WS_NOISE_ONLY, (size_t)m);
         HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(int), ps));
         hipLaunchKernelGGL(k_noise_assign_rows, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, flags, skip, noise_row, row_user, counter);
         if (known >= 0) return known;
@@ -1903,7 +2006,7 @@ template <class T> struct ExactPass {
     // the metric block of a pass that must not write into the call's outputs, [metric][users x width], in the pass's workspace
     void block(Call<T> &c, const MetricLayout &lay) const
     {
-        lay.point_at((T *)pc->ws.get("o_exact", sizeof(T) * std::max<size_t>(lay.block_size((size_t)c.m), 1)), (size_t)c.m, c.out);
+        lay.point_at(pc->ws.array<T>(WS_O_EXACT, std::max<size_t>(lay.block_size((size_t)c.m), 1)), (size_t)c.m, c.out);
     }
     // The flagged users of rows [r0, r0 + rows) through the pipeline, as passes of call `c` (over all its m users): their noise rows,
     // then run().  Dense train rows of a pass beside: the first pass's when `cx` still holds them for exactly these users, or with
@@ -1914,14 +2017,14 @@ template <class T> struct ExactPass {
         Workspace &pw = pc->ws;
         const int m = c.m, n = c.n;
         hipLaunchKernelGGL(k_noise_select, dim3(cdiv(m, 256)), dim3(256), 0, ps, m, noise_row, (int)r0, (int)r0 + rows, only);
-        unsigned *D = (unsigned *)pw.get("noise_draws", sizeof(unsigned) * (size_t)rows * (size_t)g.d_ld);
-        T *E = (T *)pw.get("noise_rows", sizeof(T) * (size_t)rows * (size_t)g.e_ld);
+        unsigned *D = pw.array<unsigned>(WS_NOISE_DRAWS, (size_t)rows * (size_t)g.d_ld);
+        T *E = pw.array<T>(WS_NOISE_ROWS, (size_t)rows * (size_t)g.e_ld);
         const long long words = dense_row_words(n);
         unsigned *bits = nullptr;
         if (own_rows) {
             const bool fit = std::is_same<T, float>::value && dense_rows_fit(pw, m, n);
             if (fit) {
-                bits = (unsigned *)pw.get("train_bits", (size_t)m * (size_t)words * 4);
+                bits = (unsigned *)pw.get(WS_TRAIN_BITS, (size_t)m * (size_t)words * 4);
                 pc->dense.invalidate();
                 launch_train_bits(ps, m, n, (int)words, c.train_p, c.train_i, (const int *)nullptr, c.test_i, bits, (const Plan *)nullptr, only);
                 c.ext_bits = bits; c.ext_words = words; c.ext_masked = false;
@@ -1984,15 +2087,15 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
             c.A = c0.A + (size_t)b0 * c0.lda; c.m = mb; c.train_p = c0.train_p + b0; c.test_p = c0.test_p + b0; c.user0 = c0.user0 + b0;
             c.outputs() = c0.from_user((size_t)b0, lay.per, c0.K);
             if (c0.only_users) c.only_users = c0.only_users + b0;
-            unsigned *D = (unsigned *)ws.get("noise_draws", sizeof(unsigned) * (size_t)mb * (size_t)g.d_ld);
-            T *E = (T *)ws.get("noise_rows", sizeof(T) * (size_t)mb * (size_t)g.e_ld);
+            unsigned *D = ws.array<unsigned>(WS_NOISE_DRAWS, (size_t)mb * (size_t)g.d_ld);
+            T *E = ws.array<T>(WS_NOISE_ROWS, (size_t)mb * (size_t)g.e_ld);
             noise_make_rows<T>(cx, c0, g, nullptr, mb, c.train_p, c.user0, D, E, stream);
             set_noise_for_all(c, E, g.e_ld);
             run<T>(c, stream, cx);
         }
         return;
     }
-    int *flag = (int *)ws.get("noise_flag", sizeof(int) * (size_t)m);
+    int *flag = ws.array<int>(WS_NOISE_FLAG, (size_t)m);
     HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int) * (size_t)m, stream));
     Call<T> c1 = c0;
     set_first_pass(c1, flag);
@@ -2005,11 +2108,11 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     const bool beside = !c0.topk_idx && !c0.only_users && !g_sw.noise_sequential;
     int *snap = nullptr;
     if (beside) {
-        snap = (int *)ws.get("noise_flag_snap", sizeof(int) * (size_t)m);
+        snap = ws.array<int>(WS_NOISE_FLAG_SNAP, (size_t)m);
         cx.noise_words->first_early = 0;
         c1.flag_snapshot = snap; c1.flag_count_host = &cx.noise_words->first_early; c1.flags_event = cx.flags_ev;
     }
-    Plan *plan = (Plan *)ws.get("plan", sizeof(Plan));
+    Plan *plan = ws.array<Plan>(WS_PLAN, 1);
     int n_beside = 0;
     ExactPass<T> nb(cx);
     run<T>(c1, stream, cx);
@@ -2154,7 +2257,7 @@ template <class T> long long batch_users_max(const Workspace &ws, int n, int k, 
 {
     if (scores) {
         const long long row = score_row_stride(n) * (long long)sizeof(T);
-        long long batch = free_plus_owned(ws, {"stream_scores", "sel_hi", "sel_lo", "in_S0", "in_S1"}) / (7 * row);
+        long long batch = free_plus_owned(ws, {WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO, WS_IN_S0, WS_IN_S1}) / (7 * row);
         if (g_sw.stream_budget_mb >= 0) batch = std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row);
         if (g_sw.batch_users > 0) batch = std::min<long long>(batch, (long long)g_sw.batch_users);
         return std::max<long long>(1, std::min<long long>(batch, 1 << 20));
@@ -2308,17 +2411,17 @@ template <class T> struct HostRange {
         up = cx.up_stream;
         if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(up, cx.done, 0));   // the previous call on this context may still read the buffers
         // item factors, dense rows of k
-        dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
+        dB = ws.array<T>(WS_IN_B, (size_t)n * k);
         if (m <= 0) { items.run(dB, cx.device, up); HIP_CHECK(hipStreamSynchronize(up)); return false; }
         // this range's users: factors, CSR rows with the index pointers rebased to the range
         tr0 = h.train_p[u0]; te0 = h.test_p[u0];
         nnz_tr = (long long)h.train_p[u0 + m] - tr0; nnz_te = (long long)h.test_p[u0 + m] - te0;
-        dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
-        dtrp = (int *)ws.get("in_trp", sizeof(int) * (size_t)(m + 1));
-        dtep = h.reco ? nullptr : (int *)ws.get("in_tep", sizeof(int) * (size_t)(m + 1));
-        dtri = (int *)ws.get("in_tri", sizeof(int) * (size_t)std::max<long long>(nnz_tr, 1));
-        dtei = (int *)ws.get("in_tei", sizeof(int) * (size_t)std::max<long long>(nnz_te, 1));
-        dtev = h.test_v ? (T *)ws.get("in_tev", sizeof(T) * (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
+        dA = ws.array<T>(WS_IN_A, (size_t)m * k);
+        dtrp = ws.array<int>(WS_IN_TRP, (size_t)(m + 1));
+        dtep = h.reco ? nullptr : ws.array<int>(WS_IN_TEP, (size_t)(m + 1));
+        dtri = ws.array<int>(WS_IN_TRI, (size_t)std::max<long long>(nnz_tr, 1));
+        dtei = ws.array<int>(WS_IN_TEI, (size_t)std::max<long long>(nnz_te, 1));
+        dtev = h.test_v ? ws.array<T>(WS_IN_TEV, (size_t)std::max<long long>(nnz_te, 1)) : nullptr;
         trp = h.train_p + u0; tep = h.test_p + u0;
         if (tr0 || te0) {
             rb.resize(2 * (size_t)(m + 1));
@@ -2328,10 +2431,10 @@ template <class T> struct HostRange {
         HIP_CHECK(hipMemcpyAsync(dtrp, trp, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
         if (dtep) HIP_CHECK(hipMemcpyAsync(dtep, tep, sizeof(int) * (size_t)(m + 1), hipMemcpyHostToDevice, up));
         if (h.topk_idx) {
-            d_rank.topk_idx = (int *)ws.get("o_topk_idx", sizeof(int) * (size_t)m * K);
-            if (h.topk_score) d_rank.topk_score = (T *)ws.get("o_topk_score", sizeof(T) * (size_t)m * K);
-            if (h.pos_rank) d_rank.pos_rank = (long long *)ws.get("o_pos_rank", sizeof(long long) * (size_t)std::max<long long>(nnz_te, 1));
-            d_rank.status = (int *)ws.get("o_status", sizeof(int) * (size_t)m);
+            d_rank.topk_idx = ws.array<int>(WS_O_TOPK_IDX, (size_t)m * K);
+            if (h.topk_score) d_rank.topk_score = ws.array<T>(WS_O_TOPK_SCORE, (size_t)m * K);
+            if (h.pos_rank) d_rank.pos_rank = ws.array<long long>(WS_O_POS_RANK, (size_t)std::max<long long>(nnz_te, 1));
+            d_rank.status = ws.array<int>(WS_O_STATUS, (size_t)m);
         }
         return true;
     }
@@ -2360,13 +2463,13 @@ template <class T> struct HostRange {
         }
         for (int i = 0; i < 2; i++) {
             if (i == 1 && ctxs[1] == ctxs[0]) { dblocks[1] = dblocks[0]; hblocks[1] = hblocks[0]; break; }
-            dblocks[i] = (T *)ctxs[i]->ws.get("o_block", sizeof(T) * std::max<size_t>(lay.block_size((size_t)mb_max), 1));
+            dblocks[i] = ctxs[i]->ws.array<T>(WS_O_BLOCK, std::max<size_t>(lay.block_size((size_t)mb_max), 1));
             hblocks[i] = lay.rec_w ? (T *)ctxs[i]->pinned_get(sizeof(T) * lay.block_size((size_t)mb_max)) : nullptr;
         }
         two_ctx = ctxs[1] != ctxs[0];
         // the caller's scores: the rows of a batch, dense, in one of two buffers -- batch i + 1 travels while batch i runs, and with one
         // context batch i - 1 has been waited for by then
-        if (h.scores) for (int i = 0; i < std::min(n_batches, 2); i++) dS[i] = (T *)ws.get(i ? "in_S1" : "in_S0", sizeof(T) * (size_t)mb_max * (size_t)n);
+        if (h.scores) for (int i = 0; i < std::min(n_batches, 2); i++) dS[i] = ws.array<T>(i ? WS_IN_S1 : WS_IN_S0, (size_t)mb_max * (size_t)n);
         // fp32 tie noise over several batches: every batch runs its first pass only and flags the users the noise can touch in its
         // slice of `range_flag`; ONE exact pass over the flagged users of the whole range follows the last batch.  (Per batch, the
         // exact pass costs two waits on the host -- for the flags, for its own plan -- during which the next batch is not enqueued:
@@ -2377,9 +2480,9 @@ template <class T> struct HostRange {
         // practice all of them -- are evaluated exactly BESIDE that sweep on a context of their own (exact_beside_last), as the device entry
         // does (run_call); what remains behind the last batch is the host-side scatter of their values, and an exact pass over the few
         // users only a batch's k_finalize flagged (a top-K score in the zone), usually none
-        range_flag = (int *)ws.get("noise_flag_range", sizeof(int) * (size_t)m);
+        range_flag = ws.array<int>(WS_NOISE_FLAG_RANGE, (size_t)m);
         HIP_CHECK(hipMemsetAsync(range_flag, 0, sizeof(int) * (size_t)m, up));      // (in front of batch 0's rows: every batch waits for its rows' event)
-        range_snap = (int *)ws.get("noise_flag_range_snap", sizeof(int) * (size_t)m);
+        range_snap = ws.array<int>(WS_NOISE_FLAG_RANGE_SNAP, (size_t)m);
         cx.need_noise_words();
     }
 
@@ -2428,7 +2531,7 @@ template <class T> struct HostRange {
     {
         const long long b0 = fl[which].b0; const int mb = fl[which].mb;
         Ctx &bc = *ctxs[which]; hipStream_t bs = streams[which];
-        const Plan *plan = (const Plan *)bc.ws.get("plan", sizeof(Plan));
+        const Plan *plan = bc.ws.array<Plan>(WS_PLAN, 1);
         // (`range_noise`: run_call ran on this context with the noise on, so the context has its words)
         if (range_noise) HIP_CHECK(hipMemcpyAsync(&bc.noise_words->batch_flagged, &plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, bs));
         if (lay.rec_w) HIP_CHECK(hipMemcpyAsync(hblocks[which], dblocks[which], sizeof(T) * lay.block_size((size_t)mb), hipMemcpyDeviceToHost, bs));
@@ -2508,7 +2611,7 @@ template <class T> struct HostRange {
         GatherArgs<T> ga{};
         for (int i = 0; i < 10; i++) { ga.src[i] = c.out[i]; ga.width[i] = (int)lay.width(i); ga.off[i] = (int)lay.rec_off[i]; }
         ga.out_w = (int)lay.rec_w;
-        T *dg = (T *)gc.ws.get("o_exact_packed", sizeof(T) * lay.rec_w * (size_t)count);
+        T *dg = gc.ws.array<T>(WS_O_EXACT_PACKED, lay.rec_w * (size_t)count);
         hipLaunchKernelGGL(k_noise_gather<T>, dim3(cdiv(count, 256)), dim3(256), 0, st, count, row_user, ga, dg);
         hx = (T *)gc.pinned_get(sizeof(T) * lay.rec_w * (size_t)count + sizeof(int) * (size_t)count);
         hu = (int *)(hx + lay.rec_w * (size_t)count);
@@ -2789,7 +2892,7 @@ void run_dev(const Request<T> &r, hipStream_t stream)
     std::lock_guard<std::mutex> lk(cx.mu);
     cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
     if (r.reco && !r.train_p) {
-        int *z = (int *)cx.ws.get("reco_zero_p", sizeof(int) * ((size_t)r.m + 1));
+        int *z = cx.ws.array<int>(WS_RECO_ZERO_P, (size_t)r.m + 1);
         if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));          // (an earlier call on another stream may still read it)
         HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)r.m + 1), stream));
         c.train_p = z; c.train_i = z; c.nnz_train = 0;
@@ -2808,9 +2911,9 @@ void run_dev(const Request<T> &r, hipStream_t stream)
     int rc = rm_csr_sort_rows(trp.data(), tri.data(), nullptr, 0, c.m, 0);
     if (rc == RM_OK) rc = rm_csr_sort_rows(tep.data(), tei.data(), c.test_v ? (void *)tev.data() : nullptr, c.test_v ? (int32_t)sizeof(T) : 0, c.m, 0);
     if (rc != RM_OK) throw RmError{rc, "sorting a copy of the CSR rows failed"};
-    int *dtri = (int *)cx.ws.get("sorted_tri", sizeof(int) * std::max<size_t>(nnz_tr, 1));
-    int *dtei = (int *)cx.ws.get("sorted_tei", sizeof(int) * std::max<size_t>(nnz_te, 1));
-    T *dtev = c.test_v ? (T *)cx.ws.get("sorted_tev", sizeof(T) * std::max<size_t>(nnz_te, 1)) : nullptr;
+    int *dtri = cx.ws.array<int>(WS_SORTED_TRI, std::max<size_t>(nnz_tr, 1));
+    int *dtei = cx.ws.array<int>(WS_SORTED_TEI, std::max<size_t>(nnz_te, 1));
+    T *dtev = c.test_v ? cx.ws.array<T>(WS_SORTED_TEV, std::max<size_t>(nnz_te, 1)) : nullptr;
     if (nnz_tr) HIP_CHECK(hipMemcpyAsync(dtri, tri.data(), sizeof(int) * nnz_tr, hipMemcpyHostToDevice, stream));
     if (nnz_te) HIP_CHECK(hipMemcpyAsync(dtei, tei.data(), sizeof(int) * nnz_te, hipMemcpyHostToDevice, stream));
     if (dtev && nnz_te) HIP_CHECK(hipMemcpyAsync(dtev, tev.data(), sizeof(T) * nnz_te, hipMemcpyHostToDevice, stream));
@@ -2834,25 +2937,25 @@ void debug_scores(const T *A, size_t lda, const T *B, size_t ldb, int m, int n, 
     cx.packed.invalidate();                                  // the packed item image is overwritten below
     cx.split.invalidate();                                   // ... and so are the slot tables
     hipStream_t stream = nullptr;
-    T *dA = (T *)ws.get("in_A", sizeof(T) * (size_t)m * k);
-    T *dB = (T *)ws.get("in_B", sizeof(T) * (size_t)n * k);
+    T *dA = ws.array<T>(WS_IN_A, (size_t)m * k);
+    T *dB = ws.array<T>(WS_IN_B, (size_t)n * k);
     HIP_CHECK(hipMemcpy2DAsync(dA, sizeof(T) * k, A, sizeof(T) * lda, sizeof(T) * k, m, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpy2DAsync(dB, sizeof(T) * k, B, sizeof(T) * ldb, sizeof(T) * k, n, hipMemcpyHostToDevice, stream));
     const int n_groups = (m + GU - 1) / GU, n_ublocks = (n_groups + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK;
     const int tiles_total = (n + TILE_ITEMS - 1) / TILE_ITEMS;
-    int *slot_user = (int *)ws.get("slot_user", sizeof(int) * (size_t)m);
-    int *zeros = (int *)ws.get("dbg_zeros", sizeof(int) * (size_t)(m + 1 + n_groups));
-    long long *grow = (long long *)ws.get("grow", sizeof(long long) * (size_t)n_groups);
+    int *slot_user = ws.array<int>(WS_SLOT_USER, (size_t)m);
+    int *zeros = ws.array<int>(WS_DBG_ZEROS, (size_t)(m + 1 + n_groups));
+    long long *grow = ws.array<long long>(WS_GROW, (size_t)n_groups);
     HIP_CHECK(hipMemsetAsync(zeros, 0, sizeof(int) * (size_t)(m + 1 + n_groups), stream));
     HIP_CHECK(hipMemsetAsync(grow, 0, sizeof(long long) * (size_t)n_groups, stream));
     hipLaunchKernelGGL(k_iota<int>, dim3(cdiv(m, 256)), dim3(256), 0, stream, slot_user, m);
     const long long bp_units = P::items_units(tiles_total, NG), ap_units = P::users_units(n_groups, NG);
-    typename P::PackT *Bp = (typename P::PackT *)ws.get("Bp", 16 * (size_t)bp_units);
-    typename P::PackT *Ap = (typename P::PackT *)ws.get("Ap", 16 * (size_t)ap_units);
+    typename P::PackT *Bp = (typename P::PackT *)ws.get(WS_BP, 16 * (size_t)bp_units);
+    typename P::PackT *Ap = (typename P::PackT *)ws.get(WS_AP, 16 * (size_t)ap_units);
     pack_operands(dA, (size_t)k, dB, (size_t)k, n, k, NG, TILE_ITEMS, slot_user, m, Ap, ap_units, Bp, bp_units, stream);
-    T *dump = (T *)ws.get("dbg_dump", sizeof(T) * (size_t)m * n);
+    T *dump = ws.array<T>(WS_DBG_DUMP, (size_t)m * n);
     const int K = 1;
-    typename P::ListT *glists = (typename P::ListT *)ws.get("glists", sizeof(typename P::ListT) * (size_t)n_ublocks * 8 * GU * (2 * K + 32));
+    typename P::ListT *glists = ws.array<typename P::ListT>(WS_GLISTS, (size_t)n_ublocks * 8 * GU * (2 * K + 32));
     typename P::Args sa{};
     sa.n = n; sa.K = K; sa.ngt = NG; sa.n_slots = m; sa.n_groups = n_groups; sa.n_ublocks = n_ublocks; sa.n_splits = 1; sa.part_splits = 1;
     sa.tiles_total = tiles_total; sa.jmax = 0; sa.check_nan = 1; sa.Ap = (decltype(sa.Ap))Ap; sa.Bp = (decltype(sa.Bp))Bp;
@@ -3191,9 +3294,9 @@ extern "C" int rm_debug_set_list_ids(const int32_t *ids, int32_t m, int32_t K)
         Ctx &cx = context(0);
         std::lock_guard<std::mutex> lk(cx.mu);
         const SplitCache &kept = cx.split;
-        const Workspace::Buf buf = cx.ws.peek("merged");
+        const Workspace::Buf buf = cx.ws.peek(WS_MERGED);
         const long long count = (long long)m * K;
-        if (!ids || m <= 0 || K <= 0 || !kept.valid || kept.lists_stamp == 0 || kept.lists_stamp != buf.stamp || kept.key.m != m || kept.key.K != K ||
+        if (!ids || m <= 0 || K <= 0 || !kept.valid || !kept.lists.current(cx.ws) || kept.key.m != m || kept.key.K != K ||
             (size_t)count * (kept.key.elem == 4 ? sizeof(Entry<float>) : sizeof(Entry<double>)) > buf.bytes)
             throw RmError{RM_ERR_INVALID, "rm_debug_set_list_ids: the context keeps no lists of " + std::to_string(m) + " x " + std::to_string(K) + " entries"};
         HIP_CHECK(hipDeviceSynchronize());
