@@ -230,6 +230,63 @@ def _no_lists(k, dtype, return_scores):
     return (np.empty((0, k), np.int32), np.empty((0, k), dtype) if return_scores else None, np.empty(0, np.int32))
 
 
+# ---- `scores` as a torch.Tensor (the from-scores functions) ---------------------------------------------------------------------
+def _torch_if_tensor(scores):
+    """the torch module when `scores` is a torch.Tensor, else None -- torch is never imported for it: a tensor cannot exist without"""
+    import sys
+    torch = sys.modules.get("torch")
+    return torch if torch is not None and isinstance(scores, torch.Tensor) else None
+
+
+def _tensor_kind(torch, scores):
+    """"f16" / "bf16" (include/recometrics_hip_half.h), np.float32 / np.float64 (the entries NumPy arrays take), None for any other dtype"""
+    return {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: np.float32, torch.float64: np.float64}.get(scores.dtype)
+
+
+def _cpu_tensor_as_array(torch, scores, kind):
+    """A CPU tensor as a NumPy array over the SAME memory: float16 / float32 / float64 as they are, bfloat16 -- NumPy has no such dtype
+    -- as its bit patterns in uint16.  Strides are kept; `_row_major_with_ld` then passes `stride(1) == 1` with its row stride and
+    copies anything else once."""
+    scores = scores.detach()
+    return scores.view(torch.int16).numpy().view(np.uint16) if kind == "bf16" else scores.numpy()
+
+
+class _DeviceCall:
+    """What the two from-scores functions share when `scores` is a GPU tensor: the call runs on the tensor's device and on torch's
+    current stream there, through the device entries; index arrays are uploaded, outputs are device tensors, and the stream is
+    synchronised before they come back as NumPy arrays."""
+
+    def __init__(self, torch, scores, kind):
+        self.torch, self.kind, self.device = torch, kind, scores.device
+        self.S = scores.detach() if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.detach().contiguous()
+        self.out_dtype = torch.float64 if kind is np.float64 else torch.float32
+        self.np_dtype = np.float64 if kind is np.float64 else np.float32
+        self.keep = []                                              # the uploads live until the stream has been synchronised
+
+    def put(self, array):
+        """device address of a host array's copy (0 for None or an empty one)"""
+        if array is None or array.size == 0:
+            return 0
+        t = self.torch.from_numpy(np.ascontiguousarray(array)).to(self.device)
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def empty(self, shape, dtype=None):
+        return self.torch.empty(shape, dtype=dtype or self.out_dtype, device=self.device)
+
+    def run(self, entry, half_entry, **arguments):
+        """`entry(dtype, S, lds, m, n, ...)` of the binding, or its 16-bit form `half_entry(kind, ...)`, on the current stream; waits"""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            _binding.load()
+            _binding.set_device(self.device.index if self.device.index is not None else torch.cuda.current_device())
+            stream = torch.cuda.current_stream()
+            (half_entry if isinstance(self.kind, str) else entry)(
+                self.kind, self.S.data_ptr(), self.S.stride(0), self.S.shape[0], self.S.shape[1], stream=stream.cuda_stream, **arguments)
+            stream.synchronize()
+        self.keep.clear()
+
+
 def calc_reco_metrics(
     X_train, X_test,
     A, B,
@@ -368,6 +425,14 @@ def calc_reco_metrics_from_scores(
     row-major array (also one with a row stride, such as a column slice of a wider matrix) is passed as it is, anything else is
     copied once.  It is never modified, and a score at a train item is never looked at.
 
+    ``scores`` may also be a ``torch.Tensor`` of dtype float16, bfloat16, float32 or float64.  A float16 / bfloat16 tensor is read
+    where it lies, every score widened exactly to float32 on the device (``include/recometrics_hip_half.h``), and the result is
+    float32: the same values the call returns for the tensor converted to float32, for half the memory and half the upload.  A CPU
+    tensor goes through the host entries without a copy (``stride(1) == 1`` keeps its row stride, anything else is made contiguous
+    once); a GPU tensor goes through the device entries on its own device and on torch's current stream there, which is
+    synchronised before the result comes back in the usual form.  A NumPy ``float16`` array keeps going through float64, as every
+    NumPy dtype but float32 does: ``torch.from_numpy(x)`` selects the 16-bit path.
+
     There is no ``break_ties_with_noise`` and no ``seed``: the reference's tie noise exists to break the ties of a factor model
     that has not learned anything (all scores equal), and the caller of this function owns the scores -- equal scores are ordered
     by item id, the rule ``calc_reco_metrics(..., break_ties_with_noise=False)`` uses, and for scores that ARE ``A @ B.T`` as the
@@ -376,7 +441,8 @@ def calc_reco_metrics_from_scores(
     requested = _requested_metrics(locals())
     from scipy.sparse import issparse
 
-    _fail_if(not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
+    torch = _torch_if_tensor(scores)
+    _fail_if(torch is None and not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
     _fail_if(scores.ndim != 2, "'scores' must be a 2-dimensional array.")
     _fail_if(not issparse(X_test), "'X_test' must be a sparse matrix.")
     n_users, n_items = X_test.shape
@@ -385,8 +451,9 @@ def calc_reco_metrics_from_scores(
     _fail_if(0 in (n_users, n_items), "Input matrices cannot be empty.")
     _fail_if(X_test.data.shape[0] == 0, "'X_test' is empty.")
     _fail_if(tuple(scores.shape) != (n_users, n_items), "'scores' and 'X_test' must have the same shape.")
-    _fail_if(scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
-    dtype = np.float32 if scores.dtype == np.float32 else np.float64
+    kind = _tensor_kind(torch, scores) if torch else None
+    _fail_if(kind is None if torch else scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
+    dtype = (np.float64 if kind is np.float64 else np.float32) if torch else np.float32 if scores.dtype == np.float32 else np.float64
 
     X_train, consider_cold_start = _train_or_empty(X_train, X_test, dtype, consider_cold_start)
     _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
@@ -408,8 +475,30 @@ def calc_reco_metrics_from_scores(
 
     # ---- everything above raises before the library is touched ----
     split = _split_arrays(X_train, X_test, n_users, dtype)
-    S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
+    if torch and scores.is_cuda:
+        want = {short: requested[name] for name, short, _ in _METRICS}
+        arrays = _binding._metric_outs(None, want, n_users, k, bool(cumulative), dtype)
+        call = _DeviceCall(torch, scores, kind)
+        on_device = [call.empty(a.size) if a.size else None for a in arrays]
+        train_p, train_i, test_p, test_i, test_v = split
+        call.run(_binding.calc_metrics_scores_device, _binding.calc_metrics_scores_half_device,
+                 train_p=call.put(train_p), train_i=call.put(train_i), nnz_train=int(train_i.shape[0]),
+                 test_p=call.put(test_p), test_i=call.put(test_i), test_v=call.put(test_v), nnz_test=int(test_i.shape[0]),
+                 k_metrics=k, outs=[t.data_ptr() if t is not None else 0 for t in on_device], cumulative=bool(cumulative),
+                 consider_cold_start=bool(consider_cold_start), min_items_pool=min_items_pool, min_pos_test=min_pos_test)
+        for a, t in zip(arrays, on_device):
+            if t is not None:
+                a.reshape(-1)[:] = t.cpu().numpy()
+        return _metrics_result(arrays, None, None, k, as_df, cumulative, rename_k)
     want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
+    if isinstance(kind, str):
+        S, lds = _row_major_with_ld(_cpu_tensor_as_array(torch, scores, kind))
+        arrays = _binding.calc_metrics_scores_half(
+            S, lds, *split, k, want, bool(cumulative), bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, outs=outs)
+        return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
+    if torch:
+        scores = _cpu_tensor_as_array(torch, scores, kind)
+    S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
     arrays = _binding.calc_metrics_scores(
         S, lds, *split, k, want, bool(cumulative), bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, outs=outs)
     return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
@@ -474,7 +563,11 @@ def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_sc
 
     ``scores``: 2-d numeric NumPy array ``[users, items]``, evaluated in float32 only when it is float32, otherwise in float64; a
     row-major array (also one with a row stride, such as a column slice of a wider matrix) is passed as it is, anything else is
-    copied once.  It is never modified, and a score at an excluded item is never looked at.  ``X_train``: optional sparse
+    copied once.  It is never modified, and a score at an excluded item is never looked at.  Or a ``torch.Tensor`` of dtype float16,
+    bfloat16, float32 or float64, on the CPU or on a GPU, as in :func:`calc_reco_metrics_from_scores`: 16-bit scores are read where
+    they lie and widened exactly to float32 (list scores come back in float32), a GPU tensor is served on its device and on torch's
+    current stream, ``users`` is gathered there.  A NumPy ``float16`` array keeps going through float64; ``torch.from_numpy(x)``
+    selects the 16-bit path.  ``X_train``: optional sparse
     user-item matrix of the items to leave out per user (any SciPy format, int32 or int64 indices; never modified), ``None`` leaves
     nothing out.  ``users``: optional integer array -- lists for these rows of ``scores`` / ``X_train`` only, in this order (the
     rows are gathered once).  Order: score descending, then item id ascending; ``-0.0`` and ``+0.0`` are equal and come out as
@@ -482,9 +575,11 @@ def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_sc
 
     Returns ``(ids, scores, status)`` shaped and coded as :func:`recommend_topk` returns them.
     """
-    _fail_if(not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
+    torch = _torch_if_tensor(scores)
+    _fail_if(torch is None and not isinstance(scores, np.ndarray), "'scores' must be a NumPy array.")
     _fail_if(scores.ndim != 2, "'scores' must be a 2-dimensional array.")
-    _fail_if(scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
+    kind = _tensor_kind(torch, scores) if torch else None
+    _fail_if(kind is None if torch else scores.dtype.kind not in "fiub", "'scores' must be a numeric array.")
     n_users, n_items = scores.shape
     _fail_if(n_items == 0, "Input matrices cannot be empty.")
     _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
@@ -495,13 +590,26 @@ def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_sc
         _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
         _fail_if(tuple(X_train.shape) != (n_users, n_items), "'scores' and 'X_train' must have the same shape.")
     users = _user_selection(users, n_users, "scores")
-    dtype = np.float32 if scores.dtype == np.float32 else np.float64
+    dtype = (np.float64 if kind is np.float64 else np.float32) if torch else np.float32 if scores.dtype == np.float32 else np.float64
 
     # ---- everything above raises before the library is touched ----
-    if users is not None:
-        scores = scores[users]                               # (the one gather: a new row-major array)
+    if users is not None:                                    # (the one gather: a new row-major array; a tensor's on its own device)
+        scores = scores[torch.from_numpy(users).to(scores.device)] if torch else scores[users]
     excl_p, excl_i = _exclusion_csr(X_train, users)
     if scores.shape[0] == 0:
         return _no_lists(k, dtype, return_scores)
+    if torch and scores.is_cuda:
+        call = _DeviceCall(torch, scores, kind)
+        m = scores.shape[0]
+        idx, sc, st = call.empty((m, k), torch.int32), call.empty((m, k)) if return_scores else None, call.empty((m,), torch.int32)
+        call.run(_binding.recommend_scores_device, _binding.recommend_scores_half_device,
+                 excl_p=call.put(excl_p), excl_i=call.put(excl_i), nnz_excl=0 if excl_i is None else int(excl_i.shape[0]), k_top=k,
+                 idx=idx.data_ptr(), score=sc.data_ptr() if return_scores else 0, status=st.data_ptr())
+        return idx.cpu().numpy(), sc.cpu().numpy() if return_scores else None, st.cpu().numpy()
+    if isinstance(kind, str):
+        S, lds = _row_major_with_ld(_cpu_tensor_as_array(torch, scores, kind))
+        return _binding.recommend_scores_half(S, lds, excl_p, excl_i, k, bool(return_scores))
+    if torch:
+        scores = _cpu_tensor_as_array(torch, scores, kind)
     S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
     return _binding.recommend_scores(S, lds, excl_p, excl_i, k, bool(return_scores))

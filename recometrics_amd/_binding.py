@@ -67,6 +67,12 @@ SIGNATURES.update({
     "rm_csr_sort_rows": ((("indptr", _vp), ("indices", _vp), ("values", _vp), ("value_bytes", _i32), ("m", _i32), ("nthreads", _i32)), _ci),
 })
 EXPORTS = tuple(SIGNATURES)
+# include/recometrics_hip_half.h: the four from-scores entries with S in IEEE binary16 ("f16") / bfloat16 ("bf16") bit patterns; every
+# other array is the _f32 entry's, so the parameters are the same rows
+HALF_KINDS = ("f16", "bf16")
+HALF_SIGNATURES = {"rm_" + request + "_scores" + form + "_" + kind: (pieces(_SCORES, host), _ci)
+                   for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
+                   for kind in HALF_KINDS}
 # test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
 TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
@@ -79,10 +85,10 @@ def lib_path():
     return _LIB_PATH
 
 
-def _declare(lib, names):
-    """gives the symbols `names` of a loaded library the types SIGNATURES states"""
+def _declare(lib, names, table=None):
+    """gives the symbols `names` of a loaded library the types SIGNATURES (or `table`) states"""
     for name in names:
-        params, restype = SIGNATURES[name]
+        params, restype = (table or SIGNATURES)[name]
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = [ctype for _, ctype in params], restype
     return lib
@@ -96,7 +102,7 @@ def load():
             raise HipLibraryMissing(
                 "recometrics_amd: %s is missing -- build it with `python -m recometrics_amd.build` "
                 "(there is no CPU fallback)" % _LIB_PATH)
-        _lib = _declare(C.CDLL(_LIB_PATH), SIGNATURES)
+        _lib = _declare(_declare(C.CDLL(_LIB_PATH), SIGNATURES), HALF_SIGNATURES, HALF_SIGNATURES)
         for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -249,10 +255,14 @@ def csr_sort_rows(indptr, indices, data, nthreads=0):
 
 
 def _invoke(entry, dtype, **values):
-    """Calls `entry`'s symbol for `dtype` with `values` given by the header's parameter names, in the order SIGNATURES states; a
-    status other than 0 raises (`_raise`).  A missing name is a KeyError and an unknown one a TypeError, both before the call."""
-    name = entry + ("_f32" if dtype == np.float32 else "_f64")
-    params = SIGNATURES[name][0]
+    """Calls `entry`'s symbol for `dtype` (or, "f16" / "bf16", its symbol of HALF_SIGNATURES) with `values` given by the header's
+    parameter names, in the order SIGNATURES states; a status other than 0 raises (`_raise`).  A missing name is a KeyError and an unknown one a TypeError, both before the call."""
+    if dtype in HALF_KINDS:
+        name = entry + "_" + dtype
+        params = HALF_SIGNATURES[name][0]
+    else:
+        name = entry + ("_f32" if dtype == np.float32 else "_f64")
+        params = SIGNATURES[name][0]
     args = [values[param] for param, _ in params]
     if len(values) != len(params):
         raise TypeError("%s has no parameter %s" % (name, ", ".join(sorted(set(values) - {param for param, _ in params}))))
@@ -317,6 +327,52 @@ def calc_metrics_scores_device(dtype, S, lds, m, n, train_p, train_i, nnz_train,
     `outs` is a sequence of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
     _invoke("rm_calc_metrics_scores_dev", dtype, S=_dp(S), lds=lds, m=m, n=n, nnz_train=nnz_train, nnz_test=nnz_test, stream=_dp(stream),
             **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+
+
+def half_kind(S):
+    """"f16" for a float16 array, "bf16" for a uint16 one (bfloat16 bit patterns: NumPy has no such dtype)"""
+    if S.dtype == np.float16:
+        return "f16"
+    if S.dtype == np.uint16:
+        return "bf16"
+    raise TypeError("16-bit scores are a float16 array, or bfloat16 bit patterns as uint16 (got %s)" % S.dtype)
+
+
+def calc_metrics_scores_half(S, lds, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
+                             consider_cold_start, min_items_pool, min_pos_test, nthreads, outs=None):
+    """`calc_metrics_scores` for 16-bit scores (rm_calc_metrics_scores_f16 / _bf16): `S` [m, n] a float16 array, or bfloat16 bit
+    patterns as uint16, with leading dimension `lds` in 2-byte elements; `test_v` and the ten outputs are float32."""
+    m, n = S.shape
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, np.float32)
+    _invoke("rm_calc_metrics_scores", half_kind(S), S=_p(S), lds=lds, m=m, n=n, nthreads=nthreads,
+            **_metrics_values(_p, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+    return outs
+
+
+def calc_metrics_scores_half_device(kind, S, lds, m, n, train_p, train_i, nnz_train, test_p, test_i, test_v, nnz_test,
+                                    k_metrics, outs, cumulative=False, consider_cold_start=True,
+                                    min_items_pool=2, min_pos_test=1, stream=0):
+    """`calc_metrics_scores_device` for 16-bit scores: `kind` "f16" / "bf16" in the place of the dtype, everything else float32"""
+    assert kind in HALF_KINDS
+    _invoke("rm_calc_metrics_scores_dev", kind, S=_dp(S), lds=lds, m=m, n=n, nnz_train=nnz_train, nnz_test=nnz_test, stream=_dp(stream),
+            **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+
+
+def recommend_scores_half(S, lds, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
+    """`recommend_scores` for 16-bit scores (rm_recommend_scores_f16 / _bf16): `S` as in `calc_metrics_scores_half`; the list scores
+    are float32."""
+    m, n = S.shape
+    idx, sc, st = _list_outs(m, k_top, np.float32, return_scores)
+    _invoke("rm_recommend_scores", half_kind(S), S=_p(S), lds=lds, m=m, n=n, Xexcl_csr_p=_host_excl_p(excl_p), Xexcl_csr_i=_p(excl_i),
+            k_top=k_top, idx=_p(idx), score=_p(sc), status=_p(st), nthreads=int(nthreads))
+    return idx, sc, st
+
+
+def recommend_scores_half_device(kind, S, lds, m, n, excl_p, excl_i, nnz_excl, k_top, idx, score, status, stream=0):
+    """`recommend_scores_device` for 16-bit scores: `kind` "f16" / "bf16" in the place of the dtype, `score` float32"""
+    assert kind in HALF_KINDS
+    _invoke("rm_recommend_scores_dev", kind, S=_dp(S), lds=lds, m=m, n=n, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
+            nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
 
 
 def rank(A, B, train_p, train_i, test_p, test_i, k_metrics, break_ties_with_noise=False, consider_cold_start=True,

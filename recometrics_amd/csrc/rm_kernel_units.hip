@@ -10,6 +10,7 @@
 //               2  rm_noise.hpp, rm_scores.hpp, rm_rowtopk.hpp: tie noise, the score-matrix entries
 //               3  k_collect_topk, lane buffers of 512 and 1024 entries          x fp32 / fp64
 //               4  k_collect_topk, lane buffers of 4096 entries                  x fp32 / fp64
+//               5  rm_scores.hpp, rm_rowtopk.hpp with 16-bit scores (f16 / bf16 in, fp32 behind the load)
 #include <hip/hip_runtime.h>
 
 #if RM_KERNELS == 0
@@ -38,8 +39,12 @@
 #elif RM_KERNELS == 4
 #include "rm_finalize.hpp"
 #define RM_UNIT_KERNELS(X) RM_COLLECT4096_KERNELS_F64(X)
+#elif RM_KERNELS == 5
+#include "rm_scores.hpp"
+#include "rm_rowtopk.hpp"
+#define RM_UNIT_KERNELS(X) RM_SCORES_KERNELS_HALF(X) RM_ROWTOPK_KERNELS_HALF(X)
 #else
-#error "RM_KERNELS: 0 .. 4"
+#error "RM_KERNELS: 0 .. 5"
 #endif
 
 namespace rm {

@@ -1,4 +1,4 @@
-// rm_lib.hip -- host orchestration + the C-ABI of include/recometrics_hip.h  (gfx950 only).
+// rm_lib.hip -- host orchestration + the C-ABI of include/recometrics_hip.h and recometrics_hip_half.h  (gfx950 only).
 //
 // Host counterpart of reference src/recometrics.hpp:359-436 (prologue: clamps, scratch) and of the instantiation
 // shims src/recometrics_instantiated.cpp:30-143.  The reference's OpenMP loop over users (:428-437) becomes:
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/recometrics_hip.h"
+#include "../../include/recometrics_hip_half.h"
 #include "rm_device.hpp"
 #include "rm_prep.hpp"
 #include "rm_launch.hpp"
@@ -191,7 +192,7 @@ std::atomic<unsigned long long> g_ws_stamp{1};
     X(WS_O_POS_RANK, "o_pos_rank")              /* long long[nnz_test of the range] */ \
     X(WS_O_STATUS, "o_status")                  /* int[m] */ \
     X(WS_O_BLOCK, "o_block")                    /* T[block_size(largest batch)]: the metric block of a batch, [metric][users x width] (the finalisation) */ \
-    X(WS_IN_S0, "in_S0")                        /* T[largest batch][n]: the caller's score rows of a batch ... (HostRange's uploads) */ \
+    X(WS_IN_S0, "in_S0")                        /* T (or 16-bit: ScoreType) [largest batch][n]: the caller's score rows of a batch ... (HostRange's uploads) */ \
     X(WS_IN_S1, "in_S1")                        /* ... and of the next one, which travels meanwhile */ \
     X(WS_NOISE_FLAG_RANGE, "noise_flag_range")  /* int[m]: fp32 tie noise over several batches: the flags of the range (zeroed by plan_batches; the batches' first passes) */ \
     X(WS_NOISE_FLAG_RANGE_SNAP, "noise_flag_range_snap")  /* int[m]: ... when the LAST batch launches its sweep */ \
@@ -452,13 +453,17 @@ template <class T> struct Outputs {
 };
 // What a caller asked for: one metric or list call as the C-ABI states it.  Its pointers are HOST pointers in a host entry (HostRange
 // stages the arrays batch by batch) and DEVICE pointers in a device entry and in every Call.
+// The element type of a caller's score matrix: the call's own T, or 16-bit patterns (include/recometrics_hip_half.h; T is float then),
+// which the three kernels that read S widen in registers (rm_scores.hpp: ScoreSrc) -- nothing behind them knows.
+enum ScoreType { SCORE_SAME, SCORE_F16, SCORE_BF16 };
 template <class T> struct Request : Outputs<T> {
     // the score source: factors, or the caller's score matrix (rm_calc_metrics_scores_*, rm_recommend_scores_*): score of item i for user u =
     // S[u * lds + i]; there are then no factors (A, B null, k = 0) and no tie noise.  Every evaluated user is streamed: k_score_rows copies
     // its row of S, masked, where the sweep would have written it, k_pos_scores_given gathers the test items' scores, and the
     // finalisation is the factor call's.
     const T *A = nullptr; size_t lda = 0; const T *B = nullptr; size_t ldb = 0; int k = 0;
-    const T *S = nullptr; size_t lds = 0; bool scores = false;
+    const void *S = nullptr; ScoreType s_type = SCORE_SAME; size_t lds = 0; bool scores = false;      // (lds in elements of S)
+    size_t s_elem() const { return s_type == SCORE_SAME ? sizeof(T) : 2; }
     int m = 0, n = 0;
     const int *train_p = nullptr, *train_i = nullptr; long long nnz_train = 0;       // (lists: the exclusion matrix)
     const int *test_p = nullptr, *test_i = nullptr; const T *test_v = nullptr; long long nnz_test = 0;
@@ -505,6 +510,13 @@ struct PassRows {                                  // dense train rows handed ov
 template <class T> struct PassRole : PassSubset<T>, PassFlags, PassRows { PassKind kind = PASS_ORDINARY; };
 // one pass over the users of a request, or over a batch of them: the request (every pointer a DEVICE pointer), the call's identity
 // and the role of the pass
+// f(Src *): the kernels' source-element type of a request's S (rm_scores.hpp); the 16-bit types exist for T = float only
+template <class T, class F> void with_score_src(ScoreType st, F f)
+{
+    if (st == SCORE_SAME) return f((const T *)nullptr);
+    if constexpr (std::is_same<T, float>::value) return st == SCORE_F16 ? f((const F16Bits *)nullptr) : f((const BF16Bits *)nullptr);
+    throw RmError{RM_ERR_INVALID, "16-bit scores are evaluated in fp32"};
+}
 template <class T> struct Call : Request<T>, PassRole<T> {
     Call() = default;
     explicit Call(const Request<T> &r) : Request<T>(r) {}
@@ -1323,7 +1335,10 @@ struct Pipeline {
                 if (c.scores) {
                     // (the caller's scores: which test items are train items first -- S is never read at a train item --, then the gather)
                     hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
-                    hipLaunchKernelGGL(k_pos_scores_given<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, c.S, c.lds, (const int *)ent_user, (const unsigned char *)ent_masked);
+                    with_score_src<T>(c.s_type, [&](auto *src) {
+                        typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+                        hipLaunchKernelGGL((k_pos_scores_given<T, Src>), dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, (const Src *)c.S, c.lds, (const int *)ent_user, (const unsigned char *)ent_masked);
+                    });
                 } else {
                 hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pf, ent_user);
                 // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
@@ -1689,8 +1704,11 @@ struct Pipeline {
         if (c.scores) {
             // the caller's scores: k_score_rows in the sweep's place -- a block per user copies the user's row of S into its masked
             // score row and leaves the candidates' statistics (rm_scores.hpp); the "sweep" timing brackets this launch
-            ScoreRowArgs<T> ra{n, n_stream, stream_slot0, g.n_part, slot_user, c.train_p, c.train_i, c.S, c.lds, stream_scores, stream_ld, pst};
-            if (n_stream > 0) hipLaunchKernelGGL(k_score_rows<T>, dim3((unsigned)n_stream), dim3(SCORE_ROW_THREADS), 0, stream, ra);
+            if (n_stream > 0) with_score_src<T>(c.s_type, [&](auto *src) {
+                typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+                ScoreRowArgs<T, Src> ra{n, n_stream, stream_slot0, g.n_part, slot_user, c.train_p, c.train_i, (const Src *)c.S, c.lds, stream_scores, stream_ld, pst};
+                hipLaunchKernelGGL((k_score_rows<T, Src>), dim3((unsigned)n_stream), dim3(SCORE_ROW_THREADS), 0, stream, ra);
+            });
             check_launch(hipGetLastError());
             RM_TRACE_POINT("run: score rows enqueued");
             HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
@@ -1742,14 +1760,19 @@ struct Pipeline {
     void topk_rows()
     {
         HIP_CHECK(hipEventRecord(cx.ev[EV_PREP_END], stream));
-        RowTopkArgs<T> ra{n, K, c.train_p, c.train_i, c.S, c.lds, c.topk_idx, c.topk_score, c.status};
-        hipLaunchKernelGGL(k_topk_rows<T>, dim3((unsigned)m), dim3(SCORE_ROW_THREADS), 0, stream, ra);
+        const void *kernel = nullptr;
+        with_score_src<T>(c.s_type, [&](auto *src) {
+            typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+            RowTopkArgs<T, Src> ra{n, K, c.train_p, c.train_i, (const Src *)c.S, c.lds, c.topk_idx, c.topk_score, c.status};
+            hipLaunchKernelGGL((k_topk_rows<T, Src>), dim3((unsigned)m), dim3(SCORE_ROW_THREADS), 0, stream, ra);
+            kernel = (const void *)k_topk_rows<T, Src>;
+        });
         HIP_CHECK(hipGetLastError());
         RM_TRACE_POINT("run: row top-K enqueued");
         HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
         double *tm = cx.timings;
         hipFuncAttributes at{};
-        HIP_CHECK(hipFuncGetAttributes(&at, (const void *)k_topk_rows<T>));
+        HIP_CHECK(hipFuncGetAttributes(&at, kernel));
         tm[4] = 1; tm[5] = 1; tm[6] = m; tm[7] = (double)at.sharedSizeBytes;
         cx.timed_slots = hp.n_slots; cx.total_slots = hp.n_slots;
     }
@@ -2253,11 +2276,14 @@ inline void print_host_trace(int n_batches, const std::vector<std::pair<const ch
 // The caller's scores (`scores`): a user of a batch costs its row of S in each of the two upload buffers (ws.get rounds an allocation
 // up by an eighth) and its masked row, which run() wants inside a third of what is then free: b (2.25 + 3) rows <= free memory, taken
 // with a margin for the top-K scratch; what the workspace already holds of exactly these buffers counts as free.
-template <class T> long long batch_users_max(const Workspace &ws, int n, int k, int K, bool scores = false)
+// 16-bit scores (`s_elem` = 2 with T = float): the two upload rows are half as large, the masked row is not -- b (1.125 + 3) rows with
+// the same margin, 5.5 rows in the place of 7.
+template <class T> long long batch_users_max(const Workspace &ws, int n, int k, int K, bool scores = false, size_t s_elem = sizeof(T))
 {
     if (scores) {
         const long long row = score_row_stride(n) * (long long)sizeof(T);
-        long long batch = free_plus_owned(ws, {WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO, WS_IN_S0, WS_IN_S1}) / (7 * row);
+        const long long per_user = s_elem == sizeof(T) ? 7 * row : (8 * row + 6 * score_row_stride(n) * (long long)s_elem) / 2;
+        long long batch = free_plus_owned(ws, {WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO, WS_IN_S0, WS_IN_S1}) / per_user;
         if (g_sw.stream_budget_mb >= 0) batch = std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row);
         if (g_sw.batch_users > 0) batch = std::min<long long>(batch, (long long)g_sw.batch_users);
         return std::max<long long>(1, std::min<long long>(batch, 1 << 20));
@@ -2375,7 +2401,7 @@ template <class T> struct HostRange {
     const MetricLayout lay;                                           // (per: values per user of the eight top-K metrics)
     // stage_inputs()
     long long tr0 = 0, te0 = 0, nnz_tr = 0, nnz_te = 0;
-    T *dS[2] = {nullptr, nullptr}; const T *cur_S = nullptr;           // the caller's scores: upload buffers of the batches, the one of the batch being enqueued
+    void *dS[2] = {nullptr, nullptr}; const void *cur_S = nullptr;        // the caller's scores: upload buffers of the batches, the one of the batch being enqueued
     T *dB = nullptr, *dA = nullptr, *dtev = nullptr; int *dtrp = nullptr, *dtep = nullptr, *dtri = nullptr, *dtei = nullptr;
     std::vector<int> rb;                                              // rebased index pointers (only when the range does not start at 0)
     const int *trp = nullptr, *tep = nullptr;
@@ -2443,7 +2469,7 @@ template <class T> struct HostRange {
     void plan_batches()
     {
         const bool forced = g_sw.batch_users > 0;                        // tests: equal batches of this size
-        cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K, h.scores), forced);
+        cuts = batch_cuts(m, batch_users_max<T>(ws, n, k, K, h.scores, h.s_elem()), forced);
         n_batches = (int)cuts.size() - 1;
         long long mb_max = 0;
         for (int bi = 0; bi < n_batches; bi++) mb_max = std::max(mb_max, cuts[bi + 1] - cuts[bi]);
@@ -2469,7 +2495,7 @@ template <class T> struct HostRange {
         two_ctx = ctxs[1] != ctxs[0];
         // the caller's scores: the rows of a batch, dense, in one of two buffers -- batch i + 1 travels while batch i runs, and with one
         // context batch i - 1 has been waited for by then
-        if (h.scores) for (int i = 0; i < std::min(n_batches, 2); i++) dS[i] = ws.array<T>(i ? WS_IN_S1 : WS_IN_S0, (size_t)mb_max * (size_t)n);
+        if (h.scores) for (int i = 0; i < std::min(n_batches, 2); i++) dS[i] = ws.array<char>(i ? WS_IN_S1 : WS_IN_S0, (size_t)mb_max * (size_t)n * h.s_elem());
         // fp32 tie noise over several batches: every batch runs its first pass only and flags the users the noise can touch in its
         // slice of `range_flag`; ONE exact pass over the flagged users of the whole range follows the last batch.  (Per batch, the
         // exact pass costs two waits on the host -- for the flags, for its own plan -- during which the next batch is not enqueued:
@@ -2490,9 +2516,10 @@ template <class T> struct HostRange {
     {
         const long long b0 = cuts[bi], b1 = cuts[bi + 1];
         if (h.scores) {
-            const T *src = h.S + ((size_t)u0 + b0) * h.lds;
-            if (h.lds == (size_t)n) HIP_CHECK(hipMemcpyAsync(dS[bi & 1], src, sizeof(T) * (size_t)(b1 - b0) * n, hipMemcpyHostToDevice, up));
-            else HIP_CHECK(hipMemcpy2DAsync(dS[bi & 1], sizeof(T) * n, src, sizeof(T) * h.lds, sizeof(T) * n, (size_t)(b1 - b0), hipMemcpyHostToDevice, up));
+            const size_t es = h.s_elem();
+            const char *src = (const char *)h.S + ((size_t)u0 + b0) * h.lds * es;
+            if (h.lds == (size_t)n) HIP_CHECK(hipMemcpyAsync(dS[bi & 1], src, es * (size_t)(b1 - b0) * n, hipMemcpyHostToDevice, up));
+            else HIP_CHECK(hipMemcpy2DAsync(dS[bi & 1], es * n, src, es * h.lds, es * n, (size_t)(b1 - b0), hipMemcpyHostToDevice, up));
         } else
         if (h.lda == (size_t)k) HIP_CHECK(hipMemcpyAsync(dA + (size_t)b0 * k, h.A + ((size_t)u0 + b0) * k, sizeof(T) * (size_t)(b1 - b0) * k, hipMemcpyHostToDevice, up));
         else HIP_CHECK(hipMemcpy2DAsync(dA + (size_t)b0 * k, sizeof(T) * k, h.A + ((size_t)u0 + b0) * h.lda, sizeof(T) * h.lda, sizeof(T) * k, (size_t)(b1 - b0),
@@ -2983,6 +3010,13 @@ template <class T> Request<T> from_scores(const T *S, size_t lds)
     r.S = S; r.lds = lds; r.scores = true;
     return r;
 }
+// 16-bit scores (recometrics_hip_half.h): bit patterns, lds in 2-byte elements; the request is an fp32 request otherwise
+inline Request<float> from_scores_half(const uint16_t *S, size_t lds, ScoreType type)
+{
+    Request<float> r;
+    r.S = S; r.s_type = type; r.lds = lds; r.scores = true;
+    return r;
+}
 template <class T>
 Request<T> metrics_request(Request<T> r, int m, int n, const int *train_p, const int *train_i, long long nnz_train,
                            const int *test_p, const int *test_i, const T *test_v, long long nnz_test,
@@ -3179,6 +3213,67 @@ extern "C" int rm_recommend_scores_dev_##SUFFIX(                                
 
 RM_RECOMMEND_SCORES_ENTRY(f32, float)
 RM_RECOMMEND_SCORES_ENTRY(f64, double)
+
+// ---- 16-bit score matrices (include/recometrics_hip_half.h): the four from-scores entries of fp32 with S in IEEE binary16 / bfloat16 ----
+#define RM_HALF_ENTRY(SUFFIX, TYPE)                                                                                     \
+extern "C" int rm_calc_metrics_scores_##SUFFIX(                                                                         \
+    const uint16_t *S, size_t lds, int32_t m, int32_t n,                                                                \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,                                                           \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const float *Xtest_csr,                                     \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    float *p_at_k, float *tp_at_k, float *r_at_k, float *ap_at_k, float *tap_at_k, float *ndcg_at_k, float *hit_at_k,   \
+    float *rr_at_k, float *roc_auc, float *pr_auc, int consider_cold_start, int32_t min_items_pool,                     \
+    int32_t min_pos_test, int32_t nthreads)                                                                             \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        host_entry<float>(metrics_request<float>(from_scores_half(S, lds, TYPE), m, n, Xtrain_csr_p, Xtrain_csr_i, 0,   \
+                                         Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0, k_metrics, cumulative, 0,              \
+                                         {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,     \
+                                          roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, 0),      \
+                      nthreads);                                                                                        \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_calc_metrics_scores_dev_##SUFFIX(                                                                     \
+    const uint16_t *S, size_t lds, int32_t m, int32_t n,                                                                \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,                                        \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const float *Xtest_csr, int64_t nnz_test,                   \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    float *p_at_k, float *tp_at_k, float *r_at_k, float *ap_at_k, float *tap_at_k, float *ndcg_at_k, float *hit_at_k,   \
+    float *rr_at_k, float *roc_auc, float *pr_auc, int consider_cold_start, int32_t min_items_pool,                     \
+    int32_t min_pos_test, void *stream)                                                                                 \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        dev_entry<float>(metrics_request<float>(from_scores_half(S, lds, TYPE), m, n, Xtrain_csr_p, Xtrain_csr_i,       \
+                                        nnz_train, Xtest_csr_p, Xtest_csr_i, Xtest_csr, nnz_test, k_metrics,            \
+                                        cumulative, 0,                                                                  \
+                                        {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,      \
+                                         roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, 0),       \
+                     stream);                                                                                           \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_scores_##SUFFIX(                                                                            \
+    const uint16_t *S, size_t lds, int32_t m, int32_t n,                                                                \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
+    int32_t *idx, float *score, int32_t *status, int32_t nthreads)                                                      \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        host_entry<float>(lists_request<float>(from_scores_half(S, lds, TYPE), m, n, Xexcl_csr_p, Xexcl_csr_i, 0,       \
+                                               k_top, idx, score, status), nthreads);                                   \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_scores_dev_##SUFFIX(                                                                        \
+    const uint16_t *S, size_t lds, int32_t m, int32_t n,                                                                \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
+    int32_t *idx, float *score, int32_t *status, void *stream)                                                          \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        dev_entry<float>(lists_request<float>(from_scores_half(S, lds, TYPE), m, n, Xexcl_csr_p, Xexcl_csr_i,           \
+                                              nnz_excl, k_top, idx, score, status), stream);                            \
+    });                                                                                                                 \
+}
+
+RM_HALF_ENTRY(f16, SCORE_F16)
+RM_HALF_ENTRY(bf16, SCORE_BF16)
 
 extern "C" int rm_debug_scores_f32(const float *A, size_t lda, const float *B, size_t ldb, int32_t m, int32_t n, int32_t k, float *out)
 {

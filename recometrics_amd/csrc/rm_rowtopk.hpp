@@ -13,6 +13,8 @@
 //     It also compacts as soon as the buffer holds max(4 K, 256) pairs: a small network early is cheaper than a full one later;
 //   * behind the row the same network sorts what is left; min(K, C) entries, -1 / NaN behind them and the status go straight to the
 //     caller's arrays, consecutive threads on consecutive addresses.
+// 16-bit scores (Src = F16Bits / BF16Bits, T = float: rm_scores.hpp): a 16-byte load is 8 scores, which walk_score_row hands over in two
+// pieces of four with a step in front of each -- ROW_TOPK_PASS, ROW_TOPK_CAP and `early` are the fp32 kernel's.
 // The validity statistics (max / min / has-NaN of the CANDIDATES, -0 as +0) are reduced on the way as k_score_rows does: status 2
 // overrides the list.  A score at an excluded item takes part in nothing.
 #pragma once
@@ -78,21 +80,25 @@ __device__ __forceinline__ void topk_sort_desc(TopkPairs<T> &buf, const int cnt)
         }
 }
 
-template <class T> struct RowTopkArgs {
+template <class T, class Src = T> struct RowTopkArgs {
     int n, K;
     const int *train_p, *train_i;                  // the exclusion rows, validated and sorted (run(): the plan stage)
-    const T *S; size_t lds;
+    const Src *S; size_t lds;
     int *idx; T *score; int *status;               // the caller's arrays [m][K], [m][K] (may be null), [m]
 };
 
 // A block per user of the call.
-template <class T>
-__global__ __launch_bounds__(SCORE_ROW_THREADS) void k_topk_rows(RowTopkArgs<T> a)
+template <class T, class Src = T>
+__global__ __launch_bounds__(SCORE_ROW_THREADS) void k_topk_rows(RowTopkArgs<T, Src> a)
 {
     typedef TopkPairs<T> B;
     typedef typename B::Pair Pair;
     typedef typename ScoreVec<T>::Aligned VT;
     constexpr int VE = 16 / (int)sizeof(T), CAP = ROW_TOPK_CAP, PASS = row_topk_pass<T>();
+    // (16-bit scores: walk_score_row hands a 16-byte load over in two pieces with a step in front of each, so a step is VE scores per
+    // thread as in the fp32 call and the buffer and `early` stay what they are)
+    static_assert(16 / (int)sizeof(Src) == VE * ScoreSrc<T, Src>::PIECES && ROW_TOPK_MAX_K + PASS <= CAP,
+                  "the K survivors of a compaction and one step's appends must fit the buffer");
     __shared__ B buf;
     __shared__ unsigned bitmap[SCORE_CHUNK / 32 + 2];
     __shared__ int sh_taken, sh_count, sh_status;
@@ -122,7 +128,7 @@ __global__ __launch_bounds__(SCORE_ROW_THREADS) void k_topk_rows(RowTopkArgs<T> 
             const int at = __builtin_amdgcn_readfirstlane(base) + rank;
             if (at < CAP) buf.set(at, p);                            // (never false: see `pass`)
         };
-        walk_score_row<T>(a.S + (size_t)u * a.lds, n, a.train_i, tr0, tr1, bitmap, &sh_taken,
+        walk_score_row<T, Src>(a.S + (size_t)u * a.lds, n, a.train_i, tr0, tr1, bitmap, &sh_taken,
             offer,
             [&](int i, const VT &x, unsigned mb) {
                 #pragma unroll
@@ -160,7 +166,9 @@ __global__ __launch_bounds__(SCORE_ROW_THREADS) void k_topk_rows(RowTopkArgs<T> 
 // ---- every instantiation of this header's kernel template (rm_kernel_units.hpp) -----------------------------------------
 #define RM_ROWTOPK_KERNELS_F32(X) X(k_topk_rows<float>)
 #define RM_ROWTOPK_KERNELS_F64(X) X(k_topk_rows<double>)
+#define RM_ROWTOPK_KERNELS_HALF(X) X(k_topk_rows<float, F16Bits>) X(k_topk_rows<float, BF16Bits>)
 RM_ROWTOPK_KERNELS_F32(RM_EXTERN_KERNEL)
 RM_ROWTOPK_KERNELS_F64(RM_EXTERN_KERNEL)
+RM_ROWTOPK_KERNELS_HALF(RM_EXTERN_KERNEL)
 
 } // namespace rm
