@@ -317,6 +317,22 @@ int rm_get_timings(double *out, int n);
 /* Releases the cached device workspace of the current device. */
 int rm_release_workspace(void);
 
+/* Test hooks of RM_DEBUG_WS_GUARD: while that switch is set, every workspace buffer the library allocates lies
+ * between two red zones of a fixed pattern -- the tail zone starts at the byte count of the largest request the allocation has served --
+ * and its payload is poisoned.
+ *   rm_debug_ws_check  synchronises the current device and compares the zones of every live guarded buffer of its contexts with the
+ *                      pattern (of a tail zone longer than 1 MiB the first 1 MiB).  Returns the number of damaged zones, -1 on an
+ *                      error (rm_last_error).  msg (cap bytes, may be NULL) receives "checked <buffers> buffers, <zones> damaged
+ *                      zones" and then one line per damaged zone: "damaged: buffer=<name> slot=<context slot> side=<head|tail>
+ *                      first=<offset> last=<offset> requested=<bytes> zone=<bytes>", the offsets of the first and the last damaged
+ *                      byte counted from the payload's start (head: -256 .. -1) or from its end (tail: 0 ..)
+ *   rm_debug_ws_poke   the positive control: overwrites ONE byte of a zone of the live guarded buffer `buffer_id` (its place in the
+ *                      list RM_WS_BUFFERS of csrc/rm_lib.hip): tail = 0 the head zone, else the tail zone; offset >= 0 from the zone's
+ *                      first byte, < 0 from behind its last one.  It touches only memory allocated as a zone.  RM_ERR_INVALID when
+ *                      no such buffer is live or the offset lies outside the zone */
+int rm_debug_ws_check(char *msg, int cap);
+int rm_debug_ws_poke(int buffer_id, int tail, int offset);
+
 /* ---- train / test splitting (host only; "next" row N3) ------------------------------------------------------------
  * Replaces split_data_selected_users_{float,double}, split_data_separate_users_* and split_data_joined_users_*
  * (src/recometrics_signatures.hpp:100-220), which hand their results back in std::vector& parameters; a C-ABI returns an

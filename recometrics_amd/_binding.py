@@ -61,6 +61,8 @@ SIGNATURES.update({
                             + (("out6", C.POINTER(_ci)),), _ci),
     "rm_debug_supported_ng": ((("elem_bytes", _ci), ("k", _ci)), _ci),
     "rm_debug_sweep_launched": ((("elem_bytes", _ci), ("counts", C.POINTER(_ci)), ("cap", _ci)), _ci), "rm_debug_sweep_launched_reset": ((), None),
+    "rm_debug_ws_check": ((("msg", C.POINTER(C.c_char)), ("cap", _ci)), _ci),
+    "rm_debug_ws_poke": ((("buffer_id", _ci), ("tail", _ci), ("offset", _ci)), _ci),
     "rm_split_size": ((("result", _vp), ("which", _ci)), _i64), "rm_split_copy": ((("result", _vp), ("which", _ci), ("dst", _vp)), _ci),
     "rm_split_free": ((("result", _vp),), None), "rm_split_last_error": ((), C.c_char_p),
     "rm_csr_rows_sorted": ((("indptr", _vp), ("indices", _vp), ("m", _i32), ("nthreads", _i32)), _ci),
@@ -228,6 +230,26 @@ def set_list_ids(ids):
     lib = load()
     ids = np.ascontiguousarray(ids, dtype=np.int32)
     rc = lib.rm_debug_set_list_ids(ids.ctypes.data_as(C.POINTER(_i32)), ids.shape[0], ids.shape[1])
+    if rc:
+        _raise(lib, rc)
+
+
+def ws_check():
+    """Test hook (rm_debug_ws_check) of RM_DEBUG_WS_GUARD: (damaged zones, buffers checked, the report's text) of the current device's
+    workspace buffers."""
+    lib = load()
+    buf = C.create_string_buffer(1 << 16)
+    damaged = lib.rm_debug_ws_check(buf, len(buf))
+    if damaged < 0:
+        _raise(lib, 2)
+    text = buf.value.decode()
+    return damaged, int(text.split()[1]), text
+
+
+def ws_poke(buffer_id, tail, offset):
+    """Test hook (rm_debug_ws_poke): damages one byte of a red zone of the live guarded buffer `buffer_id`."""
+    lib = load()
+    rc = lib.rm_debug_ws_poke(int(buffer_id), int(bool(tail)), int(offset))
     if rc:
         _raise(lib, rc)
 

@@ -56,7 +56,7 @@ struct RmError { int code; std::string msg; };
 // tests/test_switches_cpu.py compares this table with that list); nothing here turns a feature of the call off.
 struct Switches {
     bool no_train_bits, no_spec, no_side, ext_topk, no_test_mask, hbm_lists, nsub2, no_pending, no_pos_beside, no_seed, rank_generic,
-         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk, no_split_cache, no_warm_bounds;
+         no_fused_auc, no_defer_auc, noise_sequential, one_context, noise_per_batch, host_trace, no_pos_flat, no_row_topk, no_split_cache, no_warm_bounds, ws_guard;
     long long free_mb, stream_budget_mb, noise_budget_mb, lane_cap_min, lane_min_k, lane_cap_set, sample_seed, split_cache_mb;      // -1 = not set
     unsigned long long epoch = 0;                                              // counts load(): what a context keeps of a split was decided under one set of switches
     double batch_users;                                                        // 0 = not set
@@ -83,6 +83,7 @@ struct Switches {
         no_split_cache = on("RM_DEBUG_NO_SPLIT_CACHE");        // every call plans, validates and builds its split's tables itself (A/B timing, the tests' reference path)
         split_cache_mb = num("RM_SPLIT_CACHE_MB");              // the largest split (bytes of its five arrays) a context keeps copies of; 0 = none
         no_warm_bounds = on("RM_DEBUG_NO_WARM_BOUNDS");        // a call on the kept split seeds its top-K bounds as a first call does: no k_hint_bounds (A/B timing, the tests' reference path)
+        ws_guard = on("RM_DEBUG_WS_GUARD");                    // buffers allocated from now on lie between red zones, their payload poisoned (Workspace; tests)
         epoch++;
         const char *b = getenv("RM_BATCH_USERS"); batch_users = b ? atof(b) : 0.0;
         const char *s = getenv("RM_DEBUG_SPLITS"); splits = s ? s : "";
@@ -210,30 +211,101 @@ enum WsBuf { RM_WS_BUFFERS(RM_WS_ID) WS_COUNT };
 constexpr const char *WS_NAMES[WS_COUNT] = { RM_WS_BUFFERS(RM_WS_NAME) };
 #undef RM_WS_ID
 #undef RM_WS_NAME
+// RM_DEBUG_WS_GUARD (tests): a buffer allocated while the switch is set lies between two red zones, and its payload is poisoned:
+//     [ head zone, WS_ZONE bytes ][ payload: the bytes asked for ][ tail zone: the slack of an ordinary allocation + WS_ZONE bytes ]
+// The tail zone starts at the byte count the request states, so a store one element past it is seen; whatever lies inside an ordinary
+// allocation -- `cap` bytes from the pointer handed out -- lies inside a guarded one too (an over-read stays as harmless as it was).
+// The allocation policy is the ordinary one: a later request that fits the buffer gets it as it is.  Where that request is LARGER than
+// every one before (the batches of a host call, the next call at a few more slots: it fits the slack), the payload grows into the tail
+// zone: the part taken over is checked first, then poisoned (guard_grow) -- the stores of that request's kernels are no damage.
+// The zones repeat WS_RED, the payload the word of its request: WS_POISON_FLOAT behind ws.array<float / double> (a quiet NaN as a
+// float and, in pairs, as a double; not the library's own 0xFFFFFFFF), WS_POISON_INT behind everything else -- small on purpose: a
+// counter or flag nobody zeroed is visibly wrong, an index nobody wrote stays in range or one element behind it, inside the zone.
+// Every byte of an allocation is byte (offset & 3) of its region's word, offsets counted from the 256-byte-aligned allocation.
+// rm_debug_ws_check compares the zones with WS_RED, rm_debug_ws_poke damages one byte of one (both at the end of this file).
+constexpr size_t WS_ZONE = 256, WS_CHECK_MAX = size_t(1) << 20;
+constexpr unsigned WS_RED = 0xC3A55A3Cu, WS_POISON_FLOAT = 0x7FF87FF8u, WS_POISON_INT = 0x00000001u;
+inline unsigned char ws_pattern_byte(unsigned word, size_t offset) { return (unsigned char)(word >> (8 * (offset & 3))); }
+// the words [w0, w1) of a guarded allocation: `poison` where a byte lies in [lo, hi) (offsets in the allocation); every other byte of
+// those words becomes WS_RED (`fresh`: the allocation's first fill) or stays what it is (a payload that grows into its tail zone)
+__global__ void k_ws_guard_fill(unsigned *base, size_t w0, size_t w1, size_t lo, size_t hi, unsigned poison, bool fresh)
+{
+    for (size_t w = w0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < w1; w += (size_t)gridDim.x * blockDim.x) {
+        const size_t o = 4 * w;
+        unsigned v = fresh ? WS_RED : base[w];
+        for (int b = 0; b < 4; b++)
+            if (o + b >= lo && o + b < hi) v = (v & ~(0xFFu << (8 * b))) | (poison & (0xFFu << (8 * b)));
+        base[w] = v;
+    }
+}
 struct Workspace {
-    struct Buf { void *ptr = nullptr; size_t bytes = 0; unsigned long long stamp = 0; };
+    // `bytes`: what the buffer serves without a new allocation (the request that allocated it and its slack); `real`: what hipMalloc
+    // gave -- the same, or in guard mode the zones too --; `req`: the byte count of the largest request the allocation has served,
+    // where a guarded buffer's tail zone starts; `lost_*`: damage found in the part of the tail zone a larger request took over
+    struct Buf {
+        void *ptr = nullptr; size_t bytes = 0; unsigned long long stamp = 0; size_t real = 0, req = 0; bool guard = false;
+        long long lost_first = -1, lost_last = -1; size_t lost_req = 0;
+        void *base() const { return guard ? (char *)ptr - WS_ZONE : ptr; }
+        size_t tail_bytes() const { return guard ? real - WS_ZONE - req : 0; }
+    };
     Buf bufs[WS_COUNT];
-    void *get(WsBuf id, size_t bytes)
+    static void drop(Buf &b) { if (b.ptr) { (void)hipFree(b.base()); g_ws_bytes -= (long long)b.real; } b = Buf{}; }
+    // poisons the bytes [lo, hi) of a guarded allocation and waits for the whole device (the streams beside the call's may be the next
+    // to touch the buffer)
+    static void guard_fill(WsBuf id, Buf &b, size_t lo, size_t hi, unsigned poison, bool fresh)
     {
+        const size_t w0 = fresh ? 0 : lo / 4, w1 = fresh ? b.real / 4 : (hi + 3) / 4;
+        hipError_t e = hipSuccess;
+        if (w1 > w0) {
+            hipLaunchKernelGGL(k_ws_guard_fill, dim3((unsigned)std::min<size_t>((w1 - w0 + 255) / 256, 4096)), dim3(256), 0, nullptr,
+                               (unsigned *)b.base(), w0, w1, lo, hi, poison, fresh);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) { drop(b); throw RmError{RM_ERR_HIP, std::string("RM_DEBUG_WS_GUARD: filling ") + WS_NAMES[id] + ": " + hipGetErrorString(e)}; }
+    }
+    // A guarded buffer serves a request larger than any before, inside its slack: the payload grows into the tail zone.  What it takes
+    // over is compared with WS_RED first (damage there is kept for rm_debug_ws_check: `lost_*`, the first such find) and then poisoned.
+    static void guard_grow(WsBuf id, Buf &b, size_t req, unsigned poison)
+    {
+        HIP_CHECK(hipDeviceSynchronize());
+        const size_t at = WS_ZONE + b.req, len = std::min(req - b.req, WS_CHECK_MAX);
+        std::vector<unsigned char> host(len);
+        HIP_CHECK(hipMemcpy(host.data(), (const char *)b.base() + at, len, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < len && b.lost_first < 0; i++)
+            if (host[i] != ws_pattern_byte(WS_RED, at + i)) {
+                b.lost_first = b.lost_last = (long long)i; b.lost_req = b.req;
+                for (size_t j = len; j-- > i;) if (host[j] != ws_pattern_byte(WS_RED, at + j)) { b.lost_last = (long long)j; break; }
+            }
+        guard_fill(id, b, at, WS_ZONE + req, poison, false);
+        b.req = req;
+    }
+    void *get(WsBuf id, size_t bytes, unsigned poison = WS_POISON_INT)
+    {
+        const size_t req = bytes;
         bytes = std::max<size_t>(bytes, 256);
         Buf &b = bufs[id];
         if (b.bytes < bytes) {
-            if (b.ptr) { (void)hipFree(b.ptr); g_ws_bytes -= (long long)b.bytes; b = Buf{}; }
+            drop(b);
             const size_t cap = bytes + bytes / 8;
+            const bool guard = g_sw.ws_guard;
+            const size_t real = guard ? WS_ZONE + (cap + 3) / 4 * 4 + WS_ZONE : cap;
             const long long sim = debug_free_cap();
-            if (sim >= 0 && g_ws_bytes.load() + (long long)cap > sim)
-                throw RmError{RM_ERR_NOMEM, std::string("hipMalloc(") + WS_NAMES[id] + ", " + std::to_string(cap) + " B): beyond RM_DEBUG_FREE_MB"};
-            hipError_t e = hipMalloc(&b.ptr, cap);
-            if (e != hipSuccess) { b.ptr = nullptr; throw RmError{RM_ERR_NOMEM, std::string("hipMalloc(") + WS_NAMES[id] + ", " + std::to_string(cap) + " B): " + hipGetErrorString(e)}; }
-            b.bytes = cap; b.stamp = g_ws_stamp.fetch_add(1);
-            g_ws_bytes += (long long)cap;
-        }
+            if (sim >= 0 && g_ws_bytes.load() + (long long)real > sim)
+                throw RmError{RM_ERR_NOMEM, std::string("hipMalloc(") + WS_NAMES[id] + ", " + std::to_string(real) + " B): beyond RM_DEBUG_FREE_MB"};
+            void *p = nullptr;
+            hipError_t e = hipMalloc(&p, real);
+            if (e != hipSuccess) throw RmError{RM_ERR_NOMEM, std::string("hipMalloc(") + WS_NAMES[id] + ", " + std::to_string(real) + " B): " + hipGetErrorString(e)};
+            g_ws_bytes += (long long)real;
+            b.ptr = guard ? (char *)p + WS_ZONE : p; b.bytes = cap; b.real = real; b.req = req; b.guard = guard; b.stamp = g_ws_stamp.fetch_add(1);
+            if (guard) guard_fill(id, b, WS_ZONE, WS_ZONE + req, poison, true);
+        } else if (b.guard && b.req < req) guard_grow(id, b, req, poison);
         return b.ptr;
     }
-    template <class T> T *array(WsBuf id, size_t count) { return (T *)get(id, sizeof(T) * count); }
+    template <class T> T *array(WsBuf id, size_t count) { return (T *)get(id, sizeof(T) * count, std::is_floating_point<T>::value ? WS_POISON_FLOAT : WS_POISON_INT); }
     // the buffer as it stands (never asked for, or released: null and stamp 0, which no valid record carries)
     const Buf &peek(WsBuf id) const { return bufs[id]; }
-    void release() { for (Buf &b : bufs) { if (b.ptr) { (void)hipFree(b.ptr); g_ws_bytes -= (long long)b.bytes; } b = Buf{}; } }      // (every slot: no stamp outlives its memory)
+    void release() { for (Buf &b : bufs) drop(b); }      // (every slot: no stamp outlives its memory)
 };
 // What a workspace buffer was last filled with, for the callers that may find it filled already.  A record is valid only for the
 // allocation it was made in (Workspace::Buf::stamp): `Filled<ID>` is that half of every record, bound to its buffer; each question a
@@ -720,7 +792,7 @@ inline long long free_plus_owned(const Workspace &ws, std::initializer_list<WsBu
     const long long sim = debug_free_cap();
     if (sim >= 0) fr = (size_t)std::max<long long>(0, std::min<long long>((long long)fr, sim - g_ws_bytes.load()));
     long long owned = 0;
-    for (WsBuf id : ids) owned += (long long)ws.peek(id).bytes;
+    for (WsBuf id : ids) owned += (long long)ws.peek(id).real;
     return (long long)fr + owned;
 }
 // elements between two stored score rows of n items (stream_scores, the tie noise's rows): whole tiles of either size of the sweep (64 / 96 items)
@@ -3444,5 +3516,86 @@ extern "C" int rm_release_workspace(void)
             std::lock_guard<std::mutex> cl(c->mu);
             c->ws.release();                  // (what the context remembers of the buffers' contents goes with their stamps)
         }
+    });
+}
+
+// Test hooks of RM_DEBUG_WS_GUARD (Workspace).  The contexts of the current device, by slot; their mutexes are taken one by one
+// (rm_release_workspace says why).
+static std::vector<Ctx *> contexts_of_current_device()
+{
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    std::vector<Ctx *> mine;
+    std::lock_guard<std::mutex> lk(g_ctx_mu);
+    for (auto &kv : g_ctx) if (kv.first.first == dev) mine.push_back(kv.second.get());
+    return mine;
+}
+// Compares both zones of every live guarded buffer of the current device with WS_RED (of a tail longer than WS_CHECK_MAX its first
+// WS_CHECK_MAX bytes) and returns the number of damaged zones, -1 on a HIP error (rm_last_error).  `msg` (cap bytes, may be NULL)
+// receives "checked <buffers> buffers, <damaged> damaged zones" and a line per damaged zone:
+//     damaged: buffer=<name> slot=<context slot> side=<head|tail> first=<offset> last=<offset> requested=<bytes> zone=<bytes>
+// first / last: the first and the last damaged byte, counted from the payload's start (head: -256 .. -1) or from its end (tail: 0 ..).
+extern "C" int rm_debug_ws_check(char *msg, int cap)
+{
+    int damaged = 0;
+    const int rc = guarded([&] {
+        HIP_CHECK(hipDeviceSynchronize());
+        int checked = 0;
+        std::string lines;
+        std::vector<unsigned char> host;
+        for (Ctx *c : contexts_of_current_device()) {
+            std::lock_guard<std::mutex> cl(c->mu);
+            for (int id = 0; id < WS_COUNT; id++) {
+                const Workspace::Buf &b = c->ws.peek((WsBuf)id);
+                if (!b.ptr || !b.guard) continue;
+                checked++;
+                if (b.lost_first >= 0) {              // (found when a larger request took that part of the tail zone over: Workspace::guard_grow)
+                    damaged++;
+                    lines += std::string("damaged: buffer=") + WS_NAMES[id] + " slot=" + std::to_string(c->slot) + " side=tail first=" + std::to_string(b.lost_first) +
+                             " last=" + std::to_string(b.lost_last) + " requested=" + std::to_string(b.lost_req) + " zone=" + std::to_string(b.real - WS_ZONE - b.lost_req) + "\n";
+                }
+                for (int tail = 0; tail < 2; tail++) {
+                    const size_t zone = tail ? b.tail_bytes() : WS_ZONE, len = std::min(zone, WS_CHECK_MAX);
+                    const size_t at = tail ? WS_ZONE + b.req : 0;            // the zone's offset in the allocation
+                    host.resize(len);
+                    HIP_CHECK(hipMemcpy(host.data(), (const char *)b.base() + at, len, hipMemcpyDeviceToHost));
+                    long long first = -1, last = -1;
+                    for (size_t i = 0; i < len; i++)
+                        if (host[i] != ws_pattern_byte(WS_RED, at + i)) { if (first < 0) first = (long long)i; last = (long long)i; }
+                    if (first < 0) continue;
+                    damaged++;
+                    const long long origin = tail ? 0 : -(long long)WS_ZONE;
+                    lines += std::string("damaged: buffer=") + WS_NAMES[id] + " slot=" + std::to_string(c->slot) + " side=" + (tail ? "tail" : "head") +
+                             " first=" + std::to_string(origin + first) + " last=" + std::to_string(origin + last) +
+                             " requested=" + std::to_string(b.req) + " zone=" + std::to_string(zone) + "\n";
+                }
+            }
+        }
+        const std::string text = "checked " + std::to_string(checked) + " buffers, " + std::to_string(damaged) + " damaged zones\n" + lines;
+        if (msg && cap > 0) { const size_t n = std::min(text.size(), (size_t)cap - 1); std::memcpy(msg, text.data(), n); msg[n] = 0; }
+    });
+    return rc ? -1 : damaged;
+}
+// The positive control of that check: one byte of a zone of the live guarded buffer `buffer_id` (its place in RM_WS_BUFFERS; the
+// first context of the current device that has one) is overwritten with the complement of its pattern byte.  tail = 0: the head
+// zone; offset >= 0 counts from the zone's first byte, offset < 0 from behind its last one (-1: the last byte).  Only memory that
+// Workspace::get allocated as a zone is touched.  RM_ERR_INVALID when there is no such buffer or the offset lies outside the zone.
+extern "C" int rm_debug_ws_poke(int buffer_id, int tail, int offset)
+{
+    return guarded([&] {
+        if (buffer_id < 0 || buffer_id >= WS_COUNT) throw RmError{RM_ERR_INVALID, "rm_debug_ws_poke: no buffer " + std::to_string(buffer_id)};
+        HIP_CHECK(hipDeviceSynchronize());
+        for (Ctx *c : contexts_of_current_device()) {
+            std::lock_guard<std::mutex> cl(c->mu);
+            const Workspace::Buf &b = c->ws.peek((WsBuf)buffer_id);
+            if (!b.ptr || !b.guard) continue;
+            const long long zone = (long long)(tail ? b.tail_bytes() : WS_ZONE), i = offset < 0 ? zone + offset : offset;
+            if (i < 0 || i >= zone) throw RmError{RM_ERR_INVALID, std::string("rm_debug_ws_poke: ") + WS_NAMES[buffer_id] + ": offset " + std::to_string(offset) + " is outside the zone of " + std::to_string(zone) + " B"};
+            const size_t at = (tail ? WS_ZONE + b.req : 0) + (size_t)i;
+            HIP_CHECK(hipMemset((char *)b.base() + at, ws_pattern_byte(WS_RED, at) ^ 0xFF, 1));
+            HIP_CHECK(hipDeviceSynchronize());
+            return;
+        }
+        throw RmError{RM_ERR_INVALID, std::string("rm_debug_ws_poke: no live guarded buffer ") + WS_NAMES[buffer_id]};
     });
 }
