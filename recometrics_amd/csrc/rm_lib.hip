@@ -448,8 +448,15 @@ struct Ctx {
         }
         return pinned;
     }
-    double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // rm_get_timings' out[]: the four stage times, then the launch the "sweep" timing brackets (launches, item splits, blocks, LDS bytes)
+    enum { TM_LAUNCHES = 4, TM_SPLITS, TM_BLOCKS, TM_LDS, TM_TIMED_SLOTS, TM_TOTAL_SLOTS, TM_SPLIT_REUSED, TM_HINTED, TM_COUNT };
+    double timings[TM_TIMED_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};
     int timed_slots = 0, total_slots = 0;     // slots (user lanes) of the sweep launch the "sweep" timing brackets / of the call
+    void sweep_shape(double launches, double splits, double blocks, double lds, int slots)      // (slots < 0: nothing was launched, they stay)
+    {
+        timings[TM_LAUNCHES] = launches; timings[TM_SPLITS] = splits; timings[TM_BLOCKS] = blocks; timings[TM_LDS] = lds;
+        if (slots >= 0) timed_slots = total_slots = slots;
+    }
     double acc[4] = {0, 0, 0, 0};            // prep / sweep / finalize / total ms of the batches already read back (host entry)
     PackedItems packed; DenseRows dense; DiscountTable discounts;    // what WS_BP, WS_TRAIN_BITS and WS_LOG2TAB of `ws` hold
     SplitCache split;                                                // ... and what the plan stage's buffers hold of the last call's split
@@ -966,7 +973,7 @@ inline void launch_csr_index_checks(int m, int n, const int *train_p, const int 
     if (nnz_test > 0) hipLaunchKernelGGL(k_check_csr_flat, blocks(nnz_test), dim3(CHECK_FLAT_THREADS), 0, stream, m, n, test_p, test_i, plan, 1);
 }
 inline void launch_csr_checks(int m, int n, const int *train_p, const int *train_i, long long nnz_train, const int *test_p, const int *test_i, long long nnz_test,
-                              Plan *plan, const unsigned char *, hipStream_t stream)
+                              Plan *plan, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_check_csr_ptr, dim3(cdiv(m, 256)), dim3(256), 0, stream, m, train_p, nnz_train, test_p, nnz_test, plan);
     launch_csr_index_checks(m, n, train_p, train_i, nnz_train, test_p, test_i, nnz_test, plan, stream);
@@ -980,7 +987,7 @@ void check_csr_now(const Call<T> &c, hipStream_t stream, Ctx &cx)
     cx.split.invalidate();                                         // (the Plan is zeroed below)
     if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));
     HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
-    launch_csr_checks(c.m, c.n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, c.only_users, stream);
+    launch_csr_checks(c.m, c.n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, stream);
     Plan hp;
     HIP_CHECK(hipMemcpyAsync(&hp, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -1047,6 +1054,8 @@ struct Geometry {
     size_t per_key, lds_total, sync_off; int pend_cap;
     int u_split, j_shallow; size_t lds_l;                  // depth split: the shallow user blocks [0, u_split) with their lists in LDS
 };
+// blocks of a sweep launch over `n_ublocks` user blocks of the two-level grid, `tail_ublocks` of them cut into the tail's item ranges
+inline unsigned sweep_blocks(int n_ublocks, int tail_ublocks, const Geometry &g) { return (unsigned)((n_ublocks - tail_ublocks) * g.n_splits + tail_ublocks * g.tail_splits); }
 template <class T>
 Geometry sweep_geometry(const Call<T> &c, const Plan &hp, int NG, bool want_auc, bool want_lane, bool ext_topk, bool check_nan, bool dense_ok,
                         const Switches &sw)
@@ -1183,12 +1192,16 @@ struct Pipeline {
     int *flags = nullptr, *user_nslots = nullptr, *uslot_base = nullptr, *heavy_users = nullptr; Plan *plan = nullptr;
     int *slot_user = nullptr, *slot_chunk = nullptr, *slot_index = nullptr, *gj = nullptr, *sc_user = nullptr, *sc_chunk = nullptr;
     long long *grow = nullptr; double *log2tab = nullptr;
-    ClassifyArgs ca{};
+    unsigned char *slot_j = nullptr; int *tile_total = nullptr, *tile_offset = nullptr, n_tiles = 0;      // (the plan chain's own)
+    ClassifyArgs ca{}; long long stream_cap = 0;          // (score rows of streamed users the budget admits)
+    int *ent_user = nullptr; unsigned char *ent_masked = nullptr;      // the scores by entry (flat_early); what every positives' kernel gets:
+    PosArgs<T> pa{};
     bool want_lane = false, ext_topk = false, items_known = false, dense_ok = false;
     bool row_topk = false;                  // lists from the caller's scores, selected while the row is read (k_topk_rows): no score row is stored
     bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
     // the split the context kept (SplitCache): may this pass run on it, does it, may the next one run on this pass's
     bool allow_reuse = true, reused = false, keepable = false; SplitKey split_key{};
+    std::array<const void *, SPLIT_ARRAYS> theirs{};      // the caller's five arrays (a pass on the kept split reads the copies: `c`)
     bool hints = false; int *hint_counts_dev = nullptr;  // ... and its previous lists give this pass bounds (k_hint_bounds)
     Plan hp{};
     int n_slots = 0, n_stream = 0, stream_slot0 = 0; bool check_nan = false;
@@ -1238,9 +1251,30 @@ struct Pipeline {
     // ---- plan: classify the users, slots and groups; beside it the CSR checks, the maxima, the early dense rows; read back ----
     void plan_stage()
     {
+        user_buffers();
+        list_scheme();
+        slot_buffers();
+        discount_table();
+        beside_scheme();
+        kept_split();
+        if (flat_early) fill_pos_args();                               // (else positives() does: the scores by slot)
+        if (reused) plan_reused();
+        else for (int attempt = 0; ; attempt++) {
+            plan_chain(attempt);
+            beside_chain(attempt);
+            enqueue_read_back(attempt);
+            if (!plan_again(attempt)) break;
+        }
+        n_slots = hp.n_slots;
+        // streamed users own the last slots; the tables and their kernels cover slots [0, stream_slot0)
+        n_stream = (want_auc || ext_topk) ? hp.class_count[STREAM_CLASS] : 0;
+        stream_slot0 = n_stream > 0 ? hp.class_offset[STREAM_CLASS] : n_slots;
+        if (!reused) check_nan = scores_may_overflow();                // (a pass on a kept split assumes the kept answer until verdict())
+    }
+    void user_buffers()                     // the per-user buffers and k_classify's arguments
+    {
         flags = ws.array<int>(WS_FLAGS, (size_t)m);
-        user_nslots = ws.array<int>(WS_USER_NSLOTS, (size_t)m);
-        uslot_base = ws.array<int>(WS_USLOT_BASE, (size_t)m);
+        user_nslots = ws.array<int>(WS_USER_NSLOTS, (size_t)m); uslot_base = ws.array<int>(WS_USLOT_BASE, (size_t)m);
         plan = ws.array<Plan>(WS_PLAN, 1);
         heavy_users = ws.array<int>(WS_HEAVY_USERS, (size_t)m);
         ca = ClassifyArgs{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
@@ -1251,51 +1285,50 @@ struct Pipeline {
         // k_train_bits would be a memory fault; on the CPU reference it is a segfault): the index pointers by k_classify itself, the
         // 80 MB of indices of BASELINE C2 by k_check_csr_rows beside the plan chain (~40 us)
         ca.check_ptr = c.csr_checked ? 0 : 1; ca.nnz_train = c.nnz_train; ca.nnz_test = c.nnz_test;
+    }
+    void list_scheme()                      // the list scheme and the stream budget (both ask for the FREE memory: they stay between the two groups of buffers)
+    {
         // Users with more than POS_CHUNK test items are "streamed" (rm_device.hpp STREAM_CLASS) when a score row for each of
         // them fits the HBM budget: a third of the free memory unless RM_STREAM_BUDGET_MB says otherwise (0 = never; such
         // users then take one sweep slot per chunk of their test row -- same results, the contraction repeated per chunk).
         // The plan assumes they fit; the host looks at their number in the read-back and, should the rows not fit, plans once more
         // without streaming (what used to be two launches in front of k_classify -- count, decide -- on every call).
         const long long stream_ld_max = score_row_stride(n);
+        // (a pass over a subset of the users -- the exact second pass of the fp32 tie noise -- stores rows for that subset only)
+        const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
         // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
         // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
-        want_lane = !c.scores && lane_lists_fit<T>(ws, K, c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m, P::max_nsub >= 3 && NG <= 8);
+        want_lane = !c.scores && lane_lists_fit<T>(ws, K, m_rows, P::max_nsub >= 3 && NG <= 8);
         // (the caller's scores: the same plan -- the row every user needs is a copy of its row of S with the train items masked;
         // lists of up to ROW_TOPK_MAX_K items from them need no stored row at all: k_topk_rows, rm_rowtopk.hpp)
         row_topk = c.reco && c.scores && K <= ROW_TOPK_MAX_K && !g_sw.no_row_topk;
-        ext_topk = (!want_lane && K > 256) || g_sw.ext_topk || c.scores;
-        if (row_topk) ext_topk = false;
-        long long stream_cap = 0;
+        ext_topk = !row_topk && ((!want_lane && K > 256) || g_sw.ext_topk || c.scores);
         if (want_auc || ext_topk) {
             stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
-            // (a pass over a subset of the users -- the exact second pass of the fp32 tie noise -- stores rows for that subset only)
-            const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
             if (ext_topk) {
                 if (m_rows > stream_cap) throw RmError{RM_ERR_NOMEM, std::string(c.scores && c.reco ? "lists of more than 1024 items from a score matrix keep one masked score row (" : c.scores ? "metrics from a score matrix keep one masked score row (" : "k_metrics > 256 keeps one score row (") + std::to_string(stream_ld_max * (long long)sizeof(T)) +
                                            " B) per user in device memory: " + std::to_string(m_rows) + " users do not fit, at most " + std::to_string(stream_cap) + " per call"};
                 ca.force_stream = 1;
             } else if (stream_cap > 0) ca.allow_stream = 1;
         }
+    }
+    void slot_buffers()                     // the per-slot and per-group tables, the tiles of the scan
+    {
         const long long slot_bound = (long long)m + c.nnz_test / POS_CHUNK + 1;
         const long long group_bound = slot_bound / GU + 2;
-        slot_user = ws.array<int>(WS_SLOT_USER, (size_t)slot_bound);
-        slot_chunk = ws.array<int>(WS_SLOT_CHUNK, (size_t)slot_bound);
-        slot_index = ws.array<int>(WS_SLOT_INDEX, (size_t)slot_bound);
-        unsigned char *slot_j = ws.array<unsigned char>(WS_SLOT_J, (size_t)slot_bound);
-        gj = ws.array<int>(WS_GJ, (size_t)group_bound);
-        grow = ws.array<long long>(WS_GROW, (size_t)group_bound);
-        sc_user = ws.array<int>(WS_SC_USER, (size_t)slot_bound);
-        sc_chunk = ws.array<int>(WS_SC_CHUNK, (size_t)slot_bound);
-        int *tile_total = nullptr, *tile_offset = nullptr;
-        const int n_tiles = (int)cdiv(m, 1024);
-        if (m > 8192) {                                          // one block walking the whole array costs ~0.5 us per 1024 entries
-            tile_total = ws.array<int>(WS_SCAN_TILE_TOTAL, (size_t)n_tiles);
-            tile_offset = ws.array<int>(WS_SCAN_TILE_OFFSET, (size_t)n_tiles);
-        }
-        items_known = cx.packed.of_call(c.items_tag);                          // a later batch of the same host call
-        // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
-        // depends on K alone: it stays in the workspace, and only a longer one (or one for a new allocation) is uploaded again -- the
-        // copy comes from pageable memory, which blocks the host and waits for the stream
+        slot_user = ws.array<int>(WS_SLOT_USER, (size_t)slot_bound); slot_chunk = ws.array<int>(WS_SLOT_CHUNK, (size_t)slot_bound);
+        slot_index = ws.array<int>(WS_SLOT_INDEX, (size_t)slot_bound); slot_j = ws.array<unsigned char>(WS_SLOT_J, (size_t)slot_bound);
+        gj = ws.array<int>(WS_GJ, (size_t)group_bound); grow = ws.array<long long>(WS_GROW, (size_t)group_bound);
+        sc_user = ws.array<int>(WS_SC_USER, (size_t)slot_bound); sc_chunk = ws.array<int>(WS_SC_CHUNK, (size_t)slot_bound);
+        n_tiles = (int)cdiv(m, 1024);
+        if (m <= 8192) return;                                   // one block walking the whole array costs ~0.5 us per 1024 entries
+        tile_total = ws.array<int>(WS_SCAN_TILE_TOTAL, (size_t)n_tiles); tile_offset = ws.array<int>(WS_SCAN_TILE_OFFSET, (size_t)n_tiles);
+    }
+    // log2(i + 2) for the DCG discounts, from the host's libm like the reference's (:620,:902, int -> double log2).  The table
+    // depends on K alone: it stays in the workspace, and only a longer one (or one for a new allocation) is uploaded again -- the
+    // copy comes from pageable memory, which blocks the host and waits for the stream
+    void discount_table()
+    {
         if (!c.reco) log2tab = ws.array<double>(WS_LOG2TAB, (size_t)K);
         if (!c.reco && !cx.discounts.holds(ws, K)) {
             std::vector<double> lt((size_t)K);
@@ -1303,6 +1336,10 @@ struct Pipeline {
             HIP_CHECK(hipMemcpy(log2tab, lt.data(), sizeof(double) * (size_t)K, hipMemcpyHostToDevice));       // (synchronous: `lt` is on the stack)
             cx.discounts.set(ws, K);
         }
+    }
+    void beside_scheme()                    // what the call's kind lets run beside the plan chain, and where the read-back lands
+    {
+        items_known = cx.packed.of_call(c.items_tag);                          // a later batch of the same host call
         if (!cx.pinned_plan) HIP_CHECK(hipHostMalloc((void **)&cx.pinned_plan, sizeof(Plan), hipHostMallocDefault));
         // (one answer per call: a later pass -- the exact passes of the tie noise, on this or on a peer context with less free memory --
         // carries the first pass's answer; rows handed over by another pass are proof that they fit)
@@ -1310,11 +1347,13 @@ struct Pipeline {
         // the positives' stream: the streamed users' chain beside the table users', and what is made per test entry beside the plan chain
         // (the caller's scores: the test entries' scores are gathered by entry whatever the switch says -- there is no kernel by slot)
         flat_early = want_auc && !c.only_users && c.nnz_test > 0 && (!g_sw.no_pos_flat || c.scores);
-        int *ent_user = nullptr; unsigned char *ent_masked = nullptr;
-        // The split the context kept: when this call's key is the kept one, the pass reads the context's COPIES of the five arrays --
-        // validated when they were made, and the arrays every kept table was derived from -- while k_split_same finds out whether the
-        // caller's arrays still equal them: nothing is ever indexed through an array that has not been validated.
-        const void *theirs[SPLIT_ARRAYS] = {c.train_p, c.train_i, c.test_p, c.test_i, c.test_v};
+    }
+    // The split the context kept: when this call's key is the kept one, the pass reads the context's COPIES of the five arrays --
+    // validated when they were made, and the arrays every kept table was derived from -- while k_split_same finds out whether the
+    // caller's arrays still equal them: nothing is ever indexed through an array that has not been validated.
+    void kept_split()
+    {
+        theirs = {c.train_p, c.train_i, c.test_p, c.test_i, c.test_v};
         keepable = make_split_key(split_key);
         cx.split_reused = keepable ? 0 : -1;
         reused = keepable && allow_reuse && cx.split.holds(ws, split_key) &&
@@ -1330,116 +1369,127 @@ struct Pipeline {
             c.test_p = (const int *)cx.split.copy(ws, 2); c.test_i = (const int *)cx.split.copy(ws, 3);
             if (c.test_v) c.test_v = (const T *)cx.split.copy(ws, 4);
         } else cx.split.invalidate();                                 // (the kernels below overwrite what the record speaks of)
-        PosArgs<T> pf{};
-        if (flat_early) {
-            ent_user = ws.array<int>(WS_ENT_USER, (size_t)c.nnz_test);
-            ent_masked = ws.array<unsigned char>(WS_ENT_MASKED, (size_t)c.nnz_test);
-            pf.m = m; pf.n = n; pf.k = k; pf.A = c.A; pf.lda = c.lda; pf.B = c.B; pf.ldb = c.ldb;
-            pf.train_p = c.train_p; pf.train_i = c.train_i; pf.test_p = c.test_p; pf.test_i = c.test_i; pf.flags = flags;
-            pf.pos_tmp = ws.array<T>(WS_POS_TMP, (size_t)c.nnz_test);
-            if (sizeof(T) == 4) pf.pos_key = (unsigned long long *)ws.get(WS_POS_KEY, 8 * ((size_t)c.nnz_test + 8));
-            pf.noise_row = c.noise_row; pf.noise_row0 = c.noise_row0; pf.noise_E = c.noise_E; pf.noise_ld = c.noise_ld;
-            pf.noise_flag = c.noise_flag; pf.plan = plan;
+    }
+    // `pa`, the arguments of the positives' kernels, as far as they are known in front of the first of them: with the scores by entry
+    // (flat_early, which implies nnz_test > 0) the plan stage asks, and the two per-entry buffers come with them; else positives() does,
+    // which adds what it allocates either way.  The factors and the CSR arrays are read BEHIND kept_split(): a pass on the kept split
+    // scores through the context's copies.
+    void fill_pos_args()
+    {
+        const size_t nz = (size_t)std::max<long long>(c.nnz_test, 1);
+        if (flat_early) { ent_user = ws.array<int>(WS_ENT_USER, nz); ent_masked = ws.array<unsigned char>(WS_ENT_MASKED, nz); }
+        pa.m = m; pa.n = n; pa.k = k; pa.A = c.A; pa.lda = c.lda; pa.B = c.B; pa.ldb = c.ldb;
+        pa.train_p = c.train_p; pa.train_i = c.train_i; pa.test_p = c.test_p; pa.test_i = c.test_i; pa.flags = flags;
+        pa.pos_tmp = ws.array<T>(WS_POS_TMP, nz);
+        if (sizeof(T) == 4) pa.pos_key = (unsigned long long *)ws.get(WS_POS_KEY, 8 * (nz + 8));
+        pa.noise_row = c.noise_row; pa.noise_row0 = c.noise_row0; pa.noise_E = c.noise_E; pa.noise_ld = c.noise_ld;
+        pa.noise_flag = c.noise_flag; pa.plan = plan;
+    }
+    // ---- the plan chain: five launches that depend on one another, on the call's stream (index pointers only) ----
+    void plan_chain(int attempt)
+    {
+        if (attempt == 0) HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
+        else {
+            // (a second plan keeps the count of the users the tie noise's first pass has flagged so far: the positives' scores of the
+            // first attempt, which count them, are not made again)
+            const size_t at = offsetof(Plan, n_noise_flagged);
+            HIP_CHECK(hipMemsetAsync(plan, 0, at, stream));
+            HIP_CHECK(hipMemsetAsync((char *)plan + at + sizeof(int), 0, sizeof(Plan) - at - sizeof(int), stream));
         }
-        if (reused) plan_reused(pf, ent_user, ent_masked, theirs);
-        else for (int attempt = 0; ; attempt++) {
-            // ---- the plan chain: five launches that depend on one another, on the call's stream (index pointers only) ----
-            if (attempt == 0) HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
-            else {
-                // (a second plan keeps the count of the users the tie noise's first pass has flagged so far: the positives' scores of the
-                // first attempt, which count them, are not made again)
-                const size_t at = offsetof(Plan, n_noise_flagged);
-                HIP_CHECK(hipMemsetAsync(plan, 0, at, stream));
-                HIP_CHECK(hipMemsetAsync((char *)plan + at + sizeof(int), 0, sizeof(Plan) - at - sizeof(int), stream));
+        hipLaunchKernelGGL(k_classify, dim3(cdiv(m, 1024)), dim3(1024), 0, stream, ca);
+        // (the two forks behind k_classify, recorded BEFORE the rest of the chain is enqueued: the host needs ~4 us per launch, and the
+        // chain's kernels used to reach the device 60 us late, behind everything that was enqueued for the other streams)
+        side.cut(SIDE_PLAN_FORK); pos.cut(POS_PLAN_FORK);
+        if (tile_total) {
+            hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(1024), 0, stream, user_nslots, uslot_base, m, tile_total);
+            hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, tile_total, tile_offset, n_tiles, &plan->n_slots, plan, GU);
+        } else hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, user_nslots, uslot_base, m, &plan->n_slots, plan, GU);
+        AssignArgs aa{m, c.test_p, flags, user_nslots, uslot_base, want_auc ? 1 : 0, plan, slot_user, slot_chunk, slot_index, slot_j, sc_user, sc_chunk,
+                      ext_topk ? 1 : 0, tile_offset};
+        hipLaunchKernelGGL(k_assign_slots, dim3(cdiv(m, ASSIGN_THREADS)), dim3(ASSIGN_THREADS), 0, stream, aa);
+        hipLaunchKernelGGL(k_block_tables, dim3(1), dim3(1024), 0, stream, plan, slot_j, gj, grow, GU);
+    }
+    // ---- beside it: what reads the index arrays and the factors ----
+    void beside_chain(int attempt)
+    {
+        // On the side stream the CSR rows' validation (gated on the index pointers k_classify has just checked), then the dense train
+        // rows (fp32, small item counts; set_train_bits), which depend on the CSR inputs alone: they run during the rest of the plan
+        // chain, the read-back -- the host's one wait of the call -- and the positives' scores.  Whether the rows also mark the test
+        // items (`mask_test`) is only decided behind the read-back; the guess here is the usual answer, and a wrong guess costs one
+        // more launch of the kernel behind it.  On the positives' stream max |A| and max |B| and the user of every test entry.  The
+        // plan carries the checks' verdicts and the maxima: its read-back waits for both streams.
+        const hipStream_t aux = side.behind(SIDE_PLAN_FORK), aux2 = pos.behind(POS_PLAN_FORK);
+        if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
+        side.mark(SIDE_CHECKS_DONE);
+        if (!c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
+        if (!items_known && !c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
+        pos.mark(POS_MAXIMA_DONE);
+        if (attempt != 0) return;                                      // (the second plan makes neither again)
+        // (the user of every test entry, for the positives' scores by entry: index pointers only)
+        if (flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, pos.on(), m, c.test_p, ent_user, plan);
+        // (463 MB of writes at BASELINE C2; four resident blocks per CU leave half of the wave slots to the plan's kernels and the
+        // read-back's copy.  With the positives' scores by entry the kernel also says which test items are train items, `ent_masked`:
+        // a bit of the row it has just built.)
+        if (std::is_same<T, float>::value && use_side && !c.ext_bits && dense_ok) {
+            SweepArgs probe{};
+            const bool guess = want_auc && !ext_topk && !g_sw.no_test_mask;
+            (void)ws.get(WS_TRAIN_BITS, (size_t)m * (size_t)dense_row_words(n) * 4);
+            if (!(c.same_train_rows && cx.dense.fits(ws, m, dense_row_words(n), guess))) {
+                set_train_bits(probe, cx, c, m, n, dense_ok, side.on(), guess, false, false, flat_early ? ent_masked : nullptr);
+                side.mark(SIDE_ROWS_AND_PACKS); side.mark(SIDE_ROWS_FOR_POS);
+                bits_early = true; bits_early_masked = guess; masked_from_bits = flat_early;
             }
-            hipLaunchKernelGGL(k_classify, dim3(cdiv(m, 1024)), dim3(1024), 0, stream, ca);
-            // (the two forks behind k_classify, recorded BEFORE the rest of the chain is enqueued: the host needs ~4 us per launch, and the
-            // chain's kernels used to reach the device 60 us late, behind everything that was enqueued for the other streams)
-            side.cut(SIDE_PLAN_FORK); pos.cut(POS_PLAN_FORK);
-            if (tile_total) {
-                hipLaunchKernelGGL(k_scan_tiles, dim3(n_tiles), dim3(1024), 0, stream, user_nslots, uslot_base, m, tile_total);
-                hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, tile_total, tile_offset, n_tiles, &plan->n_slots, plan, GU);
-            } else {
-                hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, stream, user_nslots, uslot_base, m, &plan->n_slots, plan, GU);
-            }
-            AssignArgs aa{m, c.test_p, flags, user_nslots, uslot_base, want_auc ? 1 : 0, plan, slot_user, slot_chunk, slot_index, slot_j, sc_user, sc_chunk,
-                          ext_topk ? 1 : 0, tile_offset};
-            hipLaunchKernelGGL(k_assign_slots, dim3(cdiv(m, ASSIGN_THREADS)), dim3(ASSIGN_THREADS), 0, stream, aa);
-            hipLaunchKernelGGL(k_block_tables, dim3(1), dim3(1024), 0, stream, plan, slot_j, gj, grow, GU);
-            // ---- beside it: what reads the index arrays and the factors ----
-            // On the side stream the CSR rows' validation (gated on the index pointers k_classify has just checked), then the dense train
-            // rows (fp32, small item counts; set_train_bits), which depend on the CSR inputs alone: they run during the rest of the plan
-            // chain, the read-back -- the host's one wait of the call -- and the positives' scores.  Whether the rows also mark the test
-            // items (`mask_test`) is only decided behind the read-back; the guess here is the usual answer, and a wrong guess costs one
-            // more launch of the kernel behind it.  On the positives' stream max |A| and max |B| and the user of every test entry.  The
-            // plan carries the checks' verdicts and the maxima: its read-back waits for both streams.
-            const hipStream_t aux = side.behind(SIDE_PLAN_FORK), aux2 = pos.behind(POS_PLAN_FORK);
-            if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
-            side.mark(SIDE_CHECKS_DONE);
-            if (!c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
-            if (!items_known && !c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
-            pos.mark(POS_MAXIMA_DONE);
-            // (the user of every test entry, for the positives' scores by entry: index pointers only)
-            if (attempt == 0 && flat_early) hipLaunchKernelGGL(k_entry_users, dim3(cdiv(cdiv(m, WAVE) * WAVE, 256)), dim3(256), 0, pos.on(), m, c.test_p, ent_user, plan);
-            // (463 MB of writes at BASELINE C2; four resident blocks per CU leave half of the wave slots to the plan's kernels and the
-            // read-back's copy.  With the positives' scores by entry the kernel also says which test items are train items, `ent_masked`:
-            // a bit of the row it has just built.)
-            if (attempt == 0 && std::is_same<T, float>::value && use_side && !c.ext_bits && dense_ok) {
-                SweepArgs probe{};
-                const bool guess = want_auc && !ext_topk && !g_sw.no_test_mask;
-                (void)ws.get(WS_TRAIN_BITS, (size_t)m * (size_t)dense_row_words(n) * 4);
-                if (!(c.same_train_rows && cx.dense.fits(ws, m, dense_row_words(n), guess))) {
-                    set_train_bits(probe, cx, c, m, n, dense_ok, side.on(), guess, false, false, flat_early ? ent_masked : nullptr);
-                    side.mark(SIDE_ROWS_AND_PACKS); side.mark(SIDE_ROWS_FOR_POS);
-                    bits_early = true; bits_early_masked = guess; masked_from_bits = flat_early;
-                }
-            }
-            side.await(SIDE_CHECKS_DONE, stream); pos.await(POS_MAXIMA_DONE, stream);
-            HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
-            if (attempt == 0 && flat_early) {
-                // The scores of the test entries (k_pos_scores_flat) depend on the inputs and on the users' flags alone: they run on the
-                // positives' stream beside the read-back and the host's work behind it.  They index the item factors by the test items, so
-                // they follow the index checks (and return when those found a defect) -- and they follow the plan's last kernel and the
-                // copy: their blocks take every wave slot they find, and a plan kernel's block of 1,024 threads then waits for sixteen
-                // slots of one CU to fall free at once (measured: the read-back 0.2 ms late).  Without dense train rows k_test_masked says
-                // which test items are train items, behind the scores.
-                const hipStream_t sc = pos.fork(POS_SCORES_AFTER_COPY);
-                if (c.scores) {
-                    // (the caller's scores: which test items are train items first -- S is never read at a train item --, then the gather)
-                    hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
-                    with_score_src<T>(c.s_type, [&](auto *src) {
-                        typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
-                        hipLaunchKernelGGL((k_pos_scores_given<T, Src>), dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, (const Src *)c.S, c.lds, (const int *)ent_user, (const unsigned char *)ent_masked);
-                    });
-                } else {
-                hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pf, ent_user);
-                // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
-                if (masked_from_bits) side.await(SIDE_ROWS_FOR_POS, sc);
-                else hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan);
-                hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, ent_masked);
-                }
-                pos.mark(POS_SCORES_DONE);
-            }
-            RM_TRACE_POINT("run: plan chain + side kernels enqueued");
-            HIP_CHECK(hipStreamSynchronize(stream));
-            RM_TRACE_POINT("run: plan read back");
-            hp = *cx.pinned_plan;
-            throw_csr_defects(hp, c, cx);
-            // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
-            if (ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0) {
-                ca.allow_stream = 0; ca.check_ptr = 0; keepable = false;     // (a second plan is never kept)
-                // (attempt 0's kernels on BOTH side streams read `flags` and `plan`, which the second plan rewrites: wait for them)
-                side.sync(); pos.sync();
-                continue;
-            }
-            break;
         }
-        if (!reused) throw_csr_defects(hp, c, cx);
-        n_slots = hp.n_slots;
-        // streamed users own the last slots; the tables and their kernels cover slots [0, stream_slot0)
-        n_stream = (want_auc || ext_topk) ? hp.class_count[STREAM_CLASS] : 0;
-        stream_slot0 = n_stream > 0 ? hp.class_offset[STREAM_CLASS] : n_slots;
-        if (!reused) check_nan = scores_may_overflow();                // (a pass on a kept split assumes the kept answer until verdict())
+    }
+    // ---- the read-back's copy, behind the verdicts and the maxima of the two streams beside; behind the copy the scores by entry ----
+    // The scores of the test entries (k_pos_scores_flat) depend on the inputs and on the users' flags alone: they run on the
+    // positives' stream beside the read-back and the host's work behind it.  They index the item factors by the test items, so
+    // they follow the index checks (and return when those found a defect) -- and they follow the plan's last kernel and the
+    // copy: their blocks take every wave slot they find, and a plan kernel's block of 1,024 threads then waits for sixteen
+    // slots of one CU to fall free at once (measured: the read-back 0.2 ms late).  Without dense train rows k_test_masked says
+    // which test items are train items, behind the scores.
+    void enqueue_read_back(int attempt)
+    {
+        side.await(SIDE_CHECKS_DONE, stream); pos.await(POS_MAXIMA_DONE, stream);
+        HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
+        if (attempt == 0 && flat_early) launch_entry_scores(pos.fork(POS_SCORES_AFTER_COPY), masked_from_bits ? MASKED_BY_ROWS : MASKED_BY_KERNEL);
+    }
+    // The positives' scores by entry on `sc`, the last thing the positives' stream is given in the plan stage (POS_SCORES_DONE).  Which
+    // test items are train items (`ent_masked`) is KEPT from the pass that planned the split, a bit of the dense train rows' kernel
+    // beside the chain, or k_test_masked's answer.
+    enum EntryMasked { MASKED_KEPT, MASKED_BY_ROWS, MASKED_BY_KERNEL };
+    void launch_entry_scores(hipStream_t sc, EntryMasked from)
+    {
+        auto test_masked = [&] { hipLaunchKernelGGL(k_test_masked, dim3(cdiv(m, TM_USERS)), dim3(256), 0, sc, m, c.test_p, c.test_i, c.train_p, c.train_i, ent_user, ent_masked, plan); };
+        if (c.scores) {
+            // (the caller's scores: which test items are train items first -- S is never read at a train item --, then the gather)
+            test_masked();
+            with_score_src<T>(c.s_type, [&](auto *src) {
+                typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+                hipLaunchKernelGGL((k_pos_scores_given<T, Src>), dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pa, (const Src *)c.S, c.lds, (const int *)ent_user, (const unsigned char *)ent_masked);
+            });
+        } else {
+            hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pa, ent_user);
+            // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
+            if (from == MASKED_BY_ROWS) side.await(SIDE_ROWS_FOR_POS, sc);
+            else if (from == MASKED_BY_KERNEL) test_masked();
+            hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pa, ent_masked);
+        }
+        pos.mark(POS_SCORES_DONE);
+    }
+    bool plan_again(int attempt)            // the host's wait, the checks' verdicts, and whether the call has to be planned once more
+    {
+        RM_TRACE_POINT("run: plan chain + side kernels enqueued");
+        HIP_CHECK(hipStreamSynchronize(stream));
+        RM_TRACE_POINT("run: plan read back");
+        hp = *cx.pinned_plan;
+        throw_csr_defects(hp, c, cx);
+        // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
+        if (!(ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0)) return false;
+        ca.allow_stream = 0; ca.check_ptr = 0; keepable = false;     // (a second plan is never kept)
+        // (attempt 0's kernels on BOTH side streams read `flags` and `plan`, which the second plan rewrites: wait for them)
+        side.sync(); pos.sync();
+        return true;
     }
     // |any partial sum| <= k * max|A| * max|B|: if that is comfortably finite in T, no score is NaN / Inf
     bool scores_may_overflow()
@@ -1460,11 +1510,10 @@ struct Pipeline {
     {
         std::memset(&key, 0, sizeof(SplitKey));
         if (g_sw.no_split_cache || !use_side || c.reco || c.scores || !c.plain() || c.items_tag != 0 || !c.test_p || m <= 0) return false;
-        const void *arr[SPLIT_ARRAYS] = {c.train_p, c.train_i, c.test_p, c.test_i, c.test_v};
         const long long words[SPLIT_ARRAYS] = {(long long)m + 1, std::max<long long>(c.nnz_train, 0), (long long)m + 1, std::max<long long>(c.nnz_test, 0),
                                                c.test_v ? std::max<long long>(c.nnz_test, 0) * (long long)(sizeof(T) / 4) : 0};
         long long total = 0;
-        for (int i = 0; i < SPLIT_ARRAYS; i++) { key.arr[i] = arr[i]; key.words[i] = words[i]; total += words[i]; }
+        for (int i = 0; i < SPLIT_ARRAYS; i++) { key.arr[i] = theirs[i]; key.words[i] = words[i]; total += words[i]; }
         if (total * 4 > ((g_sw.split_cache_mb >= 0 ? g_sw.split_cache_mb : SPLIT_CACHE_DEFAULT_MB) << 20)) return false;
         key.nnz_train = c.nnz_train; key.nnz_test = c.nnz_test;
         key.m = m; key.n = n; key.k = k; key.K = K; key.elem = (int)sizeof(T); key.req = req;
@@ -1478,7 +1527,7 @@ struct Pipeline {
     // The plan stage of a pass on the kept split.  On the side stream k_split_same, the maxima and the read-back of the call's words
     // of the Plan (SIDE_VERDICT: the host's one wait, verdict()); on the positives' stream, at once, the scores of the test entries.
     // Every kernel of this pass reads the copies, so none of them waits for k_split_same.
-    void plan_reused(const PosArgs<T> &pf, const int *ent_user, const unsigned char *ent_masked, const void *const theirs[SPLIT_ARRAYS])
+    void plan_reused()
     {
         const SplitCache &kept = cx.split;
         const size_t at = offsetof(Plan, split_differs);
@@ -1498,12 +1547,7 @@ struct Pipeline {
         hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
         HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, aux));
         side.mark(SIDE_VERDICT);
-        if (flat_early) {
-            const hipStream_t sc = pos.fork(POS_PLAN_FORK);
-            hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pf, ent_user);
-            hipLaunchKernelGGL(k_pos_apply_masked<T>, dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pf, ent_masked);      // (`ent_masked`: kept)
-            pos.mark(POS_SCORES_DONE);
-        }
+        if (flat_early) launch_entry_scores(pos.fork(POS_PLAN_FORK), MASKED_KEPT);
         hints = hints && kept.hp.n_slots > 0;
         if (hints) {
             // (the kernel's two counters, zeroed here where the call's stream is idle; the launch itself follows the verdict: sweep())
@@ -1652,7 +1696,7 @@ struct Pipeline {
         if (n_stream > 0) stream_scores = ws.array<T>(WS_STREAM_SCORES, (size_t)n_stream * (size_t)stream_ld);
         if (!ext_topk) pl = ws.array<Entry<T>>(WS_PL, (size_t)n_slots * g.n_part * K);
         pst = ws.array<PartialStat<T>>(WS_PST, (size_t)n_slots * g.n_part);
-        const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
+        const unsigned n_blocks = sweep_blocks(g.n_ublocks, g.tail_ublocks, g);
         lane_lists = want_lane && !ext_topk;                     // per-lane append buffers + k_collect_topk (rm_list.hpp)
         int lane_cap = lane_lists ? P::lane_cap(K) : 0;
         if (lane_lists && g_sw.lane_cap_set > 0) lane_cap = (int)std::min<long long>(std::max<long long>(P::lane_cap(K), (g_sw.lane_cap_set + 15) / 16 * 16), (COLLECT_MAX_ENTRIES - K) / 16 * 16);
@@ -1709,14 +1753,10 @@ struct Pipeline {
         pos_score = ws.array<T>(WS_POS_SCORE, (size_t)(rows + 1) * GU);
         pos_item = ws.array<int>(WS_POS_ITEM, (size_t)(rows + 1) * GU);
         hist = ws.array<unsigned>(WS_HIST, (size_t)(rows + 1) * GU);
-        T *pos_tmp = ws.array<T>(WS_POS_TMP, (size_t)std::max<long long>(c.nnz_test, 1));
+        if (!flat_early) fill_pos_args();                      // (the scores by slot: nothing has asked for the arguments yet)
         pos_order = ws.array<int>(WS_POS_ORDER, (size_t)std::max<long long>(c.nnz_test, 1));
-        PosArgs<T> pa{m, n, k, c.A, c.lda, c.B, c.ldb, c.train_p, c.train_i, c.test_p, c.test_i,
-                      flags, user_nslots, uslot_base, slot_index, grow, pos_tmp, pos_order, pos_score, pos_item, GU};
-        pa.noise_row = c.noise_row; pa.noise_row0 = c.noise_row0; pa.noise_E = c.noise_E; pa.noise_ld = c.noise_ld;
-        pa.noise_flag = c.noise_flag; pa.plan = plan;
-        if (sizeof(T) == 4)
-            pa.pos_key = (unsigned long long *)ws.get(WS_POS_KEY, 8 * ((size_t)std::max<long long>(c.nnz_test, 1) + 8));
+        pa.user_nslots = user_nslots; pa.uslot_base = uslot_base; pa.slot_index = slot_index; pa.grow = grow;
+        pa.pos_order = pos_order; pa.pos_score = pos_score; pa.pos_item = pos_item; pa.gu = GU;
         // Scores of the test entries: by entry (k_pos_scores_flat, launched beside the plan chain: every lane busy) unless the call
         // evaluates a few of its users only -- then a wavefront per slot is less work.
         const bool flat = flat_early;
@@ -1767,10 +1807,9 @@ struct Pipeline {
             HIP_CHECK(hipEventRecord(c.flags_event, stream));
         }
         HIP_CHECK(hipEventRecord(cx.ev[EV_PREP_END], stream));
-        double *tm = cx.timings;
         if (n_slots == 0) {
             HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
-            tm[4] = 0; tm[5] = 0; tm[6] = 0; tm[7] = 0;
+            cx.sweep_shape(0, 0, 0, 0, -1);
             return;
         }
         if (c.scores) {
@@ -1784,11 +1823,10 @@ struct Pipeline {
             check_launch(hipGetLastError());
             RM_TRACE_POINT("run: score rows enqueued");
             HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
-            tm[4] = 1; tm[5] = 1; tm[6] = n_stream; tm[7] = 0;
-            cx.timed_slots = n_slots; cx.total_slots = n_slots;
+            cx.sweep_shape(1, 1, n_stream, 0, n_slots);
             return;
         }
-        const unsigned n_blocks = (unsigned)((g.n_ublocks - g.tail_ublocks) * g.n_splits + g.tail_ublocks * g.tail_splits);
+        const unsigned n_blocks = sweep_blocks(g.n_ublocks, g.tail_ublocks, g);
         if (hints && merged && thr_shared) launch_hints();
         if (g.u_split > 0) {
             // Depth split: the two launches run side by side on two streams so that neither pays a partially filled last round of its own.
@@ -1803,9 +1841,9 @@ struct Pipeline {
             sb.tail_ublocks = g.tail_ublocks - sl.tail_ublocks;
             sl.pend_cap = g.pend_cap;  sl.pend_off = 0;
             sl.sync_off = (int)(g.lds_l - SYNC_BYTES);
-            dispatch_sweep(want_auc, false, false, g.nsub, NG, dim3((unsigned)((n_ublocks - u_split - sb.tail_ublocks) * g.n_splits + sb.tail_ublocks * g.tail_splits)), g.lds_total, side.fork(SIDE_SWEEP_FORK), sb);
+            dispatch_sweep(want_auc, false, false, g.nsub, NG, dim3(sweep_blocks(sb.n_ublocks, sb.tail_ublocks, g)), g.lds_total, side.fork(SIDE_SWEEP_FORK), sb);
             side.mark(SIDE_SWEEP_DEEP_DONE);
-            dispatch_sweep(want_auc, false, true, g.nsub, NG, dim3((unsigned)((u_split - sl.tail_ublocks) * g.n_splits + sl.tail_ublocks * g.tail_splits)), g.lds_l, stream, sl);
+            dispatch_sweep(want_auc, false, true, g.nsub, NG, dim3(sweep_blocks(sl.n_ublocks, sl.tail_ublocks, g)), g.lds_l, stream, sl);
             side.await(SIDE_SWEEP_DEEP_DONE, stream);
             side.enabled = use_side;
         } else {
@@ -1822,9 +1860,7 @@ struct Pipeline {
             collect = true;
             collect_g = CollectGeom{sa.ublock0, sa.n_ublocks, g.n_splits, g.tail_ublocks, g.tail_splits, g.nsub, GU, P::lanes_per_user, sa.lane_cap, g.part_extra ? g.n_part - 1 : -1};
         }
-        tm[4] = g.u_split > 0 ? 2 : 1; tm[5] = g.n_splits; tm[6] = n_blocks; tm[7] = (double)g.lds_total;
-        cx.timed_slots = n_slots;
-        cx.total_slots = n_slots;
+        cx.sweep_shape(g.u_split > 0 ? 2 : 1, g.n_splits, n_blocks, (double)g.lds_total, n_slots);
     }
 
     // ---- lists from the caller's scores (row_topk): k_topk_rows in the place of preparation, sweep and finalisation -- a block per
@@ -1842,11 +1878,9 @@ struct Pipeline {
         HIP_CHECK(hipGetLastError());
         RM_TRACE_POINT("run: row top-K enqueued");
         HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
-        double *tm = cx.timings;
         hipFuncAttributes at{};
         HIP_CHECK(hipFuncGetAttributes(&at, kernel));
-        tm[4] = 1; tm[5] = 1; tm[6] = m; tm[7] = (double)at.sharedSizeBytes;
-        cx.timed_slots = hp.n_slots; cx.total_slots = hp.n_slots;
+        cx.sweep_shape(1, 1, m, (double)at.sharedSizeBytes, hp.n_slots);
     }
 
     int stream_parts() const { return (int)cdiv(n, STREAM_RANK_THREADS * STREAM_RANK_ITEMS); }
@@ -2237,7 +2271,7 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
     HIP_CHECK(hipMemcpyAsync(n_flagged_host, &plan->n_noise_flagged, sizeof(int), hipMemcpyDeviceToHost, stream));
     auto tail = [=, &cx]() -> bool {
         HIP_CHECK(hipStreamSynchronize(stream));
-        cx.timings[4] = 0;
+        cx.timings[Ctx::TM_LAUNCHES] = 0;
         const int n_flagged = *n_flagged_host - n_beside;               // what the first pass's k_finalize flagged on top (top-K in the zone)
         if (n_flagged <= 0) return false;
         Call<T> c = c0;
@@ -3491,12 +3525,12 @@ extern "C" int rm_get_timings(double *out, int n)
         cx->stage_ms(ms);
     }
     for (int i = 0; i < 4; i++) cx->timings[i] = cx->acc[i] + ms[i];
-    const int cnt = n < 12 ? n : 12;
-    for (int i = 0; i < cnt && i < 8; i++) out[i] = cx->timings[i];
-    if (cnt > 8) out[8] = cx->timed_slots;
-    if (cnt > 9) out[9] = cx->total_slots;
-    if (cnt > 10) out[10] = cx->split_reused;
-    if (cnt > 11) out[11] = (cx->hints_ran && cx->ev_recorded && cx->hint_counts) ? cx->hint_counts[0] : 0;      // (EV_END is behind the counts' copy)
+    const int cnt = n < Ctx::TM_COUNT ? n : Ctx::TM_COUNT;
+    for (int i = 0; i < cnt && i < Ctx::TM_TIMED_SLOTS; i++) out[i] = cx->timings[i];
+    if (cnt > Ctx::TM_TIMED_SLOTS) out[Ctx::TM_TIMED_SLOTS] = cx->timed_slots;
+    if (cnt > Ctx::TM_TOTAL_SLOTS) out[Ctx::TM_TOTAL_SLOTS] = cx->total_slots;
+    if (cnt > Ctx::TM_SPLIT_REUSED) out[Ctx::TM_SPLIT_REUSED] = cx->split_reused;
+    if (cnt > Ctx::TM_HINTED) out[Ctx::TM_HINTED] = (cx->hints_ran && cx->ev_recorded && cx->hint_counts) ? cx->hint_counts[0] : 0;      // (EV_END is behind the counts' copy)
     return cnt;
 }
 
