@@ -18,7 +18,7 @@
  * 2-byte scores, so a batch is about a quarter larger than the fp32 call's.  Device entries: lists up to k_top = 1024 keep no row
  * per user and never answer RM_ERR_NOMEM; beyond, and for metrics, the masked row that is kept is fp32 -- the bytes per row in the
  * RM_ERR_NOMEM message are the fp32 call's.
- * There is no 16-bit form of the factor entries, of the outputs, or of fp64.
+ * The 16-bit form of the factor entries is recometrics_hip_half_factors.h; there is none of the outputs or of fp64.
  */
 #ifndef RECOMETRICS_HIP_HALF_H
 #define RECOMETRICS_HIP_HALF_H

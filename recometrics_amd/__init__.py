@@ -251,14 +251,56 @@ def _cpu_tensor_as_array(torch, scores, kind):
     return scores.view(torch.int16).numpy().view(np.uint16) if kind == "bf16" else scores.numpy()
 
 
+def _factor_tensors(A, B):
+    """(torch, kind) when `A` and `B` are torch tensors of one dtype on one device -- kind as `_tensor_kind` states it --, (None, None)
+    when neither is a tensor; a tensor next to anything else, two dtypes, two devices or a dtype without an entry are a ValueError"""
+    torch = _torch_if_tensor(A) or _torch_if_tensor(B)
+    if torch is None:
+        return None, None
+    _fail_if(not (isinstance(A, torch.Tensor) and isinstance(B, torch.Tensor)), "'A' and 'B' must both be torch tensors, or both NumPy arrays.")
+    _fail_if(A.dtype != B.dtype, "'A' and 'B' must have the same dtype when they are torch tensors.")
+    _fail_if(A.device != B.device, "'A' and 'B' must be on the same device.")
+    kind = _tensor_kind(torch, A)
+    _fail_if(kind is None, "'A' and 'B' must be float16, bfloat16, float32 or float64 tensors.")
+    return torch, kind
+
+
+def _fail_if_biases_on_half(kind, item_biases):
+    _fail_if(isinstance(kind, str) and item_biases is not None,
+             "'item_biases' cannot be added to 16-bit factors (a bias column in 16 bits would be rounded): pass float32 factors.")
+
+
+def _fold_item_biases_tensors(torch, A, B, item_biases, n_items):
+    """`_fold_item_biases` for float32 / float64 tensors: the two columns are appended on the tensors' device"""
+    if isinstance(item_biases, torch.Tensor):
+        item_biases = item_biases.detach().cpu().numpy()
+    assert isinstance(item_biases, np.ndarray)
+    _fail_if(item_biases.ndim > 2, "'item_biases' should be a 1-d array.")
+    item_biases = item_biases.reshape(-1)
+    _fail_if(item_biases.shape[0] == 0, "'item_biases' is empty.")
+    _fail_if(item_biases.shape[0] < n_items, "Number of items in 'item_biases' must match with 'X_test'.")
+    if item_biases.shape[0] > n_items:
+        warn("'item_biases' has more items than 'X_test'.")
+        item_biases = item_biases[:n_items]
+    bias = torch.from_numpy(np.ascontiguousarray(item_biases)).to(device=B.device, dtype=B.dtype).reshape(-1, 1)
+    return torch.cat([A, torch.ones((A.shape[0], 1), dtype=A.dtype, device=A.device)], dim=1), torch.cat([B, bias], dim=1)
+
+
+def _half_or_typed(kind, A, B, dtype):
+    """the factors of a host call, row-major with their leading dimensions: 16-bit arrays as they are, anything else in `dtype`"""
+    if not isinstance(kind, str):
+        A, B = A.astype(dtype, copy=False), B.astype(dtype, copy=False)
+    return _row_major_with_ld(A) + _row_major_with_ld(B)
+
+
 class _DeviceCall:
-    """What the two from-scores functions share when `scores` is a GPU tensor: the call runs on the tensor's device and on torch's
-    current stream there, through the device entries; index arrays are uploaded, outputs are device tensors, and the stream is
-    synchronised before they come back as NumPy arrays."""
+    """What the functions share when `scores`, or the factors `A` and `B`, are GPU tensors: the call runs on the tensor's device and
+    on torch's current stream there, through the device entries; index arrays are uploaded, outputs are device tensors, and the stream
+    is synchronised before they come back as NumPy arrays."""
 
     def __init__(self, torch, scores, kind):
         self.torch, self.kind, self.device = torch, kind, scores.device
-        self.S = scores.detach() if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.detach().contiguous()
+        self.S = self.row_major(scores)
         self.out_dtype = torch.float64 if kind is np.float64 else torch.float32
         self.np_dtype = np.float64 if kind is np.float64 else np.float32
         self.keep = []                                              # the uploads live until the stream has been synchronised
@@ -274,15 +316,28 @@ class _DeviceCall:
     def empty(self, shape, dtype=None):
         return self.torch.empty(shape, dtype=dtype or self.out_dtype, device=self.device)
 
+    @staticmethod
+    def row_major(t):
+        """`t` as it is when its rows are dense and ascend (a row stride is passed on), else one contiguous copy"""
+        t = t.detach()
+        return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
     def run(self, entry, half_entry, **arguments):
         """`entry(dtype, S, lds, m, n, ...)` of the binding, or its 16-bit form `half_entry(kind, ...)`, on the current stream; waits"""
+        self._run(entry, half_entry, (self.S.data_ptr(), self.S.stride(0), self.S.shape[0], self.S.shape[1]), arguments)
+
+    def run_factors(self, entry, half_entry, B, **arguments):
+        """the same for the factor entries, `entry(dtype, A, lda, B, ldb, m, n, k, ...)`: the call was made over `A`"""
+        A, B = self.S, self.row_major(B)
+        self._run(entry, half_entry, (A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), A.shape[0], B.shape[0], A.shape[1]), arguments)
+
+    def _run(self, entry, half_entry, source, arguments):
         torch = self.torch
         with torch.cuda.device(self.device):
             _binding.load()
             _binding.set_device(self.device.index if self.device.index is not None else torch.cuda.current_device())
             stream = torch.cuda.current_stream()
-            (half_entry if isinstance(self.kind, str) else entry)(
-                self.kind, self.S.data_ptr(), self.S.stride(0), self.S.shape[0], self.S.shape[1], stream=stream.cuda_stream, **arguments)
+            (half_entry if isinstance(self.kind, str) else entry)(self.kind, *source, stream=stream.cuda_stream, **arguments)
             stream.synchronize()
         self.keep.clear()
 
@@ -321,6 +376,14 @@ def calc_reco_metrics(
     cut-off.  Returns a ``pandas.DataFrame`` with one row per user (``as_df=True``) or a dict of arrays plus the
     entry ``"K"``.  Users that cannot be evaluated get NaN.
 
+    ``A`` and ``B`` may also be ``torch.Tensor``s of one dtype -- float16, bfloat16, float32 or float64 -- on one device.  16-bit
+    factors are read where they lie, every factor widened exactly to float32 on the device
+    (``include/recometrics_hip_half_factors.h``), and the result is float32: the same values the call returns for the tensors
+    converted to float32, without the float32 copies.  CPU tensors go through the host entries without a copy; GPU tensors go through
+    the device entries on their device and on torch's current stream there, which is synchronised before the result comes back in
+    the usual form.  ``item_biases`` cannot be added to 16-bit factors (the bias column would be rounded).  NumPy ``float16`` arrays
+    keep going through float64.
+
     Differences from the CPU reference, all documented in DESIGN.md: ``nthreads`` only drives the host-side sort of a matrix
     whose rows turn out unsorted (the reference sorts ``X_train`` / ``X_test`` in place; here they are never modified);
     ``break_ties_with_noise`` adds the reference's own noise (``std::mt19937(seed + user)``, reproduced bit for bit on
@@ -341,7 +404,10 @@ def calc_reco_metrics(
         A = np.ones((X_test.shape[0], 1), dtype=np.float64)
         B = np.ascontiguousarray(item_biases, dtype=np.float64).reshape(-1, 1)
         item_biases = None
-    assert isinstance(A, np.ndarray) and isinstance(B, np.ndarray)
+    torch, kind = _factor_tensors(A, B)
+    if torch is None:
+        assert isinstance(A, np.ndarray) and isinstance(B, np.ndarray)
+    _fail_if_biases_on_half(kind, item_biases)
     assert issparse(X_test)
     n_users, n_items = X_test.shape
     _fail_if(n_users >= _INT32_MAX, "Number of test user is larger than maximum supported.")
@@ -349,8 +415,11 @@ def calc_reco_metrics(
     _fail_if(X_test.data.shape[0] == 0, "'X_test' is empty.")
     A, B = _check_factors(A, B, n_users, n_items)
 
-    # float32 only when BOTH factor matrices are float32 (reference :469)
-    dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
+    # float32 only when BOTH factor matrices are float32 (reference :469); 16-bit tensors are evaluated in float32
+    if torch:
+        dtype = np.float64 if kind is np.float64 else np.float32
+    else:
+        dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
 
     # ---- train matrix ----
     X_train, consider_cold_start = _train_or_empty(X_train, X_test, dtype, consider_cold_start)
@@ -378,14 +447,31 @@ def calc_reco_metrics(
     _fail_if(k > n_items, "'k' should be smaller than the number of items.")
 
     if item_biases is not None:
-        A, B = _fold_item_biases(A, B, item_biases, n_items, dtype)
+        A, B = _fold_item_biases_tensors(torch, A, B, item_biases, n_items) if torch else _fold_item_biases(A, B, item_biases, n_items, dtype)
 
     # ---- normalise storage: factors in `dtype` and row-major; nothing is copied that already has the right type and layout ----
     split = _split_arrays(X_train, X_test, n_users, dtype)
-    A, lda = _row_major_with_ld(A.astype(dtype, copy=False))
-    B, ldb = _row_major_with_ld(B.astype(dtype, copy=False))
+    if torch and A.is_cuda:
+        want = {short: requested[name] for name, short, _ in _METRICS}
+        arrays = _binding._metric_outs(None, want, n_users, k, bool(cumulative), dtype)
+        call = _DeviceCall(torch, A, kind)
+        on_device = [call.empty(a.size) if a.size else None for a in arrays]
+        train_p, train_i, test_p, test_i, test_v = split
+        call.run_factors(_binding.calc_metrics_device, _binding.calc_metrics_half_device, B,
+                         train_p=call.put(train_p), train_i=call.put(train_i), nnz_train=int(train_i.shape[0]),
+                         test_p=call.put(test_p), test_i=call.put(test_i), test_v=call.put(test_v), nnz_test=int(test_i.shape[0]),
+                         k_metrics=k, outs=[t.data_ptr() if t is not None else 0 for t in on_device], cumulative=bool(cumulative),
+                         break_ties_with_noise=bool(break_ties_with_noise), consider_cold_start=bool(consider_cold_start),
+                         min_items_pool=min_items_pool, min_pos_test=min_pos_test, seed=seed)
+        for a, t in zip(arrays, on_device):
+            if t is not None:
+                a.reshape(-1)[:] = t.cpu().numpy()
+        return _metrics_result(arrays, None, None, k, as_df, cumulative, rename_k)
+    if torch:
+        A, B = _cpu_tensor_as_array(torch, A, kind), _cpu_tensor_as_array(torch, B, kind)
+    A, lda, B, ldb = _half_or_typed(kind, A, B, dtype)
     want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
-    arrays = _binding.calc_metrics(
+    arrays = (_binding.calc_metrics_half if isinstance(kind, str) else _binding.calc_metrics)(
         A, lda, B, ldb, *split, k, want, bool(cumulative), bool(break_ties_with_noise),
         bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, seed, outs=outs)
     return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
@@ -512,6 +598,8 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
     ``A=None, B=None`` with ``item_biases`` ranks by the biases alone; ``item_biases`` next to factors is added to the scores).
     ``X_train``: optional sparse user-item matrix of the items to leave out per user (any SciPy format; never modified), ``None``
     leaves nothing out.  ``users``: optional integer array -- lists for these rows of ``A`` / ``X_train`` only, in this order.
+    ``A`` and ``B`` may be ``torch.Tensor``s as in :func:`calc_reco_metrics` (16-bit factors: list scores in float32; ``users`` gathers
+    the rows of ``A`` where it lies).
 
     Returns ``(ids, scores, status)``: ``ids`` [len(users) or users, k] int32, ``scores`` of the same shape (``None`` with
     ``return_scores=False``), ``status`` int32 per row: 0 = the first ``min(k, candidates)`` places hold the list and the others
@@ -527,7 +615,10 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
         n_rows = X_train.shape[0] if X_train is not None else int(np.max(np.asarray(users), initial=-1)) + 1
         A = np.ones((n_rows, 1), dtype=np.float64)
         item_biases = None
-    assert isinstance(A, np.ndarray) and isinstance(B, np.ndarray)
+    torch, kind = _factor_tensors(A, B)
+    if torch is None:
+        assert isinstance(A, np.ndarray) and isinstance(B, np.ndarray)
+    _fail_if_biases_on_half(kind, item_biases)
     _fail_if(A.ndim != 2, "'A' must be a 2-dimensional array.")
     _fail_if(B.ndim != 2, "'B' must be a 2-dimensional array.")
     _fail_if(A.shape[1] != B.shape[1], "'A' and 'B' must have the same number of columns.")
@@ -542,19 +633,31 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
         _fail_if(X_train.shape[1] != n_items, "Number of items in 'B' and 'X_train' does not match.")
         _fail_if(X_train.shape[0] != n_users, "Number of users in 'A' and 'X_train' does not match.")
     users = _user_selection(users, n_users, "A")
-    dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
+    if torch:
+        dtype = np.float64 if kind is np.float64 else np.float32
+    else:
+        dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
     if item_biases is not None:
-        A, B = _fold_item_biases(A, B, item_biases, n_items, dtype)
+        A, B = _fold_item_biases_tensors(torch, A, B, item_biases, n_items) if torch else _fold_item_biases(A, B, item_biases, n_items, dtype)
 
     # ---- everything above raises before the library is touched ----
-    if users is not None:
-        A = A[users]
+    if users is not None:                                    # (the one gather; a tensor's on its own device)
+        A = A[torch.from_numpy(users).to(A.device)] if torch else A[users]
     excl_p, excl_i = _exclusion_csr(X_train, users)
     if A.shape[0] == 0:
         return _no_lists(k, dtype, return_scores)
-    A, lda = _row_major_with_ld(A.astype(dtype, copy=False))
-    B, ldb = _row_major_with_ld(B.astype(dtype, copy=False))
-    return _binding.recommend(A, lda, B, ldb, excl_p, excl_i, k, bool(return_scores))
+    if torch and A.is_cuda:
+        call = _DeviceCall(torch, A, kind)
+        m = A.shape[0]
+        idx, sc, st = call.empty((m, k), torch.int32), call.empty((m, k)) if return_scores else None, call.empty((m,), torch.int32)
+        call.run_factors(_binding.recommend_device, _binding.recommend_half_device, B,
+                         excl_p=call.put(excl_p), excl_i=call.put(excl_i), nnz_excl=0 if excl_i is None else int(excl_i.shape[0]), k_top=k,
+                         idx=idx.data_ptr(), score=sc.data_ptr() if return_scores else 0, status=st.data_ptr())
+        return idx.cpu().numpy(), sc.cpu().numpy() if return_scores else None, st.cpu().numpy()
+    if torch:
+        A, B = _cpu_tensor_as_array(torch, A, kind), _cpu_tensor_as_array(torch, B, kind)
+    A, lda, B, ldb = _half_or_typed(kind, A, B, dtype)
+    return (_binding.recommend_half if isinstance(kind, str) else _binding.recommend)(A, lda, B, ldb, excl_p, excl_i, k, bool(return_scores))
 
 
 def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_scores=True):

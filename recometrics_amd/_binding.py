@@ -75,6 +75,10 @@ HALF_KINDS = ("f16", "bf16")
 HALF_SIGNATURES = {"rm_" + request + "_scores" + form + "_" + kind: (pieces(_SCORES, host), _ci)
                    for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
                    for kind in HALF_KINDS}
+# include/recometrics_hip_half_factors.h: the four factor entries with A and B in 16-bit patterns of one kind; again the _f32 rows
+HALF_FACTOR_SIGNATURES = {"rm_" + request + form + "_" + kind: (pieces(_FACTORS, host), _ci)
+                          for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
+                          for kind in HALF_KINDS}
 # test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
 TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
@@ -105,6 +109,7 @@ def load():
                 "recometrics_amd: %s is missing -- build it with `python -m recometrics_amd.build` "
                 "(there is no CPU fallback)" % _LIB_PATH)
         _lib = _declare(_declare(C.CDLL(_LIB_PATH), SIGNATURES), HALF_SIGNATURES, HALF_SIGNATURES)
+        _declare(_lib, HALF_FACTOR_SIGNATURES, HALF_FACTOR_SIGNATURES)
         for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -277,11 +282,11 @@ def csr_sort_rows(indptr, indices, data, nthreads=0):
 
 
 def _invoke(entry, dtype, **values):
-    """Calls `entry`'s symbol for `dtype` (or, "f16" / "bf16", its symbol of HALF_SIGNATURES) with `values` given by the header's
+    """Calls `entry`'s symbol for `dtype` (or, "f16" / "bf16", its symbol of HALF_SIGNATURES / HALF_FACTOR_SIGNATURES) with `values` given by the header's
     parameter names, in the order SIGNATURES states; a status other than 0 raises (`_raise`).  A missing name is a KeyError and an unknown one a TypeError, both before the call."""
     if dtype in HALF_KINDS:
         name = entry + "_" + dtype
-        params = HALF_SIGNATURES[name][0]
+        params = (HALF_SIGNATURES if name in HALF_SIGNATURES else HALF_FACTOR_SIGNATURES)[name][0]
     else:
         name = entry + ("_f32" if dtype == np.float32 else "_f64")
         params = SIGNATURES[name][0]
@@ -394,6 +399,50 @@ def recommend_scores_half_device(kind, S, lds, m, n, excl_p, excl_i, nnz_excl, k
     """`recommend_scores_device` for 16-bit scores: `kind` "f16" / "bf16" in the place of the dtype, `score` float32"""
     assert kind in HALF_KINDS
     _invoke("rm_recommend_scores_dev", kind, S=_dp(S), lds=lds, m=m, n=n, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
+            nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
+
+
+def calc_metrics_half(A, lda, B, ldb, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
+                      break_ties_with_noise, consider_cold_start, min_items_pool, min_pos_test, nthreads, seed, outs=None):
+    """`calc_metrics` for 16-bit factors (rm_calc_metrics_f16 / _bf16): `A` [m, k] and `B` [n, k] float16 arrays, or bfloat16 bit
+    patterns as uint16, both of one kind, with leading dimensions in 2-byte elements; `test_v` and the ten outputs are float32."""
+    kind = half_kind(A)
+    if half_kind(B) != kind:
+        raise TypeError("A and B must hold the same 16-bit type")
+    m, k = A.shape
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, np.float32)
+    _invoke("rm_calc_metrics", kind, A=_p(A), lda=lda, B=_p(B), ldb=ldb, m=m, n=B.shape[0], k=k,
+            break_ties_with_noise=int(bool(break_ties_with_noise)), nthreads=nthreads, seed=seed,
+            **_metrics_values(_p, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+    return outs
+
+
+def calc_metrics_half_device(kind, A, lda, B, ldb, m, n, k, train_p, train_i, nnz_train, test_p, test_i, test_v, nnz_test,
+                             k_metrics, outs, cumulative=False, break_ties_with_noise=False, consider_cold_start=True,
+                             min_items_pool=2, min_pos_test=1, seed=1, stream=0):
+    """`calc_metrics_device` for 16-bit factors: `kind` "f16" / "bf16" in the place of the dtype, everything else float32"""
+    assert kind in HALF_KINDS
+    _invoke("rm_calc_metrics_dev", kind, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, nnz_train=nnz_train, nnz_test=nnz_test,
+            break_ties_with_noise=int(bool(break_ties_with_noise)), seed=seed, stream=_dp(stream),
+            **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+
+
+def recommend_half(A, lda, B, ldb, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
+    """`recommend` for 16-bit factors (rm_recommend_f16 / _bf16): `A`, `B` as in `calc_metrics_half`; the list scores are float32."""
+    kind = half_kind(A)
+    if half_kind(B) != kind:
+        raise TypeError("A and B must hold the same 16-bit type")
+    m, k = A.shape
+    idx, sc, st = _list_outs(m, k_top, np.float32, return_scores)
+    _invoke("rm_recommend", kind, A=_p(A), lda=lda, B=_p(B), ldb=ldb, m=m, n=B.shape[0], k=k, Xexcl_csr_p=_host_excl_p(excl_p), Xexcl_csr_i=_p(excl_i),
+            k_top=k_top, idx=_p(idx), score=_p(sc), status=_p(st), nthreads=int(nthreads))
+    return idx, sc, st
+
+
+def recommend_half_device(kind, A, lda, B, ldb, m, n, k, excl_p, excl_i, nnz_excl, k_top, idx, score, status, stream=0):
+    """`recommend_device` for 16-bit factors: `kind` "f16" / "bf16" in the place of the dtype, `score` float32"""
+    assert kind in HALF_KINDS
+    _invoke("rm_recommend_dev", kind, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
             nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
 
 

@@ -25,10 +25,11 @@ KERNEL_UNITS = {"collect4096_f32": (["-DRM_KERNELS=4", "-DRM_F64=0"], ("rm_final
                 "collect4096_f64": (["-DRM_KERNELS=4", "-DRM_F64=1"], ("rm_finalize.hpp",)),
                 "collect_f32": (["-DRM_KERNELS=3", "-DRM_F64=0"], ("rm_finalize.hpp",)),
                 "collect_f64": (["-DRM_KERNELS=3", "-DRM_F64=1"], ("rm_finalize.hpp",)),
-                "prep": (["-DRM_KERNELS=0"], ("rm_prep.hpp",)),
+                "prep": (["-DRM_KERNELS=0"], ("rm_prep.hpp", "rm_half.hpp")),
+                "prep_half": (["-DRM_KERNELS=6"], ("rm_prep.hpp", "rm_half.hpp")),
                 "finalize": (["-DRM_KERNELS=1"], ("rm_finalize.hpp",)),
-                "rows": (["-DRM_KERNELS=2"], ("rm_noise.hpp", "rm_scores.hpp", "rm_rowtopk.hpp", "rm_prep.hpp", "rm_finalize.hpp")),
-                "rows_half": (["-DRM_KERNELS=5"], ("rm_scores.hpp", "rm_rowtopk.hpp", "rm_prep.hpp", "rm_finalize.hpp"))}
+                "rows": (["-DRM_KERNELS=2"], ("rm_noise.hpp", "rm_scores.hpp", "rm_rowtopk.hpp", "rm_prep.hpp", "rm_half.hpp", "rm_finalize.hpp")),
+                "rows_half": (["-DRM_KERNELS=5"], ("rm_scores.hpp", "rm_rowtopk.hpp", "rm_prep.hpp", "rm_half.hpp", "rm_finalize.hpp"))}
 KERNEL_HEADERS = sorted({h for _, hdrs in KERNEL_UNITS.values() for h in hdrs} | {"rm_kernel_units.hpp"})
 # (the pool starts the units in this order: the longest compiles first)
 SOURCES = ([KERNEL_SRC + ":" + u for u in KERNEL_UNITS] + ["rm_lib.hip"] + [SWEEP_SRC + ":" + u for u in SWEEP_UNITS]

@@ -11,6 +11,7 @@
 //               3  k_collect_topk, lane buffers of 512 and 1024 entries          x fp32 / fp64
 //               4  k_collect_topk, lane buffers of 4096 entries                  x fp32 / fp64
 //               5  rm_scores.hpp, rm_rowtopk.hpp with 16-bit scores (f16 / bf16 in, fp32 behind the load)
+//               6  rm_prep.hpp's readers of raw A / B with 16-bit factors (f16 / bf16 in, fp32 behind the load)
 #include <hip/hip_runtime.h>
 
 #if RM_KERNELS == 0
@@ -43,8 +44,11 @@
 #include "rm_scores.hpp"
 #include "rm_rowtopk.hpp"
 #define RM_UNIT_KERNELS(X) RM_SCORES_KERNELS_HALF(X) RM_ROWTOPK_KERNELS_HALF(X)
+#elif RM_KERNELS == 6
+#include "rm_prep.hpp"
+#define RM_UNIT_KERNELS(X) RM_PREP_KERNELS_HALF(X)
 #else
-#error "RM_KERNELS: 0 .. 5"
+#error "RM_KERNELS: 0 .. 6"
 #endif
 
 namespace rm {

@@ -27,6 +27,7 @@
 
 #include "../../include/recometrics_hip.h"
 #include "../../include/recometrics_hip_half.h"
+#include "../../include/recometrics_hip_half_factors.h"
 #include "rm_device.hpp"
 #include "rm_prep.hpp"
 #include "rm_launch.hpp"
@@ -181,8 +182,8 @@ std::atomic<unsigned long long> g_ws_stamp{1};
     X(WS_NOISE_FLAG, "noise_flag")              /* int[m]: users the first pass flags (zeroed by run_call; the positives' scores, k_finalize) */ \
     X(WS_NOISE_FLAG_SNAP, "noise_flag_snap")    /* int[m]: the flags when that pass launches its sweep (Pipeline::sweep, a copy) */ \
     /* ---- the host-pointer entry (HostRange): uploads, outputs on the device ---- */ \
-    X(WS_IN_B, "in_B")                          /* T[n][k]: the item factors, dense rows (HostRange's uploads; debug_scores) */ \
-    X(WS_IN_A, "in_A")                          /* T[m][k]: the range's user factors (HostRange's uploads; debug_scores) */ \
+    X(WS_IN_B, "in_B")                          /* T (or 16-bit: Request::f_type) [n][k]: the item factors, dense rows (HostRange's uploads; debug_scores) */ \
+    X(WS_IN_A, "in_A")                          /* T (or 16-bit) [m][k]: the range's user factors (HostRange's uploads; debug_scores) */ \
     X(WS_IN_TRP, "in_trp")                      /* int[m + 1]: train index pointers, rebased to the range (stage_inputs) */ \
     X(WS_IN_TEP, "in_tep")                      /* int[m + 1]: test index pointers, rebased (stage_inputs) */ \
     X(WS_IN_TRI, "in_tri")                      /* int[nnz_train of the range] (HostRange's uploads) */ \
@@ -540,7 +541,12 @@ template <class T> struct Request : Outputs<T> {
     // S[u * lds + i]; there are then no factors (A, B null, k = 0) and no tie noise.  Every evaluated user is streamed: k_score_rows copies
     // its row of S, masked, where the sweep would have written it, k_pos_scores_given gathers the test items' scores, and the
     // finalisation is the factor call's.
-    const T *A = nullptr; size_t lda = 0; const T *B = nullptr; size_t ldb = 0; int k = 0;
+    // The factors' element type `f_type` is the call's own T, or 16-bit patterns (include/recometrics_hip_half_factors.h; T is float then):
+    // A and B then hold 2-byte elements wherever they lie -- the caller's arrays, the upload buffers, the resident copies -- and the kernels
+    // that read them widen in registers (rm_prep.hpp: FactorSrc).  lda / ldb count elements; whoever steps through A or B steps by f_elem().
+    const void *A = nullptr; size_t lda = 0; const void *B = nullptr; size_t ldb = 0; int k = 0; ScoreType f_type = SCORE_SAME;
+    size_t f_elem() const { return f_type == SCORE_SAME ? sizeof(T) : 2; }
+    const void *A_from(size_t user) const { return (const char *)A + user * lda * f_elem(); }
     const void *S = nullptr; ScoreType s_type = SCORE_SAME; size_t lds = 0; bool scores = false;      // (lds in elements of S)
     size_t s_elem() const { return s_type == SCORE_SAME ? sizeof(T) : 2; }
     int m = 0, n = 0;
@@ -595,6 +601,13 @@ template <class T, class F> void with_score_src(ScoreType st, F f)
     if (st == SCORE_SAME) return f((const T *)nullptr);
     if constexpr (std::is_same<T, float>::value) return st == SCORE_F16 ? f((const F16Bits *)nullptr) : f((const BF16Bits *)nullptr);
     throw RmError{RM_ERR_INVALID, "16-bit scores are evaluated in fp32"};
+}
+// f(Src *): the same for a request's factors (Request::f_type; rm_prep.hpp: FactorSrc)
+template <class T, class F> void with_factor_src(ScoreType ft, F f)
+{
+    if (ft == SCORE_SAME) return f((const T *)nullptr);
+    if constexpr (std::is_same<T, float>::value) return ft == SCORE_F16 ? f((const F16Bits *)nullptr) : f((const BF16Bits *)nullptr);
+    throw RmError{RM_ERR_INVALID, "16-bit factors are evaluated in fp32"};
 }
 template <class T> struct Call : Request<T>, PassRole<T> {
     Call() = default;
@@ -759,7 +772,9 @@ void dispatch_sweep(bool auc, bool dump, bool llds, int nsub, int NG, dim3 grid,
     check_launch(rc);
 }
 
-inline void pack_operands(const float *A, size_t lda, const float *B, size_t ldb, int n, int k, int NG, int tile_items, const int *slot_user,
+// (Src: float, or 16-bit patterns -- the images are the same fp32 images)
+template <class Src>
+inline void pack_operands(const Src *A, size_t lda, const Src *B, size_t ldb, int n, int k, int NG, int tile_items, const int *slot_user,
                           int n_slots, float4 *Ap, long long ap, float4 *Bp, long long bp, hipStream_t stream, bool items = true)
 {
     if (items) {
@@ -769,20 +784,40 @@ inline void pack_operands(const float *A, size_t lda, const float *B, size_t ldb
         // the library that takes more than 64 KB; a refusal falls back to the kernel that needs no LDS)
         bool tiled = lds <= 96 * 1024 && tiles * NG * 2 * tile_items == bp;
         if (tiled && lds > 48 * 1024)
-            tiled = hipFuncSetAttribute((const void *)k_pack_items_tile<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+            tiled = hipFuncSetAttribute((const void *)k_pack_items_tile<float, Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
         if (tiled) {
-            hipLaunchKernelGGL(k_pack_items_tile<float>, dim3((unsigned)tiles), dim3(256), lds, stream, B, ldb, n, k, NG, tile_items, Bp);
+            hipLaunchKernelGGL((k_pack_items_tile<float, Src>), dim3((unsigned)tiles), dim3(256), lds, stream, B, ldb, n, k, NG, tile_items, Bp);
             if (hipGetLastError() != hipSuccess) tiled = false;
         }
-        if (!tiled) hipLaunchKernelGGL(k_pack_items<float>, dim3(cdiv(bp, 256)), dim3(256), 0, stream, B, ldb, n, k, NG, tile_items, Bp, bp);
+        if (!tiled) hipLaunchKernelGGL((k_pack_items<float, Src>), dim3(cdiv(bp, 256)), dim3(256), 0, stream, B, ldb, n, k, NG, tile_items, Bp, bp);
     }
-    if (ap > 0) hipLaunchKernelGGL(k_pack_users<float>, dim3(cdiv(ap, 256)), dim3(256), 0, stream, A, lda, k, NG, slot_user, n_slots, Ap, ap);
+    if (ap > 0) hipLaunchKernelGGL((k_pack_users<float, Src>), dim3(cdiv(ap, 256)), dim3(256), 0, stream, A, lda, k, NG, slot_user, n_slots, Ap, ap);
 }
 inline void pack_operands(const double *A, size_t lda, const double *B, size_t ldb, int n, int k, int NG, int, const int *slot_user,
                           int n_slots, double2 *Ap, long long ap, double2 *Bp, long long bp, hipStream_t stream, bool items = true)
 {
     if (items) hipLaunchKernelGGL(k_pack_items64<double>, dim3(cdiv(bp, 256)), dim3(256), 0, stream, B, ldb, n, k, NG, Bp, bp);
     if (ap > 0) hipLaunchKernelGGL(k_pack_users64<double>, dim3(cdiv(ap, 256)), dim3(256), 0, stream, A, lda, k, NG, slot_user, n_slots, Ap, ap);
+}
+
+// a call's factors through pack_operands / k_absmax, typed by Request::f_type
+template <class T, class PackT>
+inline void pack_call_operands(const Request<T> &c, int n, int NG, int tile_items, const int *slot_user, int n_slots, PackT *Ap, long long ap,
+                               PackT *Bp, long long bp, hipStream_t stream, bool items)
+{
+    with_factor_src<T>(c.f_type, [&](auto *src) {
+        typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+        pack_operands((const Src *)c.A, c.lda, (const Src *)c.B, c.ldb, n, c.k, NG, tile_items, slot_user, n_slots, Ap, ap, Bp, bp, stream, items);
+    });
+}
+template <class T>
+inline void launch_absmax(ScoreType f_type, const void *X, size_t ld, long long rows, int k, unsigned blocks, hipStream_t stream,
+                          unsigned long long *amax_bits, int *nonfinite)
+{
+    with_factor_src<T>(f_type, [&](auto *src) {
+        typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+        hipLaunchKernelGGL((k_absmax<T, Src>), dim3(blocks), dim3(256), 0, stream, (const Src *)X, ld, rows, k, amax_bits, nonfinite);
+    });
 }
 
 constexpr size_t LDS_LIMIT = 160 * 1024;
@@ -1421,8 +1456,8 @@ struct Pipeline {
         const hipStream_t aux = side.behind(SIDE_PLAN_FORK), aux2 = pos.behind(POS_PLAN_FORK);
         if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
         side.mark(SIDE_CHECKS_DONE);
-        if (!c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux2, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
-        if (!items_known && !c.scores) hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux2, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
+        if (!c.scores) launch_absmax<T>(c.f_type, c.A, c.lda, (long long)m, k, 512, aux2, &plan->amax_a, &plan->nonfinite);
+        if (!items_known && !c.scores) launch_absmax<T>(c.f_type, c.B, c.ldb, (long long)n, k, 1024, aux2, &plan->amax_b, &plan->nonfinite_b);
         pos.mark(POS_MAXIMA_DONE);
         if (attempt != 0) return;                                      // (the second plan makes neither again)
         // (the user of every test entry, for the positives' scores by entry: index pointers only)
@@ -1469,7 +1504,10 @@ struct Pipeline {
                 hipLaunchKernelGGL((k_pos_scores_given<T, Src>), dim3(cdiv(c.nnz_test, 256)), dim3(256), 0, sc, pa, (const Src *)c.S, c.lds, (const int *)ent_user, (const unsigned char *)ent_masked);
             });
         } else {
-            hipLaunchKernelGGL(k_pos_scores_flat<T>, dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pa, ent_user);
+            with_factor_src<T>(c.f_type, [&](auto *src) {
+                typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+                hipLaunchKernelGGL((k_pos_scores_flat<T, Src>), dim3(cdiv(c.nnz_test, POSF_WAVES * WAVE)), dim3(POSF_WAVES * WAVE), 0, sc, pa, (const int *)ent_user);
+            });
             // test items that are train items: +inf, once the answer (the dense train rows' kernel, or k_test_masked) is there
             if (from == MASKED_BY_ROWS) side.await(SIDE_ROWS_FOR_POS, sc);
             else if (from == MASKED_BY_KERNEL) test_masked();
@@ -1543,8 +1581,8 @@ struct Pipeline {
         ss.plan = plan;
         const unsigned blocks = (unsigned)std::min<long long>(SPLIT_SAME_BLOCKS, cdiv(cdiv(longest, 4), SPLIT_SAME_THREADS));
         hipLaunchKernelGGL(k_split_same, dim3(blocks), dim3(SPLIT_SAME_THREADS), 0, aux, ss);
-        hipLaunchKernelGGL(k_absmax<T>, dim3(512), dim3(256), 0, aux, c.A, c.lda, (long long)m, k, &plan->amax_a, &plan->nonfinite);
-        hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, aux, c.B, c.ldb, (long long)n, k, &plan->amax_b, &plan->nonfinite_b);
+        launch_absmax<T>(c.f_type, c.A, c.lda, (long long)m, k, 512, aux, &plan->amax_a, &plan->nonfinite);
+        launch_absmax<T>(c.f_type, c.B, c.ldb, (long long)n, k, 1024, aux, &plan->amax_b, &plan->nonfinite_b);
         HIP_CHECK(hipMemcpyAsync(cx.pinned_plan, plan, sizeof(Plan), hipMemcpyDeviceToHost, aux));
         side.mark(SIDE_VERDICT);
         if (flat_early) launch_entry_scores(pos.fork(POS_PLAN_FORK), MASKED_KEPT);
@@ -1573,7 +1611,10 @@ struct Pipeline {
         const long long waves = cdiv(m, users_per_wave);
         HintArgs<T, ThrT> ha{m, n, k, K, c.A, c.lda, c.B, c.ldb, c.train_p, c.train_i, flags, user_nslots, uslot_base, slot_index,
                              (const Entry<T> *)merged, thr_shared, hint_counts_dev};
-        hipLaunchKernelGGL((k_hint_bounds<T, ThrT>), dim3(cdiv(waves, HINT_WAVES)), dim3(HINT_WAVES * WAVE), 0, stream, ha);
+        with_factor_src<T>(c.f_type, [&](auto *src) {
+            typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+            hipLaunchKernelGGL((k_hint_bounds<T, ThrT, Src>), dim3(cdiv(waves, HINT_WAVES)), dim3(HINT_WAVES * WAVE), 0, stream, ha);
+        });
         cx.split.hint_judge = true; cx.hints_ran = true;
     }
     // The host's wait of a pass on the kept split, in front of the sweep's launch (the device is busy with the positives' chain):
@@ -1678,7 +1719,7 @@ struct Pipeline {
         // Only the sweep reads the packed images: with a side stream they are made there, behind the dense train rows and beside the
         // positives' kernels (120 us of BASELINE C2's preparation that sat in front of k_pos_scores); the sweep's launch waits for both.
         const bool packs_side = use_side && want_auc && cx.side_stream != nullptr;
-        pack_operands(c.A, c.lda, c.B, c.ldb, n, k, NG, tile_items, slot_user, n_slots, Ap, ap_units, Bp, bp_units, packs_side ? side.on() : stream, !items_packed);
+        pack_call_operands<T>(c, n, NG, tile_items, slot_user, n_slots, Ap, ap_units, Bp, bp_units, packs_side ? side.on() : stream, !items_packed);
         if (packs_side) side.mark(SIDE_ROWS_AND_PACKS);                 // (behind the rows, when they were launched: the sweep waits for both)
         cx.packed.set(ws, c.items_tag, tile_items, NG);
         launch_top_values();
@@ -1739,7 +1780,7 @@ struct Pipeline {
             const long long units = P::items_units(sample_S / TILE_ITEMS, NG);
             typename P::PackT *Bs = (typename P::PackT *)ws.get(WS_SAMPLE_ITEMS, 16 * (size_t)units);
             void *Ls = ws.array<typename P::ListT>(WS_SAMPLE_LISTS, (size_t)g.n_ublocks * 8 * GU * (2 + 32));
-            pack_operands(c.A, c.lda, c.B, c.ldb, sample_S, k, NG, TILE_ITEMS, slot_user, 0, Ap, 0, Bs, units, stream, true);
+            pack_call_operands<T>(c, sample_S, NG, TILE_ITEMS, slot_user, 0, Ap, 0, Bs, units, stream, true);
             seed_from_sample<T>(sa, ws, sample_S, NG, n_slots, g.n_ublocks, stream, Bs, Ls);
         }
         RM_TRACE_POINT("run: preparation enqueued");
@@ -1785,8 +1826,11 @@ struct Pipeline {
             // (the scores are the last thing on the positives' stream: whoever is not on it waits for them)
             pos.await(POS_SCORES_DONE, stream);
         } else {
-            if (n_stream > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(nsc, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, ps, pb, sc_user, sc_chunk, nsc);
-            if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_scores<T>, dim3(cdiv(stream_slot0, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
+            with_factor_src<T>(c.f_type, [&](auto *src) {
+                typedef std::remove_cv_t<std::remove_pointer_t<decltype(src)>> Src;
+                if (n_stream > 0) hipLaunchKernelGGL((k_pos_scores<T, Src>), dim3(cdiv(nsc, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, ps, pb, (const int *)sc_user, (const int *)sc_chunk, nsc);
+                if (stream_slot0 > 0) hipLaunchKernelGGL((k_pos_scores<T, Src>), dim3(cdiv(stream_slot0, POSS_WAVES)), dim3(POSS_WAVES * WAVE), 0, stream, pa, (const int *)slot_user, (const int *)slot_chunk, stream_slot0);
+            });
         }
         if (n_stream > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)nsc * WAVE, 256)), dim3(256), 0, ps, pb, sc_user, sc_chunk, nsc);
         if (stream_slot0 > 0) hipLaunchKernelGGL(k_pos_place<T>, dim3(cdiv((long long)stream_slot0 * WAVE, 256)), dim3(256), 0, stream, pa, slot_user, slot_chunk, stream_slot0);
@@ -2213,7 +2257,7 @@ void run_call(const Call<T> &c_in, hipStream_t stream, Ctx &cx, std::function<bo
         for (long long b0 = 0; b0 < m; b0 += g.cap) {
             const int mb = (int)std::min<long long>(g.cap, m - b0);
             Call<T> c = c0;
-            c.A = c0.A + (size_t)b0 * c0.lda; c.m = mb; c.train_p = c0.train_p + b0; c.test_p = c0.test_p + b0; c.user0 = c0.user0 + b0;
+            c.A = c0.A_from((size_t)b0); c.m = mb; c.train_p = c0.train_p + b0; c.test_p = c0.test_p + b0; c.user0 = c0.user0 + b0;
             c.outputs() = c0.from_user((size_t)b0, lay.per, c0.K);
             if (c0.only_users) c.only_users = c0.only_users + b0;
             unsigned *D = ws.array<unsigned>(WS_NOISE_DRAWS, (size_t)mb * (size_t)g.d_ld);
@@ -2446,9 +2490,10 @@ template <class T> struct ItemUpload {
             sh->cv.wait(sl, [&] { return sh->copies_pending <= 0; });
         } else if (!reported) sh->copy_done();
     }
-    void run(T *dB, int device, hipStream_t up)
+    void run(void *dB, int device, hipStream_t up)
     {
         const int n = h.n, k = h.k;
+        const size_t fe = h.f_elem();                                // (16-bit factors travel as they are: half the bytes, here and between the shards)
         if (h.scores) {                                              // no item factors: the shards' handshake alone
             if (sh && shard == 0) { std::lock_guard<std::mutex> sl(sh->mu); sh->ready = true; sh->failed = false; sh->src = dB; sh->src_device = device; published = true; sh->cv.notify_all(); }
             else if (sh) { reported = true; sh->copy_done(); }
@@ -2457,8 +2502,8 @@ template <class T> struct ItemUpload {
         if (!sh || shard == 0) {
             // (dense rows: ONE plain copy -- a 2-D copy of pageable memory goes through a staging buffer and a second,
             // device-side pass: 1.1 ms more for BASELINE C2's A and B)
-            hipError_t e = h.ldb == (size_t)k ? hipMemcpyAsync(dB, h.B, sizeof(T) * (size_t)n * k, hipMemcpyHostToDevice, up)
-                                              : hipMemcpy2DAsync(dB, sizeof(T) * k, h.B, sizeof(T) * h.ldb, sizeof(T) * k, n, hipMemcpyHostToDevice, up);
+            hipError_t e = h.ldb == (size_t)k ? hipMemcpyAsync(dB, h.B, fe * (size_t)n * k, hipMemcpyHostToDevice, up)
+                                              : hipMemcpy2DAsync(dB, fe * k, h.B, fe * h.ldb, fe * k, n, hipMemcpyHostToDevice, up);
             if (sh) {
                 if (e == hipSuccess) e = hipStreamSynchronize(up);
                 std::lock_guard<std::mutex> sl(sh->mu);
@@ -2474,7 +2519,7 @@ template <class T> struct ItemUpload {
                 if (sh->failed) throw RmError{RM_ERR_HIP, "upload of the item factors failed on the first device"};
             }
             enable_peer_access(device, sh->src_device);
-            HIP_CHECK(hipMemcpyPeerAsync(dB, device, sh->src, sh->src_device, sizeof(T) * (size_t)n * k, up));
+            HIP_CHECK(hipMemcpyPeerAsync(dB, device, sh->src, sh->src_device, fe * (size_t)n * k, up));
             HIP_CHECK(hipStreamSynchronize(up));                      // the source buffer is shard 0's: tell it when we are done with it
             reported = true;
             sh->copy_done();
@@ -2508,7 +2553,8 @@ template <class T> struct HostRange {
     // stage_inputs()
     long long tr0 = 0, te0 = 0, nnz_tr = 0, nnz_te = 0;
     void *dS[2] = {nullptr, nullptr}; const void *cur_S = nullptr;        // the caller's scores: upload buffers of the batches, the one of the batch being enqueued
-    T *dB = nullptr, *dA = nullptr, *dtev = nullptr; int *dtrp = nullptr, *dtep = nullptr, *dtri = nullptr, *dtei = nullptr;
+    char *dB = nullptr, *dA = nullptr;                                // the factors' resident copies, dense rows of k elements of Request::f_elem() bytes
+    T *dtev = nullptr; int *dtrp = nullptr, *dtep = nullptr, *dtri = nullptr, *dtei = nullptr;
     std::vector<int> rb;                                              // rebased index pointers (only when the range does not start at 0)
     const int *trp = nullptr, *tep = nullptr;
     Outputs<T> d_rank;                                                // the ranking outputs of the range on the device (rm_rank_*, lists)
@@ -2542,13 +2588,14 @@ template <class T> struct HostRange {
         }
         up = cx.up_stream;
         if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(up, cx.done, 0));   // the previous call on this context may still read the buffers
-        // item factors, dense rows of k
-        dB = ws.array<T>(WS_IN_B, (size_t)n * k);
+        // item factors, dense rows of k (typed where they are T: the guard mode's poison is the type's)
+        const auto factors = [&](WsBuf id, size_t elems) { return h.f_type == SCORE_SAME ? (char *)ws.array<T>(id, elems) : ws.array<char>(id, elems * h.f_elem()); };
+        dB = factors(WS_IN_B, (size_t)n * k);
         if (m <= 0) { items.run(dB, cx.device, up); HIP_CHECK(hipStreamSynchronize(up)); return false; }
         // this range's users: factors, CSR rows with the index pointers rebased to the range
         tr0 = h.train_p[u0]; te0 = h.test_p[u0];
         nnz_tr = (long long)h.train_p[u0 + m] - tr0; nnz_te = (long long)h.test_p[u0 + m] - te0;
-        dA = ws.array<T>(WS_IN_A, (size_t)m * k);
+        dA = factors(WS_IN_A, (size_t)m * k);
         dtrp = ws.array<int>(WS_IN_TRP, (size_t)(m + 1));
         dtep = h.reco ? nullptr : ws.array<int>(WS_IN_TEP, (size_t)(m + 1));
         dtri = ws.array<int>(WS_IN_TRI, (size_t)std::max<long long>(nnz_tr, 1));
@@ -2626,10 +2673,12 @@ template <class T> struct HostRange {
             const char *src = (const char *)h.S + ((size_t)u0 + b0) * h.lds * es;
             if (h.lds == (size_t)n) HIP_CHECK(hipMemcpyAsync(dS[bi & 1], src, es * (size_t)(b1 - b0) * n, hipMemcpyHostToDevice, up));
             else HIP_CHECK(hipMemcpy2DAsync(dS[bi & 1], es * n, src, es * h.lds, es * n, (size_t)(b1 - b0), hipMemcpyHostToDevice, up));
-        } else
-        if (h.lda == (size_t)k) HIP_CHECK(hipMemcpyAsync(dA + (size_t)b0 * k, h.A + ((size_t)u0 + b0) * k, sizeof(T) * (size_t)(b1 - b0) * k, hipMemcpyHostToDevice, up));
-        else HIP_CHECK(hipMemcpy2DAsync(dA + (size_t)b0 * k, sizeof(T) * k, h.A + ((size_t)u0 + b0) * h.lda, sizeof(T) * h.lda, sizeof(T) * k, (size_t)(b1 - b0),
-                                        hipMemcpyHostToDevice, up));
+        } else {
+            const size_t fe = h.f_elem();
+            char *dst = dA + (size_t)b0 * k * fe; const void *src = h.A_from((size_t)u0 + b0);
+            if (h.lda == (size_t)k) HIP_CHECK(hipMemcpyAsync(dst, src, fe * (size_t)(b1 - b0) * k, hipMemcpyHostToDevice, up));
+            else HIP_CHECK(hipMemcpy2DAsync(dst, fe * k, src, fe * h.lda, fe * k, (size_t)(b1 - b0), hipMemcpyHostToDevice, up));
+        }
         const long long r0 = trp[b0], r1 = trp[b1], e0 = tep[b0], e1 = tep[b1];      // range-relative entries of the batch
         if (r1 > r0) HIP_CHECK(hipMemcpyAsync(dtri + r0, h.train_i + tr0 + r0, sizeof(int) * (size_t)(r1 - r0), hipMemcpyHostToDevice, up));
         if (e1 > e0) HIP_CHECK(hipMemcpyAsync(dtei + e0, h.test_i + te0 + e0, sizeof(int) * (size_t)(e1 - e0), hipMemcpyHostToDevice, up));
@@ -2650,7 +2699,7 @@ template <class T> struct HostRange {
     Call<T> batch_call(long long b0, int mb) const
     {
         Call<T> c(h);
-        c.A = dA + (size_t)b0 * k; c.lda = k; c.B = dB; c.ldb = k; c.m = mb;
+        c.A = dA + (size_t)b0 * k * h.f_elem(); c.lda = k; c.B = dB; c.ldb = k; c.m = mb;
         if (h.scores) { c.S = cur_S; c.lds = (size_t)n; c.A = nullptr; c.B = nullptr; }
         c.train_p = dtrp + b0; c.train_i = dtri; c.nnz_train = nnz_tr;
         c.test_p = dtep ? dtep + b0 : nullptr; c.test_i = dtei; c.test_v = dtev; c.nnz_test = nnz_te;
@@ -3110,6 +3159,13 @@ template <class T> Request<T> from_factors(const T *A, size_t lda, const T *B, s
     r.A = A; r.lda = lda; r.B = B; r.ldb = ldb; r.k = k;
     return r;
 }
+// 16-bit factors (recometrics_hip_half_factors.h): bit patterns, lda / ldb in 2-byte elements; the request is an fp32 request otherwise
+inline Request<float> from_factors_half(const uint16_t *A, size_t lda, const uint16_t *B, size_t ldb, int k, ScoreType type)
+{
+    Request<float> r;
+    r.A = A; r.lda = lda; r.B = B; r.ldb = ldb; r.k = k; r.f_type = type;
+    return r;
+}
 template <class T> Request<T> from_scores(const T *S, size_t lds)
 {
     Request<T> r;
@@ -3380,6 +3436,68 @@ extern "C" int rm_recommend_scores_dev_##SUFFIX(                                
 
 RM_HALF_ENTRY(f16, SCORE_F16)
 RM_HALF_ENTRY(bf16, SCORE_BF16)
+
+// ---- 16-bit factor matrices (include/recometrics_hip_half_factors.h): the four factor entries of fp32 with A, B in IEEE binary16 / bfloat16 ----
+#define RM_HALF_FACTOR_ENTRY(SUFFIX, TYPE)                                                                              \
+extern "C" int rm_calc_metrics_##SUFFIX(                                                                                \
+    const uint16_t *A, size_t lda, const uint16_t *B, size_t ldb, int32_t m, int32_t n, int32_t k,                      \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,                                                           \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const float *Xtest_csr,                                     \
+    int32_t k_metrics, int cumulative, int break_ties_with_noise,                                                       \
+    float *p_at_k, float *tp_at_k, float *r_at_k, float *ap_at_k, float *tap_at_k, float *ndcg_at_k, float *hit_at_k,   \
+    float *rr_at_k, float *roc_auc, float *pr_auc, int consider_cold_start, int32_t min_items_pool,                     \
+    int32_t min_pos_test, int32_t nthreads, uint64_t seed)                                                              \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        host_entry<float>(metrics_request<float>(from_factors_half(A, lda, B, ldb, k, TYPE), m, n, Xtrain_csr_p,        \
+                                         Xtrain_csr_i, 0, Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0, k_metrics,            \
+                                         cumulative, break_ties_with_noise,                                             \
+                                         {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,     \
+                                          roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, seed),   \
+                      nthreads);                                                                                        \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_calc_metrics_dev_##SUFFIX(                                                                            \
+    const uint16_t *A, size_t lda, const uint16_t *B, size_t ldb, int32_t m, int32_t n, int32_t k,                      \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,                                        \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const float *Xtest_csr, int64_t nnz_test,                   \
+    int32_t k_metrics, int cumulative, int break_ties_with_noise,                                                       \
+    float *p_at_k, float *tp_at_k, float *r_at_k, float *ap_at_k, float *tap_at_k, float *ndcg_at_k, float *hit_at_k,   \
+    float *rr_at_k, float *roc_auc, float *pr_auc, int consider_cold_start, int32_t min_items_pool,                     \
+    int32_t min_pos_test, uint64_t seed, void *stream)                                                                  \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        dev_entry<float>(metrics_request<float>(from_factors_half(A, lda, B, ldb, k, TYPE), m, n, Xtrain_csr_p,         \
+                                        Xtrain_csr_i, nnz_train, Xtest_csr_p, Xtest_csr_i, Xtest_csr, nnz_test,         \
+                                        k_metrics, cumulative, break_ties_with_noise,                                   \
+                                        {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k, rr_at_k,      \
+                                         roc_auc, pr_auc}, consider_cold_start, min_items_pool, min_pos_test, seed),    \
+                     stream);                                                                                           \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_##SUFFIX(                                                                                   \
+    const uint16_t *A, size_t lda, const uint16_t *B, size_t ldb, int32_t m, int32_t n, int32_t k,                      \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
+    int32_t *idx, float *score, int32_t *status, int32_t nthreads)                                                      \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        host_entry<float>(lists_request<float>(from_factors_half(A, lda, B, ldb, k, TYPE), m, n, Xexcl_csr_p,           \
+                                               Xexcl_csr_i, 0, k_top, idx, score, status), nthreads);                   \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_dev_##SUFFIX(                                                                               \
+    const uint16_t *A, size_t lda, const uint16_t *B, size_t ldb, int32_t m, int32_t n, int32_t k,                      \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
+    int32_t *idx, float *score, int32_t *status, void *stream)                                                          \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        dev_entry<float>(lists_request<float>(from_factors_half(A, lda, B, ldb, k, TYPE), m, n, Xexcl_csr_p,            \
+                                              Xexcl_csr_i, nnz_excl, k_top, idx, score, status), stream);               \
+    });                                                                                                                 \
+}
+
+RM_HALF_FACTOR_ENTRY(f16, SCORE_F16)
+RM_HALF_FACTOR_ENTRY(bf16, SCORE_BF16)
 
 extern "C" int rm_debug_scores_f32(const float *A, size_t lda, const float *B, size_t ldb, int32_t m, int32_t n, int32_t k, float *out)
 {

@@ -5,9 +5,35 @@
 // sweep's epilogue.
 #pragma once
 #include "rm_device.hpp"
+#include "rm_half.hpp"
 #include "rm_kernel_units.hpp"
 
 namespace rm {
+
+// ---- the element type of the caller's factor matrices (Src) apart from the type everything is computed in (T) --------------------
+// rm_*_{f16,bf16} (include/recometrics_hip_half_factors.h): A and B hold 16-bit patterns, read where they lie and widened EXACTLY to
+// fp32 in registers (rm_half.hpp); T is float then.  Every kernel that reads raw A / B takes Src -- k_absmax, the operand packing,
+// FlatDot, k_pos_scores -- and everything behind them sees fp32: the packed images the sweep reads are the fp32 call's to the bit,
+// and a positive's score is the same k-ordered fp32 fma chain over the widened values.
+// A 16-byte load (Raw) holds VE factors; a Raw of zero bits is VE factors of +0 in every format.
+template <class T, class Src> struct FactorSrc;
+template <class T> struct FactorSrc<T, T> {
+    static constexpr int VE = 16 / (int)sizeof(T);
+    typedef T Elem; typedef T Raw __attribute__((ext_vector_type(16 / sizeof(T))));
+    static __device__ __forceinline__ T widen(T x) { return x; }
+    static __device__ __forceinline__ T get(const Raw &r, int e) { return r[e]; }
+    static __device__ __forceinline__ void put(Raw &r, int e, T x) { r[e] = x; }
+};
+template <class Half> struct FactorSrcHalf {
+    static constexpr int VE = 8;
+    typedef unsigned Elem; typedef unsigned Raw __attribute__((ext_vector_type(4)));       // (Elem: what a Raw is made of)
+    static __device__ __forceinline__ float widen(Half x) { return half_lo(Half{}, (unsigned)x.b); }
+    static __device__ __forceinline__ float get(const Raw &r, int e) { return (e & 1) ? half_hi(Half{}, r[e >> 1]) : half_lo(Half{}, r[e >> 1]); }
+    // (into a Raw that started as zero bits: an element load of the paths that cannot take 16 bytes at once)
+    static __device__ __forceinline__ void put(Raw &r, int e, Half x) { r[e >> 1] |= (unsigned)x.b << (16 * (e & 1)); }
+};
+template <> struct FactorSrc<float, F16Bits> : FactorSrcHalf<F16Bits> {};
+template <> struct FactorSrc<float, BF16Bits> : FactorSrcHalf<BF16Bits> {};
 
 struct ClassifyArgs {
     int m, n, K;
@@ -420,9 +446,11 @@ __global__ __launch_bounds__(1024) void k_block_tables(Plan *p, const unsigned c
 
 // max |x| over a row-major matrix (rows x k, leading dimension ld) + a non-finite flag: lets the host prove that no
 // score can overflow, in which case the sweep skips its NaN scan.
-template <class T>
-__global__ void k_absmax(const T *X, size_t ld, long long rows, int k, unsigned long long *amax_bits, int *nonfinite)
+// (16-bit factors, Src: the bound and the flag are taken over the WIDENED values -- they are the fp32 call's on the widened matrix)
+template <class T, class Src = T>
+__global__ void k_absmax(const Src *X, size_t ld, long long rows, int k, unsigned long long *amax_bits, int *nonfinite)
 {
+    typedef FactorSrc<T, Src> FS;
     double mx = 0.; bool bad = false;
     const long long total = rows * k;
     auto take = [&](T xv) {
@@ -432,8 +460,8 @@ __global__ void k_absmax(const T *X, size_t ld, long long rows, int k, unsigned 
         mx = ax > mx ? ax : mx;
     };
     if (ld == (size_t)k && (((size_t)X) & 15) == 0) {      // dense rows: one flat array, 16-byte loads, no division per element
-        constexpr int V = 16 / (int)sizeof(T);
-        typedef T VecT __attribute__((ext_vector_type(16 / sizeof(T))));
+        constexpr int V = FS::VE;
+        typedef typename FS::Raw VecT;
         const long long nv = total / V;
         // (four loads in flight per thread: with one, 35 MB of user factors took 34 us in front of the plan read-back)
         const long long stride = (long long)gridDim.x * blockDim.x;
@@ -444,12 +472,12 @@ __global__ void k_absmax(const T *X, size_t ld, long long rows, int k, unsigned 
             #pragma unroll
             for (int u = 0; u < 4; u++)
                 #pragma unroll
-                for (int e = 0; e < V; e++) take(q[u][e]);
+                for (int e = 0; e < V; e++) take(FS::get(q[u], e));
         }
-        for (long long i = nv * V + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) take(X[i]);
+        for (long long i = nv * V + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) take(FS::widen(X[i]));
     } else {
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
-            take(X[(size_t)(i / k) * ld + (i % k)]);
+            take(FS::widen(X[(size_t)(i / k) * ld + (i % k)]));
     }
     #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) { const double o = __shfl_xor(mx, d); mx = o > mx ? o : mx; }
@@ -735,8 +763,8 @@ template <class T> __global__ void k_fill(T *p, T v, long long count)
 // read covers 4 steps, so a lane wants the 4 factors k = 8g + 2i + h (i = 0..3) contiguous:
 //   packed[tile][g][h][row][i] = X[tile*ROWS + row][8g + 2i + h]        (zero for k >= k or row >= rows)
 // The k order of the accumulate chain is unchanged: step 4g+i adds k = 8g+2i (h = 0) then k = 8g+2i+1 (h = 1).
-template <class T>
-__global__ void k_pack_items(const T *B, size_t ldb, int n, int k, int NG, int tile_items, float4 *Bp, long long total_f4)
+template <class T, class Src = T>
+__global__ void k_pack_items(const Src *B, size_t ldb, int n, int k, int NG, int tile_items, float4 *Bp, long long total_f4)
 {
     const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // one float4 of the image per thread
     if (o >= total_f4) return;
@@ -748,9 +776,9 @@ __global__ void k_pack_items(const T *B, size_t ldb, int n, int k, int NG, int t
     const long long item = tile * tile_items + row;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (item < n) {
-        const T *src = B + (size_t)item * ldb;
+        const Src *src = B + (size_t)item * ldb;
         #pragma unroll
-        for (int i = 0; i < 4; i++) { const int kk = 8 * g + 2 * i + h; if (kk < k) v[i] = (float)src[kk]; }
+        for (int i = 0; i < 4; i++) { const int kk = 8 * g + 2 * i + h; if (kk < k) v[i] = (float)FactorSrc<T, Src>::widen(src[kk]); }
     }
     Bp[o] = make_float4(v[0], v[1], v[2], v[3]);
 }
@@ -760,8 +788,10 @@ __global__ void k_pack_items(const T *B, size_t ldb, int n, int k, int NG, int t
 // instruction: at 10 M items x 128 factors -- BASELINE C4 -- 10 GB moved in 3.8 ms.)  Row stride in LDS = 8 NG + 1 words: the
 // lanes of the second phase walk down a column without bank conflicts.  Used while a tile fits (pack_items_tile_lds <= 96 KB).
 inline size_t pack_items_tile_lds(int NG, int tile_items) { return sizeof(float) * (size_t)tile_items * (size_t)(8 * NG + 1); }
-template <class T>
-__global__ __launch_bounds__(256) void k_pack_items_tile(const T *B, size_t ldb, int n, int k, int NG, int tile_items, float4 *Bp)
+// (16-bit factors: a row of k factors is 2 k bytes and consecutive lanes still run along the factors -- a wavefront's load covers a
+// whole 128-byte line of a row; the LDS image and everything behind it are fp32)
+template <class T, class Src = T>
+__global__ __launch_bounds__(256) void k_pack_items_tile(const Src *B, size_t ldb, int n, int k, int NG, int tile_items, float4 *Bp)
 {
     extern __shared__ float pk_tile[];                          // [tile_items][8 NG + 1]
     const int kw = 8 * NG, ld = kw + 1, tid = threadIdx.x;
@@ -774,7 +804,7 @@ __global__ __launch_bounds__(256) void k_pack_items_tile(const T *B, size_t ldb,
             const int idx = base + q * 256 + tid;
             const int row = idx / kw, col = idx - row * kw;
             const long long item = item0 + row;
-            v[q] = (idx < total && item < n && col < k) ? (float)B[(size_t)item * ldb + col] : 0.f;
+            v[q] = (idx < total && item < n && col < k) ? (float)FactorSrc<T, Src>::widen(B[(size_t)item * ldb + col]) : 0.f;
         }
         #pragma unroll
         for (int q = 0; q < 8; q++) {
@@ -793,8 +823,8 @@ __global__ __launch_bounds__(256) void k_pack_items_tile(const T *B, size_t ldb,
     }
 }
 
-template <class T>
-__global__ void k_pack_users(const T *A, size_t lda, int k, int NG, const int *slot_user, int n_slots,
+template <class T, class Src = T>
+__global__ void k_pack_users(const Src *A, size_t lda, int k, int NG, const int *slot_user, int n_slots,
                              float4 *Ap, long long total_f4)
 {
     const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -807,9 +837,9 @@ __global__ void k_pack_users(const T *A, size_t lda, int k, int NG, const int *s
     const long long slot = group * GROUP_USERS + ul;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (slot < n_slots) {
-        const T *src = A + (size_t)slot_user[slot] * lda;
+        const Src *src = A + (size_t)slot_user[slot] * lda;
         #pragma unroll
-        for (int i = 0; i < 4; i++) { const int kk = 8 * g + 2 * i + h; if (kk < k) v[i] = (float)src[kk]; }
+        for (int i = 0; i < 4; i++) { const int kk = 8 * g + 2 * i + h; if (kk < k) v[i] = (float)FactorSrc<T, Src>::widen(src[kk]); }
     }
     Ap[o] = make_float4(v[0], v[1], v[2], v[3]);
 }
@@ -890,7 +920,7 @@ template <> __device__ __forceinline__ double chain_dot<double>(const double *x,
 
 template <class T> struct PosArgs {
     int m, n, k;
-    const T *A; size_t lda; const T *B; size_t ldb;
+    const void *A; size_t lda; const void *B; size_t ldb;      // elements of the kernel's Src (FactorSrc: T, or 16-bit patterns); lda / ldb count them
     const int *train_p, *train_i, *test_p, *test_i;
     const int *flags, *user_nslots, *uslot_base, *slot_index;
     const long long *grow;
@@ -928,18 +958,26 @@ __device__ __forceinline__ double fma_chain_step(double a, double b, double s) {
 // go into a padded LDS image and each lane then walks its own row out of LDS; the user's factors ride in one register and are
 // broadcast.  (A per-lane gather -- 16 bytes of 60-odd different rows per instruction -- thrashes the vector L1.)  The accumulate
 // chain is chain_dot's: k-ordered fma from +0.  Rows that are not 16-byte aligned take element loads.
+// 16-bit factors (Src; T is float): a piece of 128 bytes is 64 factors, and it stays in LDS as it was loaded -- the same 144-byte
+// row stride, the same 16-byte stores -- so a lane reads its row back with eight 16-byte loads (row stride 9 slots of 16 bytes: the
+// sixteen lanes of a read group sit on sixteen different slots of the 256-byte bank row) and widens eight factors per load in
+// registers.  The exchange through LDS is fenced like FlatDot's.
 constexpr int POSS_WAVES = 4;                                   // wavefronts (slots) per block
-template <class T>
+template <class T, class Src = T>
 __global__ __launch_bounds__(POSS_WAVES * WAVE) void k_pos_scores(PosArgs<T> a, const int *slot_user, const int *slot_chunk, int n_slots)
 {
+    typedef FactorSrc<T, Src> FS;
+    constexpr bool HALF = sizeof(Src) != sizeof(T);             // the image holds raw dwords (two factors each) instead of T
+    typedef typename FS::Raw VT;
+    typedef typename FS::Elem L;                                // an element of the image: T, or a dword of two factors
     constexpr int PB = 128;                                     // bytes of a row per staged piece
-    constexpr int CH = PB / (int)sizeof(T);                     // factors per piece: 32 floats / 16 doubles
-    constexpr int VE = 16 / (int)sizeof(T);                     // factors per 16-byte vector
+    constexpr int CH = PB / (int)sizeof(Src);                   // factors per piece: 32 floats / 16 doubles / 64 of 16 bits
+    constexpr int VE = FS::VE;                                  // factors per 16-byte vector
+    constexpr int LV = 16 / (int)sizeof(L);                     // elements of the image per 16-byte vector
     constexpr int LPR = PB / 16;                                // lanes per row piece
     constexpr int RPI = WAVE / LPR;                             // rows covered by one load instruction: 8
-    constexpr int LD = CH + VE;                                 // padded row stride in LDS (144 B: conflict-free vector writes and row walks)
-    typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
-    __shared__ __attribute__((aligned(16))) T rows[POSS_WAVES][WAVE][LD];
+    constexpr int LD = (PB + 16) / (int)sizeof(L);              // padded row stride in LDS (144 B: conflict-free vector writes and row walks)
+    __shared__ __attribute__((aligned(16))) L rows[POSS_WAVES][WAVE][LD];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int w = blockIdx.x * POSS_WAVES + wv;
     if (w >= n_slots) return;
@@ -952,40 +990,52 @@ __global__ __launch_bounds__(POSS_WAVES * WAVE) void k_pos_scores(PosArgs<T> a, 
     const bool mine = lane < np;
     const int item = mine ? a.test_i[e] : 0;
     const bool masked = mine && ntr && in_sorted_row(a.train_i + tr0, ntr, item);
-    const T *Au = a.A + (size_t)u * a.lda;
+    const Src *Au = (const Src *)a.A + (size_t)u * a.lda, *B = (const Src *)a.B;
     const int f = lane % CH, rsub = lane / LPR, piece = lane % LPR;
-    const bool vec_ok = ((((size_t)a.B) | (a.ldb * sizeof(T))) & 15) == 0;
+    const bool vec_ok = ((((size_t)B) | (a.ldb * sizeof(Src))) & 15) == 0;
     // the row this lane helps to fetch in each of the eight load instructions of a piece (same for every piece)
-    const T *brow[WAVE / RPI];
+    const Src *brow[WAVE / RPI];
     #pragma unroll
     for (int q = 0; q < WAVE / RPI; q++) {
         const int p = q * RPI + rsub;
-        brow[q] = a.B + (size_t)__shfl(item, p < np ? p : 0) * a.ldb;
+        brow[q] = B + (size_t)__shfl(item, p < np ? p : 0) * a.ldb;
     }
     T s = 0;
     for (int k0 = 0; k0 < a.k; k0 += CH) {
-        const T av = k0 + f < a.k ? Au[k0 + f] : (T)0;
+        const T av = k0 + f < a.k ? FS::widen(Au[k0 + f]) : (T)0;
         const int e0 = k0 + piece * VE;                             // first factor of this lane's 16 bytes
         VT bv[WAVE / RPI];
         #pragma unroll
         for (int q = 0; q < WAVE / RPI; q++) {
             const int p = q * RPI + rsub;
-            VT x;
-            #pragma unroll
-            for (int i = 0; i < VE; i++) x[i] = (T)0;
+            VT x = {};                                              // (zero bits: +0 beyond k in every format)
             if (p < np && e0 < a.k) {
                 if (vec_ok && e0 + VE <= a.k) x = *(const VT *)(brow[q] + e0);
                 else {
                     #pragma unroll
-                    for (int i = 0; i < VE; i++) if (e0 + i < a.k) x[i] = brow[q][e0 + i];
+                    for (int i = 0; i < VE; i++) if (e0 + i < a.k) FS::put(x, i, brow[q][e0 + i]);
                 }
             }
             bv[q] = x;
         }
         #pragma unroll
-        for (int q = 0; q < WAVE / RPI; q++) *(VT *)&rows[wv][q * RPI + rsub][piece * VE] = bv[q];
+        for (int q = 0; q < WAVE / RPI; q++) *(VT *)&rows[wv][q * RPI + rsub][piece * LV] = bv[q];
         const int kc = min(CH, a.k - k0);
-        for (int t = 0; t < kc; t++) s = fma_chain_step(lane_bcast<T>(av, t), rows[wv][mine ? lane : 0][t], s);
+        if constexpr (!HALF) {
+            for (int t = 0; t < kc; t++) s = fma_chain_step(lane_bcast<T>(av, t), rows[wv][mine ? lane : 0][t], s);
+        } else {
+            // (the pieces change lanes through LDS: fenced, not left to the compiler's alias analysis)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+            const L *r = rows[wv][mine ? lane : 0];
+            #pragma unroll
+            for (int j = 0; j < CH / VE; j++) {
+                if (j * VE >= kc) break;                            // (wave-uniform)
+                const VT b = *(const VT *)(r + j * LV);
+                #pragma unroll
+                for (int i = 0; i < VE; i++) if (j * VE + i < kc) s = fma_chain_step(lane_bcast<T>(av, j * VE + i), FS::get(b, i), s);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // the rows are rewritten by the next chunk
+        }
     }
     if (mine && !masked && a.noise_E) {
         const long long nr = a.noise_row ? a.noise_row[u] - a.noise_row0 : u;
@@ -1105,23 +1155,30 @@ __global__ __launch_bounds__(256) void k_test_masked(int m, const int *test_p, c
 // The scores of a wavefront's 64 (user, item) pairs, one pair per lane: k_pos_scores_flat's test entries and k_hint_bounds' advised
 // items go through this one routine, so both are the sweep's scores to the bit.  `live`: the ballot of `mine`, not zero; a lane that
 // is not `mine` reads nothing and returns 0.  `rows`: the wavefront's own [WAVE][LD] of LDS.
-template <class T> struct FlatDot {
+// 16-bit factors (Src; T is float): the geometry in BYTES is unchanged -- pieces of 64 bytes, 80-byte rows (5 slots of 16 bytes: the
+// sixteen lanes of a 16-byte read group sit on sixteen different slots of the 256-byte bank row), 16-byte stores -- so a piece is 32
+// factors, four loads of eight; the image holds the patterns as loaded and both operands are widened in registers, in k order.
+template <class T, class Src = T> struct FlatDot {
+    typedef FactorSrc<T, Src> FS;
+    typedef typename FS::Raw VT;
+    typedef typename FS::Elem L;                                // an element of the image: T, or a dword of two factors
     static constexpr int PB = 64;                               // bytes of a row per staged piece
-    static constexpr int CH = PB / (int)sizeof(T);              // factors per piece: 16 floats / 8 doubles
-    static constexpr int VE = 16 / (int)sizeof(T);              // factors per 16-byte vector
+    static constexpr int CH = PB / (int)sizeof(Src);            // factors per piece: 16 floats / 8 doubles / 32 of 16 bits
+    static constexpr int VE = FS::VE;                           // factors per 16-byte vector
+    static constexpr int LV = 16 / (int)sizeof(L);              // elements of the image per 16-byte vector
     static constexpr int LPR = PB / 16;                         // lanes per row piece
     static constexpr int RPI = WAVE / LPR;                      // rows covered by one load instruction: 16
-    static constexpr int LD = CH + VE;                          // padded row stride in LDS
-    typedef T VT __attribute__((ext_vector_type(16 / sizeof(T))));
-    static __device__ __forceinline__ T run(const T *A, size_t lda, const T *B, size_t ldb, int k, int u, int item, bool mine,
-                                            unsigned long long live, T (*rows)[LD], int lane)
+    static constexpr int LD = (PB + 16) / (int)sizeof(L);       // padded row stride in LDS
+    static __device__ __forceinline__ T run(const void *A_, size_t lda, const void *B_, size_t ldb, int k, int u, int item, bool mine,
+                                            unsigned long long live, L (*rows)[LD], int lane)
     {
+        const Src *A = (const Src *)A_, *B = (const Src *)B_;
         const int rsub = lane / LPR, piece = lane % LPR;
-        const bool vec_ok = ((((size_t)B) | (ldb * sizeof(T))) & 15) == 0, avec_ok = ((((size_t)A) | (lda * sizeof(T))) & 15) == 0;
-        const T *brow[WAVE / RPI];
+        const bool vec_ok = ((((size_t)B) | (ldb * sizeof(Src))) & 15) == 0, avec_ok = ((((size_t)A) | (lda * sizeof(Src))) & 15) == 0;
+        const Src *brow[WAVE / RPI];
         #pragma unroll
         for (int q = 0; q < WAVE / RPI; q++) brow[q] = B + (size_t)__shfl(item, q * RPI + rsub) * ldb;
-        const T *Au = A + (size_t)u * lda;
+        const Src *Au = A + (size_t)u * lda;
         T s = 0;
         for (int k0 = 0; k0 < k; k0 += CH) {
             const int e0 = k0 + piece * VE;                         // first factor of this lane's 16 bytes
@@ -1129,14 +1186,12 @@ template <class T> struct FlatDot {
             #pragma unroll
             for (int q = 0; q < WAVE / RPI; q++) {
                 const int p = q * RPI + rsub;
-                VT x;
-                #pragma unroll
-                for (int i = 0; i < VE; i++) x[i] = (T)0;
+                VT x = {};                                          // (zero bits: +0 beyond k in every format)
                 if (((live >> p) & 1) && e0 < k) {
                     if (vec_ok && e0 + VE <= k) x = *(const VT *)(brow[q] + e0);
                     else {
                         #pragma unroll
-                        for (int i = 0; i < VE; i++) if (e0 + i < k) x[i] = brow[q][e0 + i];
+                        for (int i = 0; i < VE; i++) if (e0 + i < k) FS::put(x, i, brow[q][e0 + i]);
                     }
                 }
                 bv[q] = x;
@@ -1144,37 +1199,35 @@ template <class T> struct FlatDot {
             VT av[CH / VE];
             #pragma unroll
             for (int j = 0; j < CH / VE; j++) {
-                VT x;
-                #pragma unroll
-                for (int i = 0; i < VE; i++) x[i] = (T)0;
+                VT x = {};
                 const int f0 = k0 + j * VE;
                 if (mine && f0 < k) {
                     if (avec_ok && f0 + VE <= k) x = *(const VT *)(Au + f0);
                     else {
                         #pragma unroll
-                        for (int i = 0; i < VE; i++) if (f0 + i < k) x[i] = Au[f0 + i];
+                        for (int i = 0; i < VE; i++) if (f0 + i < k) FS::put(x, i, Au[f0 + i]);
                     }
                 }
                 av[j] = x;
             }
             #pragma unroll
-            for (int q = 0; q < WAVE / RPI; q++) *(VT *)&rows[q * RPI + rsub][piece * VE] = bv[q];
+            for (int q = 0; q < WAVE / RPI; q++) *(VT *)&rows[q * RPI + rsub][piece * LV] = bv[q];
             // (the pieces change lanes through LDS: fenced like k_train_bits / k_pos_place, not left to the compiler's alias analysis)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-            const T *r = rows[lane];
+            const L *r = rows[lane];
             if (k0 + CH <= k) {
                 #pragma unroll
                 for (int j = 0; j < CH / VE; j++) {
-                    const VT b = *(const VT *)(r + j * VE);
+                    const VT b = *(const VT *)(r + j * LV);
                     #pragma unroll
-                    for (int i = 0; i < VE; i++) s = fma_chain_step(av[j][i], b[i], s);
+                    for (int i = 0; i < VE; i++) s = fma_chain_step(FS::get(av[j], i), FS::get(b, i), s);
                 }
             } else {
                 #pragma unroll
                 for (int j = 0; j < CH / VE; j++) {
-                    const VT b = *(const VT *)(r + j * VE);
+                    const VT b = *(const VT *)(r + j * LV);
                     #pragma unroll
-                    for (int i = 0; i < VE; i++) if (k0 + j * VE + i < k) s = fma_chain_step(av[j][i], b[i], s);
+                    for (int i = 0; i < VE; i++) if (k0 + j * VE + i < k) s = fma_chain_step(FS::get(av[j], i), FS::get(b, i), s);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();      // the rows are rewritten by the next chunk
@@ -1184,10 +1237,10 @@ template <class T> struct FlatDot {
 };
 
 constexpr int POSF_WAVES = 4;
-template <class T>
+template <class T, class Src = T>
 __global__ __launch_bounds__(POSF_WAVES * WAVE) void k_pos_scores_flat(PosArgs<T> a, const int *ent_user)
 {
-    __shared__ __attribute__((aligned(16))) T rows[POSF_WAVES][WAVE][FlatDot<T>::LD];
+    __shared__ __attribute__((aligned(16))) typename FlatDot<T, Src>::L rows[POSF_WAVES][WAVE][FlatDot<T, Src>::LD];
     if (a.plan->csr_bad & (CSR_BAD_INDPTR | CSR_BAD_INDEX)) return;       // (the test items index the item factors)
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const long long e = (long long)a.test_p[0] + ((long long)blockIdx.x * POSF_WAVES + wv) * WAVE + lane;
@@ -1198,7 +1251,7 @@ __global__ __launch_bounds__(POSF_WAVES * WAVE) void k_pos_scores_flat(PosArgs<T
     const bool mine = in && (f & UF_ACTIVE) && !(f & UF_ONLY_NDCG);
     const unsigned long long live = __ballot(mine);
     if (!live) return;
-    T s = FlatDot<T>::run(a.A, a.lda, a.B, a.ldb, a.k, u, item, mine, live, rows[wv], lane);
+    T s = FlatDot<T, Src>::run(a.A, a.lda, a.B, a.ldb, a.k, u, item, mine, live, rows[wv], lane);
     // (whether the train row holds the item is not known here: k_pos_apply_masked overwrites those entries afterwards.  A user
     // flagged for one of them goes through an exact pass it did not need -- same results.)
     if (mine && a.noise_E) {
@@ -1243,15 +1296,15 @@ __global__ void k_pos_apply_masked(PosArgs<T> a, const unsigned char *ent_masked
 constexpr int HINT_WAVES = 4, HINT_MAX_K = 256;
 template <class T, class KeyT> struct HintArgs {
     int m, n, k, K;
-    const T *A; size_t lda; const T *B; size_t ldb;
+    const void *A; size_t lda; const void *B; size_t ldb;      // elements of the kernel's Src, as PosArgs'
     const int *train_p, *train_i, *flags, *user_nslots, *uslot_base, *slot_index;
     const Entry<T> *lists;
     KeyT *thr_shared; int *counts;
 };
-template <class T, class KeyT>
+template <class T, class KeyT, class Src = T>
 __global__ __launch_bounds__(HINT_WAVES * WAVE) void k_hint_bounds(HintArgs<T, KeyT> a)
 {
-    __shared__ __attribute__((aligned(16))) T rows[HINT_WAVES][WAVE][FlatDot<T>::LD];
+    __shared__ __attribute__((aligned(16))) typename FlatDot<T, Src>::L rows[HINT_WAVES][WAVE][FlatDot<T, Src>::LD];
     __shared__ int ids[HINT_WAVES][HINT_MAX_K];
     __shared__ T low[HINT_WAVES][WAVE];
     __shared__ int refused[HINT_WAVES][WAVE];
@@ -1288,7 +1341,7 @@ __global__ __launch_bounds__(HINT_WAVES * WAVE) void k_hint_bounds(HintArgs<T, K
         if (has && !ok) bad = 1;
         const unsigned long long live = __ballot(ok);
         if (!live) continue;
-        const T s = FlatDot<T>::run(a.A, a.lda, a.B, a.ldb, a.k, u, ok ? id : 0, ok, live, rows[wv], lane);
+        const T s = FlatDot<T, Src>::run(a.A, a.lda, a.B, a.ldb, a.k, u, ok ? id : 0, ok, live, rows[wv], lane);
         if (ok) { if (s != s || isinf(s)) bad = 1; else mn = s < mn ? s : mn; }
     }
     low[wv][lane] = mn; refused[wv][lane] = bad;
@@ -1400,7 +1453,13 @@ __global__ __launch_bounds__(PLACE_THREADS) void k_pos_place(PosArgs<T> a, const
     X(k_pos_scores<T>) X(k_pos_scores_flat<T>) X(k_pos_apply_masked<T>) X(k_hint_bounds<T, ThrT>) X(k_pos_place<T>)
 #define RM_PREP_KERNELS_F32(X) RM_PREP_KERNELS(X, float, unsigned) X(k_pack_items<float>) X(k_pack_items_tile<float>) X(k_pack_users<float>)
 #define RM_PREP_KERNELS_F64(X) RM_PREP_KERNELS(X, double, unsigned long long) X(k_pack_items64<double>) X(k_pack_users64<double>)
+// 16-bit factors under an fp32 call: every kernel that reads raw A / B, once per kind (kernel unit 6, "prep_half")
+#define RM_PREP_KERNELS_HALF_OF(X, H) \
+    X(k_absmax<float, H>) X(k_pack_items<float, H>) X(k_pack_items_tile<float, H>) X(k_pack_users<float, H>) \
+    X(k_pos_scores<float, H>) X(k_pos_scores_flat<float, H>) X(k_hint_bounds<float, unsigned, H>)
+#define RM_PREP_KERNELS_HALF(X) RM_PREP_KERNELS_HALF_OF(X, F16Bits) RM_PREP_KERNELS_HALF_OF(X, BF16Bits)
 RM_PREP_KERNELS_F32(RM_EXTERN_KERNEL)
 RM_PREP_KERNELS_F64(RM_EXTERN_KERNEL)
+RM_PREP_KERNELS_HALF(RM_EXTERN_KERNEL)
 
 } // namespace rm

@@ -28,8 +28,7 @@ template <class T> __device__ __forceinline__ T score_canonical(T x) { return x 
 // default).  Behind the widening a score is the fp32 call's score: the callbacks of walk_score_row never see Src.
 // A 16-byte load of Src holds PIECES pieces of PE = 16 / sizeof(T) scores each -- a piece is what one call of `piece` gets, and what
 // k_score_rows stores with one 16-byte store; Src == T: one piece, the load itself.
-struct F16Bits { unsigned short b; };
-struct BF16Bits { unsigned short b; };
+// (F16Bits / BF16Bits and the widening itself, half_lo / half_hi: rm_half.hpp, shared with the 16-bit factors of rm_prep.hpp)
 template <class T> struct ScoreVec {
     typedef T Aligned __attribute__((ext_vector_type(16 / sizeof(T))));
     typedef T Unaligned __attribute__((ext_vector_type(16 / sizeof(T)), aligned(sizeof(T))));
@@ -41,11 +40,6 @@ template <class T> struct ScoreSrc<T, T> {
     static __device__ __forceinline__ T widen(T x) { return x; }
     static __device__ __forceinline__ const Raw &part(const Raw &r, int) { return r; }
 };
-// the two scores of a dword, the one at the lower address first
-__device__ __forceinline__ float half_lo(F16Bits, unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)w); }
-__device__ __forceinline__ float half_hi(F16Bits, unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
-__device__ __forceinline__ float half_lo(BF16Bits, unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float half_hi(BF16Bits, unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 template <class Half> struct ScoreSrcHalf {
     static constexpr int PIECES = 2;
     typedef unsigned Raw __attribute__((ext_vector_type(4)));
