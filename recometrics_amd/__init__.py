@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _binding
 
-__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_scores", "recommend_topk", "recommend_topk_from_scores", "split_reco_train_test"]
+__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_scores", "recommend_topk", "recommend_topk_from_candidates", "recommend_topk_from_scores",
+           "split_reco_train_test"]
 __version__ = "0.1.0"
 
 # (keyword of calc_reco_metrics, name in the C-ABI order, key of the result dict) -- reference __init__.py:590-613
@@ -658,6 +659,88 @@ def recommend_topk(A, B, k=10, X_train=None, item_biases=None, users=None, retur
         A, B = _cpu_tensor_as_array(torch, A, kind), _cpu_tensor_as_array(torch, B, kind)
     A, lda, B, ldb = _half_or_typed(kind, A, B, dtype)
     return (_binding.recommend_half if isinstance(kind, str) else _binding.recommend)(A, lda, B, ldb, excl_p, excl_i, k, bool(return_scores))
+
+
+def _candidate_csr(candidates, n_users, n_items, users):
+    """(cand_p, cand_i): the int32 CSR of the candidate rows -- a SciPy sparse matrix [users, items] (values ignored) or an
+    (indptr, indices) pair --, its rows gathered by `users`"""
+    from scipy.sparse import issparse
+    if not issparse(candidates):
+        _fail_if(not (isinstance(candidates, (tuple, list)) and len(candidates) == 2), "'candidates' must be a sparse matrix or an (indptr, indices) pair.")
+        indptr, indices = (np.ascontiguousarray(x, dtype=np.int32) for x in candidates)
+        _fail_if(indptr.ndim != 1 or indices.ndim != 1, "'candidates' must be a sparse matrix or an (indptr, indices) pair.")
+        _fail_if(indptr.shape[0] != n_users + 1, "Number of users in 'A' and 'candidates' does not match.")
+        if users is None:
+            return indptr, indices                            # (as they are: the library validates them, and sorts a copy if it has to)
+        _fail_if(indptr[0] < 0 or np.any(np.diff(indptr) < 0) or indptr[-1] > indices.shape[0], "'candidates': index pointers are negative, decreasing or beyond the indices.")
+        lens = (indptr[users + 1] - indptr[users]).astype(np.int64)
+        cand_p = np.concatenate([[0], np.cumsum(lens)])
+        _fail_if(cand_p[-1] >= _INT32_MAX, "The candidate rows of 'users' hold more entries than supported.")
+        take = np.repeat(indptr[users] - cand_p[:-1], lens) + np.arange(cand_p[-1])
+        return cand_p.astype(np.int32), np.ascontiguousarray(indices[take])
+    else:
+        _fail_if(candidates.shape[0] != n_users, "Number of users in 'A' and 'candidates' does not match.")
+        _fail_if(candidates.shape[1] != n_items, "Number of items in 'B' and 'candidates' does not match.")
+    return _exclusion_csr(candidates, users)
+
+
+def recommend_topk_from_candidates(A, B, candidates, k=10, item_biases=None, users=None, return_scores=True):
+    """The ``k`` best of each user's OWN candidate items -- the shortlist of an ANN index or a first-stage model, "positives + N sampled
+    negatives", a re-ranker's pool -- by the scores and the tie rule of :func:`recommend_topk`: a user's list is what that function
+    returns when every item that is not the user's candidate is left out, at the cost of the candidates' rows instead of a sweep over
+    the catalogue.  The reference has no such call.
+
+    ``A``, ``B``, ``item_biases`` and ``users`` as in :func:`recommend_topk` (NumPy arrays, or float32 / float64 ``torch.Tensor``s: GPU
+    tensors are read where they lie, on torch's current stream; 16-bit factors are not supported here).  ``candidates``: a SciPy sparse
+    matrix ``[users, items]`` whose row ``u`` has an entry at every candidate of user ``u`` (values ignored, never modified), or the
+    ``(indptr, indices)`` pair of such a CSR matrix; an item listed twice counts once, rows need not be sorted.  ``k`` may exceed a
+    row's candidates (the list is padded) but not 1024.
+
+    Returns ``(ids, scores, status)`` as :func:`recommend_topk`; status 1 = the user has no candidate, 2 = a candidate's score is NaN
+    or infinite.
+    """
+    if hasattr(item_biases, "to_numpy"):
+        item_biases = item_biases.to_numpy()
+    _fail_if(A is None or B is None, "'A' and 'B' must both be passed.")
+    torch, kind = _factor_tensors(A, B)
+    _fail_if(isinstance(kind, str), "16-bit factors are not supported with candidate sets: pass float32 (or float64) factors.")
+    if torch is None:
+        _fail_if(not (isinstance(A, np.ndarray) and isinstance(B, np.ndarray)), "'A' and 'B' must be NumPy arrays or torch tensors.")
+    _fail_if(A.ndim != 2, "'A' must be a 2-dimensional array.")
+    _fail_if(B.ndim != 2, "'B' must be a 2-dimensional array.")
+    _fail_if(A.shape[1] != B.shape[1], "'A' and 'B' must have the same number of columns.")
+    _fail_if(0 in (A.shape[1], B.shape[0]), "Input matrices cannot be empty.")
+    n_users, n_items = A.shape[0], B.shape[0]
+    _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
+    _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    k = int(k)
+    _fail_if(k < 1, "'k' must be positive.")
+    users = _user_selection(users, n_users, "A")
+    cand_p, cand_i = _candidate_csr(candidates, n_users, n_items, users)
+    if torch:
+        dtype = np.float64 if kind is np.float64 else np.float32
+    else:
+        dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
+    if item_biases is not None:
+        A, B = _fold_item_biases_tensors(torch, A, B, item_biases, n_items) if torch else _fold_item_biases(A, B, item_biases, n_items, dtype)
+
+    # ---- everything above raises before the library is touched ----
+    if users is not None:
+        A = A[torch.from_numpy(users).to(A.device)] if torch else A[users]
+    if A.shape[0] == 0:
+        return _no_lists(k, dtype, return_scores)
+    if torch and A.is_cuda:
+        call = _DeviceCall(torch, A, kind)
+        m = A.shape[0]
+        idx, sc, st = call.empty((m, k), torch.int32), call.empty((m, k)) if return_scores else None, call.empty((m,), torch.int32)
+        call.run_factors(_binding.recommend_candidates_device, None, B,
+                         cand_p=call.put(cand_p), cand_i=call.put(cand_i), nnz_cand=int(cand_i.shape[0]), k_top=k,
+                         idx=idx.data_ptr(), score=sc.data_ptr() if return_scores else 0, status=st.data_ptr())
+        return idx.cpu().numpy(), sc.cpu().numpy() if return_scores else None, st.cpu().numpy()
+    if torch:
+        A, B = _cpu_tensor_as_array(torch, A, kind), _cpu_tensor_as_array(torch, B, kind)
+    A, lda, B, ldb = _half_or_typed(kind, A, B, dtype)
+    return _binding.recommend_candidates(A, lda, B, ldb, cand_p, cand_i, k, bool(return_scores))
 
 
 def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_scores=True):

@@ -35,8 +35,8 @@ def _metrics(source, host):
             + ((("seed", _u64),) if source is _FACTORS else ()) + (() if host else (("stream", _vp),)))
 
 
-def _lists(source, host):
-    return (source + _csr("excl", host) + (("k_top", _i32), ("idx", _vp), ("score", _vp), ("status", _vp))
+def _lists(source, host, which="excl"):
+    return (source + _csr(which, host) + (("k_top", _i32), ("idx", _vp), ("score", _vp), ("status", _vp))
             + ((("nthreads", _i32),) if host else (("stream", _vp),)))
 
 
@@ -79,6 +79,10 @@ HALF_SIGNATURES = {"rm_" + request + "_scores" + form + "_" + kind: (pieces(_SCO
 HALF_FACTOR_SIGNATURES = {"rm_" + request + form + "_" + kind: (pieces(_FACTORS, host), _ci)
                           for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
                           for kind in HALF_KINDS}
+# include/recometrics_hip_candidates.h: lists from per-user candidate sets -- the list entries' rows with the candidate CSR in the place of
+# the exclusion matrix
+CAND_SIGNATURES = {"rm_recommend_candidates" + form + suffix: (_lists(_FACTORS, host, "cand"), _ci)
+                   for form, host in (("", True), ("_dev", False)) for suffix in ("_f32", "_f64")}
 # test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
 TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
@@ -110,6 +114,7 @@ def load():
                 "(there is no CPU fallback)" % _LIB_PATH)
         _lib = _declare(_declare(C.CDLL(_LIB_PATH), SIGNATURES), HALF_SIGNATURES, HALF_SIGNATURES)
         _declare(_lib, HALF_FACTOR_SIGNATURES, HALF_FACTOR_SIGNATURES)
+        _declare(_lib, CAND_SIGNATURES, CAND_SIGNATURES)
         for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -289,7 +294,7 @@ def _invoke(entry, dtype, **values):
         params = (HALF_SIGNATURES if name in HALF_SIGNATURES else HALF_FACTOR_SIGNATURES)[name][0]
     else:
         name = entry + ("_f32" if dtype == np.float32 else "_f64")
-        params = SIGNATURES[name][0]
+        params = (CAND_SIGNATURES if name in CAND_SIGNATURES else SIGNATURES)[name][0]
     args = [values[param] for param, _ in params]
     if len(values) != len(params):
         raise TypeError("%s has no parameter %s" % (name, ", ".join(sorted(set(values) - {param for param, _ in params}))))
@@ -478,6 +483,24 @@ def recommend_device(dtype, A, lda, B, ldb, m, n, k, excl_p, excl_i, nnz_excl, k
     is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
     _invoke("rm_recommend_dev", dtype, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
             nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
+
+
+def recommend_candidates(A, lda, B, ldb, cand_p, cand_i, k_top, return_scores=True, nthreads=0):
+    """Host-array entry of the lists from candidate sets (rm_recommend_candidates_*): A, B as in `recommend`, `cand_p` / `cand_i` the
+    int32 CSR whose row u lists the candidates of user u.  Returns (ids, scores or None, status) as `recommend`."""
+    dtype = A.dtype.type
+    m, k = A.shape
+    idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
+    _invoke("rm_recommend_candidates", dtype, A=_p(A), lda=lda, B=_p(B), ldb=ldb, m=m, n=B.shape[0], k=k, Xcand_csr_p=_host_excl_p(cand_p),
+            Xcand_csr_i=_p(cand_i), k_top=k_top, idx=_p(idx), score=_p(sc), status=_p(st), nthreads=int(nthreads))
+    return idx, sc, st
+
+
+def recommend_candidates_device(dtype, A, lda, B, ldb, m, n, k, cand_p, cand_i, nnz_cand, k_top, idx, score, status, stream=0):
+    """Device-pointer entry (rm_recommend_candidates_dev_*): every array argument is an integer device address (0 == NULL: `score` =
+    ids only).  Asynchronous on `stream` apart from one small plan read-back."""
+    _invoke("rm_recommend_candidates_dev", dtype, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, Xcand_csr_p=_dp(cand_p), Xcand_csr_i=_dp(cand_i),
+            nnz_cand=nnz_cand, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
 
 
 def recommend_scores(S, lds, excl_p, excl_i, k_top, return_scores=True, nthreads=0):

@@ -1,4 +1,5 @@
-// rm_lib.hip -- host orchestration + the C-ABI of include/recometrics_hip.h and recometrics_hip_half.h  (gfx950 only).
+// rm_lib.hip -- host orchestration + the C-ABI of include/recometrics_hip.h, recometrics_hip_half.h, recometrics_hip_half_factors.h and
+// recometrics_hip_candidates.h  (gfx950 only).
 //
 // Host counterpart of reference src/recometrics.hpp:359-436 (prologue: clamps, scratch) and of the instantiation
 // shims src/recometrics_instantiated.cpp:30-143.  The reference's OpenMP loop over users (:428-437) becomes:
@@ -28,6 +29,7 @@
 #include "../../include/recometrics_hip.h"
 #include "../../include/recometrics_hip_half.h"
 #include "../../include/recometrics_hip_half_factors.h"
+#include "../../include/recometrics_hip_candidates.h"
 #include "rm_device.hpp"
 #include "rm_prep.hpp"
 #include "rm_launch.hpp"
@@ -35,6 +37,7 @@
 #include "rm_noise.hpp"
 #include "rm_scores.hpp"
 #include "rm_rowtopk.hpp"
+#include "rm_candidates.hpp"
 
 namespace {
 
@@ -557,6 +560,10 @@ template <class T> struct Request : Outputs<T> {
     // recommendation lists (rm_recommend_*): no test matrix (`test_p` is null on the device), no metric; every user with a candidate gets its
     // ordered list in `topk_idx` / `topk_score` (the caller's arrays, the scores optional) and every user a `status` -- k_finalize_reco
     bool reco = false;
+    // lists from candidate sets (rm_recommend_candidates_*; set together with `reco`): the exclusion matrix's slots carry the CANDIDATE
+    // rows instead -- validated, sorted, rebased and sharded as an exclusion matrix is -- and k_topk_candidates (rm_candidates.hpp) takes
+    // the place of preparation, sweep and finalisation.  k_classify is the one place where the meaning of a row's length flips.
+    bool cand = false;
     Outputs<T> &outputs() { return *this; }
 };
 // Which pass of a call this is (the tie noise, rm_noise.hpp, makes several of one call), and the three groups of fields that say so.
@@ -1233,6 +1240,7 @@ struct Pipeline {
     PosArgs<T> pa{};
     bool want_lane = false, ext_topk = false, items_known = false, dense_ok = false;
     bool row_topk = false;                  // lists from the caller's scores, selected while the row is read (k_topk_rows): no score row is stored
+    bool cand_topk = false;                 // lists from candidate sets, gathered, scored and selected in one kernel (k_topk_candidates)
     bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
     // the split the context kept (SplitCache): may this pass run on it, does it, may the next one run on this pass's
     bool allow_reuse = true, reused = false, keepable = false; SplitKey split_key{};
@@ -1269,7 +1277,7 @@ struct Pipeline {
         if (c.reco) { min_items_pool = 1; min_pos_test = 0; }          // (lists for whoever has a candidate: k_classify's `reco`)
         for (int i = 0; i < 10; i++) if (c.out[i] && !c.reco) req |= (1 << i);
         want_auc = req & (RQ_ROC | RQ_PR);
-        NG = c.scores ? 2 : P::supported_ng(k);                        // (scores: no factors, no sweep -- the value is never used)
+        NG = c.scores || c.cand ? 2 : P::supported_ng(k);              // (scores, candidate sets: no sweep -- the value is never used)
         if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
         if (!cx.ev_valid) {
             for (int i = 0; i < EV_COUNT; i++) HIP_CHECK(hipEventCreate(&cx.ev[i]));
@@ -1314,7 +1322,7 @@ struct Pipeline {
         heavy_users = ws.array<int>(WS_HEAVY_USERS, (size_t)m);
         ca = ClassifyArgs{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
                           flags, user_nslots, heavy_users, plan};
-        ca.only = c.only_users; ca.reco = c.reco ? 1 : 0;
+        ca.only = c.only_users; ca.reco = c.cand ? 2 : c.reco ? 1 : 0;
         ca.heavy_npos = K > FIN_TOPV ? FIN_TOPV : HEAVY_NPOS;
         // the caller's CSR arrays are validated in front of everything that indexes by them (an out-of-range column index in
         // k_train_bits would be a memory fault; on the CPU reference it is a segfault): the index pointers by k_classify itself, the
@@ -1333,11 +1341,13 @@ struct Pipeline {
         const long long m_rows = c.eval_users >= 0 ? std::min<long long>(c.eval_users, m) : m;
         // k_metrics beyond the sweep's lists (append buffers + wave compaction reach 256): every user is streamed and
         // k_select_topk picks its top-K from the stored row -- any k_metrics <= n, at one score row of HBM per user
-        want_lane = !c.scores && lane_lists_fit<T>(ws, K, m_rows, P::max_nsub >= 3 && NG <= 8);
+        want_lane = !c.scores && !c.cand && lane_lists_fit<T>(ws, K, m_rows, P::max_nsub >= 3 && NG <= 8);
         // (the caller's scores: the same plan -- the row every user needs is a copy of its row of S with the train items masked;
         // lists of up to ROW_TOPK_MAX_K items from them need no stored row at all: k_topk_rows, rm_rowtopk.hpp)
         row_topk = c.reco && c.scores && K <= ROW_TOPK_MAX_K && !g_sw.no_row_topk;
-        ext_topk = !row_topk && ((!want_lane && K > 256) || g_sw.ext_topk || c.scores);
+        // (lists from candidate sets, any k_top the entry admits: k_topk_candidates, rm_candidates.hpp -- no sweep, no lists, no rows)
+        cand_topk = c.cand;
+        ext_topk = !row_topk && !cand_topk && ((!want_lane && K > 256) || g_sw.ext_topk || c.scores);
         if (want_auc || ext_topk) {
             stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
             if (ext_topk) {
@@ -1378,7 +1388,7 @@ struct Pipeline {
         if (!cx.pinned_plan) HIP_CHECK(hipHostMalloc((void **)&cx.pinned_plan, sizeof(Plan), hipHostMallocDefault));
         // (one answer per call: a later pass -- the exact passes of the tie noise, on this or on a peer context with less free memory --
         // carries the first pass's answer; rows handed over by another pass are proof that they fit)
-        dense_ok = !c.scores && std::is_same<T, float>::value && (c.ext_bits ? true : c.dense_fit >= 0 ? c.dense_fit != 0 : dense_rows_fit(ws, m, n));
+        dense_ok = !c.scores && !c.cand && std::is_same<T, float>::value && (c.ext_bits ? true : c.dense_fit >= 0 ? c.dense_fit != 0 : dense_rows_fit(ws, m, n));
         // the positives' stream: the streamed users' chain beside the table users', and what is made per test entry beside the plan chain
         // (the caller's scores: the test entries' scores are gathered by entry whatever the switch says -- there is no kernel by slot)
         flat_early = want_auc && !c.only_users && c.nnz_test > 0 && (!g_sw.no_pos_flat || c.scores);
@@ -1456,8 +1466,10 @@ struct Pipeline {
         const hipStream_t aux = side.behind(SIDE_PLAN_FORK), aux2 = pos.behind(POS_PLAN_FORK);
         if (!c.csr_checked) launch_csr_index_checks(m, n, c.train_p, c.train_i, c.nnz_train, c.test_p, c.test_i, c.nnz_test, plan, aux);
         side.mark(SIDE_CHECKS_DONE);
-        if (!c.scores) launch_absmax<T>(c.f_type, c.A, c.lda, (long long)m, k, 512, aux2, &plan->amax_a, &plan->nonfinite);
-        if (!items_known && !c.scores) launch_absmax<T>(c.f_type, c.B, c.ldb, (long long)n, k, 1024, aux2, &plan->amax_b, &plan->nonfinite_b);
+        // (candidate sets: no maxima -- the kernel looks at every candidate's score, and a factor row nobody lists must not matter)
+        const bool maxima = !c.scores && !c.cand;
+        if (maxima) launch_absmax<T>(c.f_type, c.A, c.lda, (long long)m, k, 512, aux2, &plan->amax_a, &plan->nonfinite);
+        if (!items_known && maxima) launch_absmax<T>(c.f_type, c.B, c.ldb, (long long)n, k, 1024, aux2, &plan->amax_b, &plan->nonfinite_b);
         pos.mark(POS_MAXIMA_DONE);
         if (attempt != 0) return;                                      // (the second plan makes neither again)
         // (the user of every test entry, for the positives' scores by entry: index pointers only)
@@ -1537,7 +1549,7 @@ struct Pipeline {
         double amax_a, amax_b;
         std::memcpy(&amax_a, &hp.amax_a, 8); std::memcpy(&amax_b, &hp.amax_b, 8);
         const double tmax = std::is_same<T, float>::value ? 3.0e38 : 1.0e308;
-        if (c.scores) return false;                                    // (k_score_rows looks at every candidate score whatever it is)
+        if (c.scores || c.cand) return false;                          // (k_score_rows / k_topk_candidates look at every candidate score whatever it is)
         return hp.nonfinite || hp.nonfinite_b || !((double)k * amax_a * 1.001 < tmax / std::max(amax_b, 1e-300));
     }
 
@@ -1927,6 +1939,22 @@ struct Pipeline {
         cx.sweep_shape(1, 1, m, (double)at.sharedSizeBytes, hp.n_slots);
     }
 
+    // ---- lists from candidate sets (cand_topk): k_topk_candidates in the place of preparation, sweep and finalisation -- a block per
+    // user of the call gathers the item rows of the user's candidates, scores them and writes its list and status; the "sweep" timing
+    // brackets this launch.  The plan stage has validated the candidate rows (and thrown): every id the kernel indexes B by is in [0, n) ----
+    void topk_candidates()
+    {
+        HIP_CHECK(hipEventRecord(cx.ev[EV_PREP_END], stream));
+        CandArgs<T> ka{k, K, (const T *)c.A, c.lda, (const T *)c.B, c.ldb, c.train_p, c.train_i, plan, c.topk_idx, c.topk_score, c.status};
+        hipLaunchKernelGGL(k_topk_candidates<T>, dim3((unsigned)m), dim3(SCORE_ROW_THREADS), 0, stream, ka);
+        HIP_CHECK(hipGetLastError());
+        RM_TRACE_POINT("run: candidates' top-K enqueued");
+        HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
+        hipFuncAttributes at{};
+        HIP_CHECK(hipFuncGetAttributes(&at, (const void *)k_topk_candidates<T>));
+        cx.sweep_shape(1, 1, m, (double)at.sharedSizeBytes, hp.n_slots);
+    }
+
     int stream_parts() const { return (int)cdiv(n, STREAM_RANK_THREADS * STREAM_RANK_ITEMS); }
     void rank_streamed_rows(int r0, int r1, hipStream_t st)
     {
@@ -2078,6 +2106,7 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
         p.begin();
         p.plan_stage();
         if (p.row_topk) { p.topk_rows(); p.export_ranks(); return; }
+        if (p.cand_topk) { p.topk_candidates(); p.export_ranks(); return; }
         p.g = c.scores ? scores_geometry(p.hp, c.n, p.want_auc)
                        : sweep_geometry<T>(p.c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
         p.prep();
@@ -2940,11 +2969,24 @@ void check_request(const Request<T> &r, bool host)
                 int u = 0;
                 while (u < r.m && !(p[u] < 0 || p[u + 1] < p[u])) u++;
                 fail(std::string("CSR index pointers of row ") + std::to_string(u) + " are negative or decreasing ("
-                     + (p == r.train_p ? "X_train" : "X_test") + ")");
+                     + (p != r.train_p ? "X_test" : r.cand ? "X_cand" : "X_train") + ")");
             }
         }
         if (r.train_p && r.train_p[r.m] > 0 && !r.train_i) fail("null train indices");
     };
+    if (r.cand) {                                                    // lists from candidate sets: k_top may exceed a row, and n
+        if (r.m < 0 || r.n <= 0 || r.k <= 0) fail(mnk);
+        if (!r.A || !r.B || !r.train_p) fail(null_in);
+        if (!r.topk_idx || !r.status) fail("null output pointer");
+        if (r.K < 1) fail("k_top must be at least 1 (got " + std::to_string(r.K) + ")");
+        if (r.K > ROW_TOPK_MAX_K)
+            throw RmError{RM_ERR_UNSUPPORTED, "lists from candidate sets hold at most " + std::to_string(ROW_TOPK_MAX_K) + " items (k_top = " + std::to_string(r.K) + ")"};
+        ld_covers_k();
+        if (host) index_pointers();
+        else if (r.nnz_train < 0) fail("negative length of the index array");
+        else if (r.nnz_train > 0 && !r.train_i) fail(null_in);
+        return;
+    }
     if (r.reco) {                                                    // lists, from factors or from scores
         if (r.m < 0 || r.n <= 0 || (!r.scores && r.k <= 0)) fail(r.scores ? mn : mnk);
         if (r.scores ? !r.S : (!r.A || !r.B)) fail(null_in);
@@ -3207,6 +3249,15 @@ Request<T> lists_request(Request<T> r, int m, int n, const int *xp, const int *x
     return r;
 }
 
+// Lists from candidate sets (rm_recommend_candidates_*): a lists request whose exclusion-matrix slots carry the candidate rows (Request::cand)
+template <class T>
+Request<T> candidates_request(Request<T> r, int m, int n, const int *cp, const int *ci, long long nnz, int K, int *idx, T *score, int *status)
+{
+    r = lists_request<T>(r, m, n, cp, ci, nnz, K, idx, score, status);
+    r.train_p = cp; r.train_i = ci; r.cand = true;                   // (lists_request drops the indices of a null matrix: here a null matrix is an error)
+    return r;
+}
+
 template <class T> void host_entry(const Request<T> &r, int nthreads)
 {
     if (r.m == 0) return;                                            // reference :428-437: no user, nothing written
@@ -3350,6 +3401,32 @@ extern "C" int rm_recommend_dev_##SUFFIX(                                       
 
 RM_RECOMMEND_ENTRY(f32, float)
 RM_RECOMMEND_ENTRY(f64, double)
+
+// lists from candidate sets (include/recometrics_hip_candidates.h)
+#define RM_RECOMMEND_CANDIDATES_ENTRY(SUFFIX, T)                                                                        \
+extern "C" int rm_recommend_candidates_##SUFFIX(                                                                        \
+    const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
+    const int32_t *Xcand_csr_p, const int32_t *Xcand_csr_i, int32_t k_top,                                              \
+    int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        host_entry<T>(candidates_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xcand_csr_p, Xcand_csr_i, 0,      \
+                                            k_top, idx, score, status), nthreads);                                      \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_candidates_dev_##SUFFIX(                                                                    \
+    const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
+    const int32_t *Xcand_csr_p, const int32_t *Xcand_csr_i, int64_t nnz_cand, int32_t k_top,                            \
+    int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        dev_entry<T>(candidates_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xcand_csr_p, Xcand_csr_i,          \
+                                           nnz_cand, k_top, idx, score, status), stream);                               \
+    });                                                                                                                 \
+}
+
+RM_RECOMMEND_CANDIDATES_ENTRY(f32, float)
+RM_RECOMMEND_CANDIDATES_ENTRY(f64, double)
 
 #define RM_RECOMMEND_SCORES_ENTRY(SUFFIX, T)                                                                            \
 extern "C" int rm_recommend_scores_##SUFFIX(                                                                            \

@@ -54,6 +54,7 @@ struct ClassifyArgs {
     long long nnz_train, nnz_test;
     int reco;                    // 1 = recommendation lists (rm_recommend_*): there is no test matrix (`test_p` is null and never read); every
                                  //     user with at least one candidate is active, one slot, depth class 0, UF_KLEQN when it has no more than K
+                                 // 2 = ... from candidate sets (rm_recommend_candidates_*): `train_p` are the CANDIDATE rows, a row's length its candidates
 };
 
 __device__ __forceinline__ int chunk_depth(int pc)      // smallest j with 2^j - 1 >= pc   (pc in 1..63)
@@ -174,7 +175,7 @@ __global__ void k_classify(ClassifyArgs a)
             atomicOr(&a.plan->csr_bad, CSR_BAD_INDPTR); a.plan->csr_where = u;
         } else { ntr = a1 - a0; npos = b1 - b0; }
     }
-    const int cand = a.n - ntr;
+    const int cand = a.reco == 2 ? ntr : a.n - ntr;                 // (reco 2: the row lists the candidates themselves, rm_candidates.hpp)
     bool isnan_user = !live || npos <= 0 || (ntr + npos >= a.n && !(a.req & RQ_NDCG)) || cand < a.min_items_pool ||
                       (!a.cold && ntr == 0) || npos < a.min_pos_test;
     if (a.reco) isnan_user = !live || cand < 1;                     // whoever has a candidate is served
