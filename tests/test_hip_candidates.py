@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _layouts as lay
+from _candidates import complement_of, csr_of, rows_of, spread_rows  # noqa: F401 (spread_rows: test_cuda_tensors' script imports it from here)
 from test_hip_entry_fields import dev  # noqa: F401 (a fixture)
 from test_hip_recommend import check_lists, expected_lists, hip  # noqa: F401 (hip: a fixture)
 
@@ -18,26 +19,6 @@ F32, F64 = np.float32, np.float64
 DTYPES = pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
 # the step's edges (64 per wavefront, 256 per block), the append-everything limit (2,048), the first and the second compaction
 EDGE_C = (0, 1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 2048 + 256 + 1, 4999)
-
-
-def csr_of(rows):
-    p = np.zeros(len(rows) + 1, np.int64)
-    np.cumsum([len(r) for r in rows], out=p[1:])
-    return p.astype(np.int32), np.concatenate(rows).astype(np.int32)
-
-
-def rows_of(cand):
-    return [cand[1][cand[0][u]:cand[0][u + 1]] for u in range(cand[0].shape[0] - 1)]
-
-
-def complement_of(cand, n):
-    return csr_of([np.setdiff1d(np.arange(n, dtype=np.int32), r) for r in rows_of(cand)])
-
-
-def spread_rows(counts, n, seed):
-    """sorted rows of `counts` distinct ids over the whole id range, ids 0 and n - 1 among them wherever there are two or more"""
-    rng = np.random.default_rng(seed)
-    return csr_of([np.sort(np.concatenate([rng.choice(np.arange(1, n - 1), max(c - 2, 0), replace=False), [0, n - 1][:min(c, 2)]])) for c in counts])
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,11 +39,13 @@ def run_host(hip, A, B, cand, K, scores=True):
     return hip.recommend_candidates(A, A.shape[1], B, B.shape[1], cand[0], cand[1], K, scores)
 
 
-def run_dev(hip, dev, A, B, cand, K, scores=True, layout="D"):
-    """the device entry; `layout` (tests/_layouts.py) for both factor matrices, NaN in every element that is not a factor"""
+def run_dev(hip, dev, A, B, cand, K, scores=True, layout="D", layout_b=None):
+    """the device entry; `layout` for A and, unless `layout_b` names another, for B: a name of tests/_layouts.py or a (pad, off) pair
+    in elements; NaN in every element that is not a factor"""
     dtype, m, at = A.dtype.type, A.shape[0], []
-    for X in (A, B):
-        V, raw, off = lay.place_as(X, layout, lay.NAN_POISON[lay.PREC[np.dtype(dtype)]])
+    for X, name in ((A, layout), (B, layout if layout_b is None else layout_b)):
+        poison = lay.NAN_POISON[lay.PREC[np.dtype(dtype)]]
+        V, raw, off = lay.place_as(X, name, poison) if isinstance(name, str) else lay.place(X, *name, poison)
         at += [dev.put(raw) + off * raw.itemsize, V.strides[0] // raw.itemsize]
     idx, sc, st = dev.put(np.full((m, K), 77, np.int32)), dev.put(np.full((m, K), 7, dtype)), dev.put(np.full(m, 77, np.int32))
     hip.recommend_candidates_device(dtype, *at, m, B.shape[0], A.shape[1], dev.put(cand[0]), dev.put(cand[1]), int(cand[1].shape[0]), K,
