@@ -23,7 +23,8 @@
  * Host entries: user batches, rm_set_devices shards, SIGINT, `nthreads` (the fall-back sort) and rm_get_timings (out[1]: the kernel,
  * out[6]: its blocks) as for rm_recommend_*; results depend neither on the batch size nor on the device list.  The _dev entries take
  * DEVICE pointers and are asynchronous on `stream`.
- * Not here: an exclusion matrix next to the candidates (the candidate row IS the pool: filter it beforehand), 16-bit factors, metrics.
+ * Not here: an exclusion matrix next to the candidates (the candidate row IS the pool: filter it beforehand), 16-bit factors.  The
+ * metrics over the same pools are recometrics_hip_candidate_metrics.h's.
  */
 #ifndef RECOMETRICS_HIP_CANDIDATES_H
 #define RECOMETRICS_HIP_CANDIDATES_H

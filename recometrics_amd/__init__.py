@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _binding
 
-__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_scores", "recommend_topk", "recommend_topk_from_candidates", "recommend_topk_from_scores",
+__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_candidates", "calc_reco_metrics_from_scores", "recommend_topk", "recommend_topk_from_candidates", "recommend_topk_from_scores",
            "split_reco_train_test"]
 __version__ = "0.1.0"
 
@@ -741,6 +741,107 @@ def recommend_topk_from_candidates(A, B, candidates, k=10, item_biases=None, use
         A, B = _cpu_tensor_as_array(torch, A, kind), _cpu_tensor_as_array(torch, B, kind)
     A, lda, B, ldb = _half_or_typed(kind, A, B, dtype)
     return _binding.recommend_candidates(A, lda, B, ldb, cand_p, cand_i, k, bool(return_scores))
+
+
+def calc_reco_metrics_from_candidates(
+    X_test, A, B, candidates,
+    k=5,
+    as_df=True,
+    precision=True,
+    trunc_precision=False,
+    recall=False,
+    average_precision=True,
+    trunc_average_precision=False,
+    ndcg=True,
+    hit=False,
+    rr=False,
+    roc_auc=False,
+    pr_auc=False,
+    all_metrics=False,
+    rename_k=True,
+    min_pos_test=1,
+    min_items_pool=2,
+    cumulative=False,
+    item_biases=None,
+    add_test_items=False,
+):
+    """The metrics of :func:`calc_reco_metrics` over each user's OWN candidate items -- leave-one-out HR@10 / NDCG@10 over 1 + 99
+    items, sampled-negative evaluation of a large catalogue, a re-ranker over an ANN shortlist -- at the cost of the candidates' item
+    rows instead of a sweep over the catalogue.  A user's values are what :func:`calc_reco_metrics` returns with
+    ``break_ties_with_noise=False`` for the ``X_train`` that holds every item that is NOT the user's candidate; that matrix is never
+    built.  The reference has no such call.
+
+    ``X_test`` and the metric switches as in :func:`calc_reco_metrics`; ``A``, ``B``, ``item_biases`` and ``candidates`` as in
+    :func:`recommend_topk_from_candidates` (16-bit factors are not supported), a candidate row of at most 2048 entries and ``k`` of at
+    most 1024.  The test items of a user must be among its candidates: with ``add_test_items=True`` they are added here (pass the sampled
+    negatives alone), otherwise a missing one raises ``ValueError``.
+    """
+    requested = _requested_metrics(locals())
+    from scipy.sparse import csr_array, issparse
+    if hasattr(item_biases, "to_numpy"):
+        item_biases = item_biases.to_numpy()
+    _fail_if(A is None or B is None, "'A' and 'B' must both be passed.")
+    torch, kind = _factor_tensors(A, B)
+    _fail_if(isinstance(kind, str), "16-bit factors are not supported with candidate sets: pass float32 (or float64) factors.")
+    if torch is None:
+        _fail_if(not (isinstance(A, np.ndarray) and isinstance(B, np.ndarray)), "'A' and 'B' must be NumPy arrays or torch tensors.")
+    assert issparse(X_test)
+    n_users, n_items = X_test.shape
+    _fail_if(n_users >= _INT32_MAX, "Number of test user is larger than maximum supported.")
+    _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    _fail_if(X_test.data.shape[0] == 0, "'X_test' is empty.")
+    A, B = _check_factors(A, B, n_users, n_items)
+    _fail_if_no_ranking_metric(requested)
+    k, min_pos_test, min_items_pool = int(k), int(min_pos_test), int(min_items_pool)
+    _fail_if(k < 1, "'k' must be positive.")
+    assert min_pos_test >= 1 and min_items_pool >= 1
+    if torch:
+        dtype = np.float64 if kind is np.float64 else np.float32
+    else:
+        dtype = np.float32 if (A.dtype == np.float32 and B.dtype == np.float32) else np.float64
+    cand_p, cand_i = _candidate_csr(candidates, n_users, n_items, None)
+    X_test = _csr_int32(X_test)
+    test_p, test_i = np.ascontiguousarray(X_test.indptr), np.ascontiguousarray(X_test.indices)
+    test_v = np.ascontiguousarray(X_test.data if X_test.data.dtype == dtype else X_test.data.astype(dtype))
+    # the test rows against the candidate rows, as sets of (user, item) keys: both CSRs are on the host here
+    _fail_if(cand_p[0] < 0 or np.any(np.diff(cand_p) < 0) or cand_p[-1] > cand_i.shape[0], "'candidates': index pointers are negative, decreasing or beyond the indices.")
+    cand_i = cand_i[:cand_p[-1]]
+    _fail_if(cand_i.size and (cand_i.min() < 0 or cand_i.max() >= n_items), "'candidates' has item ids outside the rows of 'B'.")
+    users_of = lambda p: np.repeat(np.arange(n_users, dtype=np.int64), np.diff(p))
+    cand_keys, test_keys = users_of(cand_p) * n_items + cand_i, users_of(test_p) * n_items + test_i
+    if add_test_items:
+        keys = np.union1d(cand_keys, test_keys)
+        cand_p = np.concatenate([[0], np.cumsum(np.bincount(keys // n_items, minlength=n_users))]).astype(np.int32)
+        cand_i = (keys % n_items).astype(np.int32)
+    else:
+        missing = ~np.isin(test_keys, cand_keys)
+        _fail_if(missing.any(), "user %d has a test item that is not among its candidates (pass add_test_items=True to add the test items)."
+                 % (test_keys[missing][0] // n_items if missing.any() else -1))
+    if item_biases is not None:
+        A, B = _fold_item_biases_tensors(torch, A, B, item_biases, n_items) if torch else _fold_item_biases(A, B, item_biases, n_items, dtype)
+
+    # ---- everything above raises before the library is touched ----
+    if torch and A.is_cuda:
+        want = {short: requested[name] for name, short, _ in _METRICS}
+        arrays = _binding._metric_outs(None, want, n_users, k, bool(cumulative), dtype)
+        call = _DeviceCall(torch, A, kind)
+        on_device = [call.empty(a.size) if a.size else None for a in arrays]
+        call.run_factors(_binding.calc_metrics_candidates_device, None, B,
+                         cand_p=call.put(cand_p), cand_i=call.put(cand_i), nnz_cand=int(cand_i.shape[0]),
+                         test_p=call.put(test_p), test_i=call.put(test_i), test_v=call.put(test_v), nnz_test=int(test_i.shape[0]),
+                         k_metrics=k, outs=[t.data_ptr() if t is not None else 0 for t in on_device], cumulative=bool(cumulative),
+                         min_items_pool=min_items_pool, min_pos_test=min_pos_test)
+        for a, t in zip(arrays, on_device):
+            if t is not None:
+                a.reshape(-1)[:] = t.cpu().numpy()
+        return _metrics_result(arrays, None, None, k, as_df, cumulative, rename_k)
+    if torch:
+        A, B = _cpu_tensor_as_array(torch, A, kind), _cpu_tensor_as_array(torch, B, kind)
+    A, lda, B, ldb = _half_or_typed(kind, A, B, dtype)
+    want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
+    arrays = _binding.calc_metrics_candidates(A, lda, B, ldb, cand_p, cand_i, test_p, test_i, test_v, k, want, bool(cumulative),
+                                              min_items_pool, min_pos_test, outs=outs)
+    return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
 
 
 def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_scores=True):

@@ -83,6 +83,13 @@ HALF_FACTOR_SIGNATURES = {"rm_" + request + form + "_" + kind: (pieces(_FACTORS,
 # the exclusion matrix
 CAND_SIGNATURES = {"rm_recommend_candidates" + form + suffix: (_lists(_FACTORS, host, "cand"), _ci)
                    for form, host in (("", True), ("_dev", False)) for suffix in ("_f32", "_f64")}
+# include/recometrics_hip_candidate_metrics.h: the ten metrics over the same candidate sets -- the metric entries' rows with the candidate
+# CSR in the place of the train matrix, and without tie noise, seed and cold-start switch
+_CAND_METRICS_LEFT_OUT = ("break_ties_with_noise", "seed", "consider_cold_start")
+CAND_METRIC_SIGNATURES = {"rm_calc_metrics_candidates" + form + suffix:
+                          (tuple(("Xcand" + name[6:] if name.startswith("Xtrain") else "nnz_cand" if name == "nnz_train" else name, ctype)
+                                 for name, ctype in _metrics(_FACTORS, host) if name not in _CAND_METRICS_LEFT_OUT), _ci)
+                          for form, host in (("", True), ("_dev", False)) for suffix in ("_f32", "_f64")}
 # test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
 TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
@@ -115,6 +122,7 @@ def load():
         _lib = _declare(_declare(C.CDLL(_LIB_PATH), SIGNATURES), HALF_SIGNATURES, HALF_SIGNATURES)
         _declare(_lib, HALF_FACTOR_SIGNATURES, HALF_FACTOR_SIGNATURES)
         _declare(_lib, CAND_SIGNATURES, CAND_SIGNATURES)
+        _declare(_lib, CAND_METRIC_SIGNATURES, CAND_METRIC_SIGNATURES)
         for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -294,7 +302,7 @@ def _invoke(entry, dtype, **values):
         params = (HALF_SIGNATURES if name in HALF_SIGNATURES else HALF_FACTOR_SIGNATURES)[name][0]
     else:
         name = entry + ("_f32" if dtype == np.float32 else "_f64")
-        params = (CAND_SIGNATURES if name in CAND_SIGNATURES else SIGNATURES)[name][0]
+        params = (CAND_SIGNATURES if name in CAND_SIGNATURES else CAND_METRIC_SIGNATURES if name in CAND_METRIC_SIGNATURES else SIGNATURES)[name][0]
     args = [values[param] for param, _ in params]
     if len(values) != len(params):
         raise TypeError("%s has no parameter %s" % (name, ", ".join(sorted(set(values) - {param for param, _ in params}))))
@@ -501,6 +509,34 @@ def recommend_candidates_device(dtype, A, lda, B, ldb, m, n, k, cand_p, cand_i, 
     ids only).  Asynchronous on `stream` apart from one small plan read-back."""
     _invoke("rm_recommend_candidates_dev", dtype, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, Xcand_csr_p=_dp(cand_p), Xcand_csr_i=_dp(cand_i),
             nnz_cand=nnz_cand, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
+
+
+def _cand_metrics_values(ptr, cand_p, cand_i, test_p, test_i, test_v, k_metrics, cumulative, outs, min_items_pool, min_pos_test):
+    """what the four entries of the metrics over candidate sets share, by name"""
+    return dict(zip(OUTPUTS, map(ptr, outs)), Xcand_csr_i=ptr(cand_i), Xtest_csr_p=ptr(test_p), Xtest_csr_i=ptr(test_i), Xtest_csr=ptr(test_v),
+                k_metrics=k_metrics, cumulative=int(bool(cumulative)), min_items_pool=min_items_pool, min_pos_test=min_pos_test)
+
+
+def calc_metrics_candidates(A, lda, B, ldb, cand_p, cand_i, test_p, test_i, test_v, k_metrics, want, cumulative, min_items_pool, min_pos_test,
+                            nthreads=0, outs=None):
+    """Host-array entry of the metrics over candidate sets (rm_calc_metrics_candidates_*): A, B, `cand_p` / `cand_i` as in
+    `recommend_candidates`, the test CSR, `want` and the returned 10-tuple as in `calc_metrics`."""
+    dtype = A.dtype.type
+    m, k = A.shape
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
+    _invoke("rm_calc_metrics_candidates", dtype, A=_p(A), lda=lda, B=_p(B), ldb=ldb, m=m, n=B.shape[0], k=k, Xcand_csr_p=_host_excl_p(cand_p),
+            nthreads=int(nthreads),
+            **_cand_metrics_values(_p, cand_p, cand_i, test_p, test_i, test_v, k_metrics, cumulative, outs, min_items_pool, min_pos_test))
+    return outs
+
+
+def calc_metrics_candidates_device(dtype, A, lda, B, ldb, m, n, k, cand_p, cand_i, nnz_cand, test_p, test_i, test_v, nnz_test,
+                                   k_metrics, outs, cumulative=False, min_items_pool=2, min_pos_test=1, stream=0):
+    """Device-pointer entry (rm_calc_metrics_candidates_dev_*): every array argument is an integer device address (0 == NULL); `outs` is
+    a sequence of 10 addresses in METRIC_ORDER.  Asynchronous on `stream` apart from one small plan read-back."""
+    _invoke("rm_calc_metrics_candidates_dev", dtype, A=_dp(A), lda=lda, B=_dp(B), ldb=ldb, m=m, n=n, k=k, Xcand_csr_p=_dp(cand_p),
+            nnz_cand=nnz_cand, nnz_test=nnz_test, stream=_dp(stream),
+            **_cand_metrics_values(_dp, cand_p, cand_i, test_p, test_i, test_v, k_metrics, cumulative, outs, min_items_pool, min_pos_test))
 
 
 def recommend_scores(S, lds, excl_p, excl_i, k_top, return_scores=True, nthreads=0):

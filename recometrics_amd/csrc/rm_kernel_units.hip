@@ -1,4 +1,4 @@
-// rm_kernel_units.hip -- the kernels of rm_prep / rm_finalize / rm_noise / rm_scores / rm_rowtopk / rm_candidates.hpp, compiled apart from the host
+// rm_kernel_units.hip -- the kernels of rm_prep / rm_finalize / rm_noise / rm_scores / rm_rowtopk / rm_candidates / rm_candmetrics.hpp, compiled apart from the host
 // code that launches them (rm_lib.hip sees them `extern template`, or as declarations, and emits none: rm_kernel_units.hpp).
 //
 // This file is compiled once per translation unit with -DRM_KERNELS=k, units 3 and 4 once per precision with -DRM_F64=0 / 1
@@ -13,6 +13,7 @@
 //               5  rm_scores.hpp, rm_rowtopk.hpp with 16-bit scores (f16 / bf16 in, fp32 behind the load)
 //               6  rm_prep.hpp's readers of raw A / B with 16-bit factors (f16 / bf16 in, fp32 behind the load)
 //               7  rm_candidates.hpp: lists from candidate sets
+//               8  rm_candmetrics.hpp: metrics over candidate sets
 #include <hip/hip_runtime.h>
 
 #if RM_KERNELS == 0
@@ -51,8 +52,11 @@
 #elif RM_KERNELS == 7
 #include "rm_candidates.hpp"
 #define RM_UNIT_KERNELS(X) RM_CANDIDATES_KERNELS_F32(X) RM_CANDIDATES_KERNELS_F64(X)
+#elif RM_KERNELS == 8
+#include "rm_candmetrics.hpp"
+#define RM_UNIT_KERNELS(X) RM_CANDMETRICS_KERNELS_F32(X) RM_CANDMETRICS_KERNELS_F64(X)
 #else
-#error "RM_KERNELS: 0 .. 7"
+#error "RM_KERNELS: 0 .. 8"
 #endif
 
 namespace rm {

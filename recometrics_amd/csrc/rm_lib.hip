@@ -1,5 +1,5 @@
 // rm_lib.hip -- host orchestration + the C-ABI of include/recometrics_hip.h, recometrics_hip_half.h, recometrics_hip_half_factors.h and
-// recometrics_hip_candidates.h  (gfx950 only).
+// recometrics_hip_candidates.h, recometrics_hip_candidate_metrics.h  (gfx950 only).
 //
 // Host counterpart of reference src/recometrics.hpp:359-436 (prologue: clamps, scratch) and of the instantiation
 // shims src/recometrics_instantiated.cpp:30-143.  The reference's OpenMP loop over users (:428-437) becomes:
@@ -30,6 +30,7 @@
 #include "../../include/recometrics_hip_half.h"
 #include "../../include/recometrics_hip_half_factors.h"
 #include "../../include/recometrics_hip_candidates.h"
+#include "../../include/recometrics_hip_candidate_metrics.h"
 #include "rm_device.hpp"
 #include "rm_prep.hpp"
 #include "rm_launch.hpp"
@@ -38,6 +39,7 @@
 #include "rm_scores.hpp"
 #include "rm_rowtopk.hpp"
 #include "rm_candidates.hpp"
+#include "rm_candmetrics.hpp"
 
 namespace {
 
@@ -563,6 +565,8 @@ template <class T> struct Request : Outputs<T> {
     // lists from candidate sets (rm_recommend_candidates_*; set together with `reco`): the exclusion matrix's slots carry the CANDIDATE
     // rows instead -- validated, sorted, rebased and sharded as an exclusion matrix is -- and k_topk_candidates (rm_candidates.hpp) takes
     // the place of preparation, sweep and finalisation.  k_classify is the one place where the meaning of a row's length flips.
+    // Metrics over candidate sets (rm_calc_metrics_candidates_*): `cand` WITHOUT `reco` -- the candidate rows in the same slots, a test
+    // matrix and the ten outputs as in a metric call; the plan stage and k_metrics_candidates (rm_candmetrics.hpp), nothing else.
     bool cand = false;
     Outputs<T> &outputs() { return *this; }
 };
@@ -991,6 +995,12 @@ inline void seed_from_sample(const Args &sa, Workspace &ws, int S, int NG, int n
     check_launch(hipGetLastError());
 }
 
+// metrics over candidate sets: the message for a row the metric kernel does not rank
+inline std::string cand_row_too_long(long long row)
+{
+    return "candidate row " + std::to_string(row) + " has more than " + std::to_string(ROW_TOPK_CAP) + " entries: metrics over candidate sets rank rows of at most "
+           + std::to_string(ROW_TOPK_CAP) + " entries in one kernel; a full ranking of a longer row is the catalogue sweep's job (rm_calc_metrics_* with the complement as X_train)";
+}
 // what the plan's validation kernels found wrong with the caller's CSR arrays -> the error the entry points see
 template <class T>
 void throw_csr_defects(const Plan &hp, const Call<T> &c, Ctx &cx)
@@ -1241,6 +1251,7 @@ struct Pipeline {
     bool want_lane = false, ext_topk = false, items_known = false, dense_ok = false;
     bool row_topk = false;                  // lists from the caller's scores, selected while the row is read (k_topk_rows): no score row is stored
     bool cand_topk = false;                 // lists from candidate sets, gathered, scored and selected in one kernel (k_topk_candidates)
+    bool cand_metrics = false;              // metrics over candidate sets, gathered, scored, ranked and evaluated in one kernel (k_metrics_candidates)
     bool bits_early = false, bits_early_masked = false, masked_from_bits = false, flat_early = false;
     // the split the context kept (SplitCache): may this pass run on it, does it, may the next one run on this pass's
     bool allow_reuse = true, reused = false, keepable = false; SplitKey split_key{};
@@ -1276,7 +1287,7 @@ struct Pipeline {
         min_pos_test = std::min(c.min_pos_test, 1);
         if (c.reco) { min_items_pool = 1; min_pos_test = 0; }          // (lists for whoever has a candidate: k_classify's `reco`)
         for (int i = 0; i < 10; i++) if (c.out[i] && !c.reco) req |= (1 << i);
-        want_auc = req & (RQ_ROC | RQ_PR);
+        want_auc = !c.cand && (req & (RQ_ROC | RQ_PR));                // (candidate sets: the metric kernel ranks the whole row itself)
         NG = c.scores || c.cand ? 2 : P::supported_ng(k);              // (scores, candidate sets: no sweep -- the value is never used)
         if (NG < 0) throw RmError{RM_ERR_UNSUPPORTED, std::string(P::limit()) + " (got " + std::to_string(k) + ")"};
         if (!cx.ev_valid) {
@@ -1322,7 +1333,7 @@ struct Pipeline {
         heavy_users = ws.array<int>(WS_HEAVY_USERS, (size_t)m);
         ca = ClassifyArgs{m, n, K, c.train_p, c.test_p, req, c.cold ? 1 : 0, min_items_pool, min_pos_test, want_auc ? 1 : 0,
                           flags, user_nslots, heavy_users, plan};
-        ca.only = c.only_users; ca.reco = c.cand ? 2 : c.reco ? 1 : 0;
+        ca.only = c.only_users; ca.reco = c.cand ? (c.reco ? 2 : 3) : c.reco ? 1 : 0; ca.cand_row_cap = ROW_TOPK_CAP;
         ca.heavy_npos = K > FIN_TOPV ? FIN_TOPV : HEAVY_NPOS;
         // the caller's CSR arrays are validated in front of everything that indexes by them (an out-of-range column index in
         // k_train_bits would be a memory fault; on the CPU reference it is a segfault): the index pointers by k_classify itself, the
@@ -1346,8 +1357,10 @@ struct Pipeline {
         // lists of up to ROW_TOPK_MAX_K items from them need no stored row at all: k_topk_rows, rm_rowtopk.hpp)
         row_topk = c.reco && c.scores && K <= ROW_TOPK_MAX_K && !g_sw.no_row_topk;
         // (lists from candidate sets, any k_top the entry admits: k_topk_candidates, rm_candidates.hpp -- no sweep, no lists, no rows)
-        cand_topk = c.cand;
-        ext_topk = !row_topk && !cand_topk && ((!want_lane && K > 256) || g_sw.ext_topk || c.scores);
+        cand_topk = c.cand && c.reco;
+        // (metrics over candidate sets: k_metrics_candidates, rm_candmetrics.hpp -- the same)
+        cand_metrics = c.cand && !c.reco;
+        ext_topk = !row_topk && !c.cand && ((!want_lane && K > 256) || g_sw.ext_topk || c.scores);
         if (want_auc || ext_topk) {
             stream_cap = stream_budget_bytes(ws) / (stream_ld_max * (long long)sizeof(T));
             if (ext_topk) {
@@ -1534,6 +1547,7 @@ struct Pipeline {
         RM_TRACE_POINT("run: plan read back");
         hp = *cx.pinned_plan;
         throw_csr_defects(hp, c, cx);
+        if (cand_metrics && hp.cand_long_row) throw RmError{RM_ERR_UNSUPPORTED, cand_row_too_long((long long)c.user0 + (0x7fffffff - hp.cand_long_row))};
         // the streamed users' score rows must fit the budget; if not (memory pressure), plan again with those users in chunks
         if (!(ca.allow_stream && !ca.force_stream && hp.class_count[STREAM_CLASS] > stream_cap && attempt == 0)) return false;
         ca.allow_stream = 0; ca.check_ptr = 0; keepable = false;     // (a second plan is never kept)
@@ -1559,7 +1573,7 @@ struct Pipeline {
     bool make_split_key(SplitKey &key) const
     {
         std::memset(&key, 0, sizeof(SplitKey));
-        if (g_sw.no_split_cache || !use_side || c.reco || c.scores || !c.plain() || c.items_tag != 0 || !c.test_p || m <= 0) return false;
+        if (g_sw.no_split_cache || !use_side || c.reco || c.cand || c.scores || !c.plain() || c.items_tag != 0 || !c.test_p || m <= 0) return false;
         const long long words[SPLIT_ARRAYS] = {(long long)m + 1, std::max<long long>(c.nnz_train, 0), (long long)m + 1, std::max<long long>(c.nnz_test, 0),
                                                c.test_v ? std::max<long long>(c.nnz_test, 0) * (long long)(sizeof(T) / 4) : 0};
         long long total = 0;
@@ -1955,6 +1969,27 @@ struct Pipeline {
         cx.sweep_shape(1, 1, m, (double)at.sharedSizeBytes, hp.n_slots);
     }
 
+    // ---- metrics over candidate sets (cand_metrics): k_metrics_candidates in the place of preparation, sweep and finalisation, in its two
+    // team sizes -- a wavefront per user for rows of at most CANDM_WAVE_ROW entries, a block per user for the longer ones --, each launched
+    // over all users of the call; the "sweep" timing brackets the two launches.  The plan stage has validated both CSRs and refused rows
+    // beyond ROW_TOPK_CAP (and thrown) ----
+    void metrics_candidates()
+    {
+        HIP_CHECK(hipEventRecord(cx.ev[EV_PREP_END], stream));
+        CandMetricArgs<T> ka{k, K, req, c.cumulative ? 1 : 0, min_items_pool, min_pos_test, (const T *)c.A, c.lda, (const T *)c.B, c.ldb,
+                             c.train_p, c.train_i, c.test_p, c.test_i, c.test_v, plan, log2tab, {}};
+        for (int i = 0; i < 10; i++) ka.out[i] = c.out[i];
+        const unsigned wave_blocks = cdiv(m, SCORE_ROW_THREADS / WAVE);
+        hipLaunchKernelGGL((k_metrics_candidates<T, WAVE>), dim3(wave_blocks), dim3(SCORE_ROW_THREADS), 0, stream, ka, m);
+        hipLaunchKernelGGL((k_metrics_candidates<T, SCORE_ROW_THREADS>), dim3((unsigned)m), dim3(SCORE_ROW_THREADS), 0, stream, ka, m);
+        HIP_CHECK(hipGetLastError());
+        RM_TRACE_POINT("run: candidates' metrics enqueued");
+        HIP_CHECK(hipEventRecord(cx.ev[EV_SWEEP_END], stream));
+        hipFuncAttributes at{};
+        HIP_CHECK(hipFuncGetAttributes(&at, (const void *)k_metrics_candidates<T, WAVE>));
+        cx.sweep_shape(2, 1, (double)wave_blocks + m, (double)at.sharedSizeBytes, hp.n_slots);
+    }
+
     int stream_parts() const { return (int)cdiv(n, STREAM_RANK_THREADS * STREAM_RANK_ITEMS); }
     void rank_streamed_rows(int r0, int r1, hipStream_t st)
     {
@@ -2107,6 +2142,7 @@ void run(const Call<T> &c, hipStream_t stream, Ctx &cx)
         p.plan_stage();
         if (p.row_topk) { p.topk_rows(); p.export_ranks(); return; }
         if (p.cand_topk) { p.topk_candidates(); p.export_ranks(); return; }
+        if (p.cand_metrics) { p.metrics_candidates(); p.export_ranks(); return; }
         p.g = c.scores ? scores_geometry(p.hp, c.n, p.want_auc)
                        : sweep_geometry<T>(p.c, p.hp, p.NG, p.want_auc, p.want_lane, p.ext_topk, p.check_nan, p.dense_ok, g_sw);
         p.prep();
@@ -2974,6 +3010,22 @@ void check_request(const Request<T> &r, bool host)
         }
         if (r.train_p && r.train_p[r.m] > 0 && !r.train_i) fail("null train indices");
     };
+    if (r.cand && !r.reco) {                                         // metrics over candidate sets: k_metrics may exceed a row, and n
+        if (r.m < 0 || r.n <= 0 || r.k <= 0) fail(mnk);
+        if (!r.A || !r.B || !r.train_p || !r.test_p || (!r.test_i && nnz_test() > 0)) fail(null_in);
+        if (r.K < 1) fail("k_metrics must be at least 1 (got " + std::to_string(r.K) + ")");
+        if (r.K > ROW_TOPK_MAX_K)
+            throw RmError{RM_ERR_UNSUPPORTED, "metrics over candidate sets rank at most " + std::to_string(ROW_TOPK_MAX_K) + " places (k_metrics = " + std::to_string(r.K) + ")"};
+        ld_covers_k(); ndcg_has_values();
+        if (host) {
+            index_pointers();
+            // (the plan stage decides the same batch by batch; here, once, so that no batch has written anything by then)
+            for (int u = 0; u < r.m; u++) if (r.train_p[u + 1] - r.train_p[u] > ROW_TOPK_CAP) throw RmError{RM_ERR_UNSUPPORTED, cand_row_too_long(u)};
+        }
+        else if (r.nnz_train < 0 || r.nnz_test < 0) fail("negative length of an index array");
+        else if (r.nnz_train > 0 && !r.train_i) fail(null_in);
+        return;
+    }
     if (r.cand) {                                                    // lists from candidate sets: k_top may exceed a row, and n
         if (r.m < 0 || r.n <= 0 || r.k <= 0) fail(mnk);
         if (!r.A || !r.B || !r.train_p) fail(null_in);
@@ -3258,6 +3310,18 @@ Request<T> candidates_request(Request<T> r, int m, int n, const int *cp, const i
     return r;
 }
 
+// Metrics over candidate sets (rm_calc_metrics_candidates_*): a metric request whose train-matrix slots carry the candidate rows
+// (Request::cand without Request::reco); no tie noise, cold start considered
+template <class T>
+Request<T> candidate_metrics_request(Request<T> r, int m, int n, const int *cp, const int *ci, long long nnz_cand,
+                                     const int *test_p, const int *test_i, const T *test_v, long long nnz_test,
+                                     int K, int cumulative, const std::array<T *, 10> &out, int min_items_pool, int min_pos_test)
+{
+    r = metrics_request<T>(r, m, n, cp, ci, nnz_cand, test_p, test_i, test_v, nnz_test, K, cumulative, 0, out, 1, min_items_pool, min_pos_test, 0);
+    r.cand = true;
+    return r;
+}
+
 template <class T> void host_entry(const Request<T> &r, int nthreads)
 {
     if (r.m == 0) return;                                            // reference :428-437: no user, nothing written
@@ -3427,6 +3491,44 @@ extern "C" int rm_recommend_candidates_dev_##SUFFIX(                            
 
 RM_RECOMMEND_CANDIDATES_ENTRY(f32, float)
 RM_RECOMMEND_CANDIDATES_ENTRY(f64, double)
+
+// metrics over candidate sets (include/recometrics_hip_candidate_metrics.h)
+#define RM_CANDIDATE_METRICS_ENTRY(SUFFIX, T)                                                                           \
+extern "C" int rm_calc_metrics_candidates_##SUFFIX(                                                                     \
+    const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
+    const int32_t *Xcand_csr_p, const int32_t *Xcand_csr_i,                                                             \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr,                                         \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads)                              \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        host_entry<T>(candidate_metrics_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xcand_csr_p, Xcand_csr_i,  \
+                                                   0, Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0, k_metrics, cumulative,    \
+                                                   {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k,    \
+                                                    rr_at_k, roc_auc, pr_auc}, min_items_pool, min_pos_test),           \
+                      nthreads);                                                                                        \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_calc_metrics_candidates_dev_##SUFFIX(                                                                 \
+    const T *A, size_t lda, const T *B, size_t ldb, int32_t m, int32_t n, int32_t k,                                    \
+    const int32_t *Xcand_csr_p, const int32_t *Xcand_csr_i, int64_t nnz_cand,                                           \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr, int64_t nnz_test,                       \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int32_t min_items_pool, int32_t min_pos_test, void *stream)                                  \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        dev_entry<T>(candidate_metrics_request<T>(from_factors<T>(A, lda, B, ldb, k), m, n, Xcand_csr_p, Xcand_csr_i,   \
+                                                  nnz_cand, Xtest_csr_p, Xtest_csr_i, Xtest_csr, nnz_test, k_metrics,   \
+                                                  cumulative, {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k,   \
+                                                               hit_at_k, rr_at_k, roc_auc, pr_auc},                     \
+                                                  min_items_pool, min_pos_test), stream);                               \
+    });                                                                                                                 \
+}
+
+RM_CANDIDATE_METRICS_ENTRY(f32, float)
+RM_CANDIDATE_METRICS_ENTRY(f64, double)
 
 #define RM_RECOMMEND_SCORES_ENTRY(SUFFIX, T)                                                                            \
 extern "C" int rm_recommend_scores_##SUFFIX(                                                                            \

@@ -55,6 +55,10 @@ struct ClassifyArgs {
     int reco;                    // 1 = recommendation lists (rm_recommend_*): there is no test matrix (`test_p` is null and never read); every
                                  //     user with at least one candidate is active, one slot, depth class 0, UF_KLEQN when it has no more than K
                                  // 2 = ... from candidate sets (rm_recommend_candidates_*): `train_p` are the CANDIDATE rows, a row's length its candidates
+                                 // 3 = metrics over candidate sets (rm_calc_metrics_candidates_*): as 2, but there IS a test matrix, whose index
+                                 //     pointers are validated here; eligibility is the metric kernel's (it knows the DISTINCT count), and the first
+                                 //     candidate row of more than `cand_row_cap` entries is reported in plan->cand_long_row
+    int cand_row_cap;
 };
 
 __device__ __forceinline__ int chunk_depth(int pc)      // smallest j with 2^j - 1 >= pc   (pc in 1..63)
@@ -170,12 +174,14 @@ __global__ void k_classify(ClassifyArgs a)
     if (skip) { a.flags[u] = UF_SKIP; a.user_nslots[u] = 0; }
     int ntr = 0, npos = 0;
     if (live) {
-        const int a0 = a.train_p[u], a1 = a.train_p[u + 1], b0 = a.reco ? 0 : a.test_p[u], b1 = a.reco ? 0 : a.test_p[u + 1];
+        const bool no_test = a.reco == 1 || a.reco == 2;
+        const int a0 = a.train_p[u], a1 = a.train_p[u + 1], b0 = no_test ? 0 : a.test_p[u], b1 = no_test ? 0 : a.test_p[u + 1];
         if (a.check_ptr && (a0 < 0 || a1 < a0 || (long long)a1 > a.nnz_train || b0 < 0 || b1 < b0 || (long long)b1 > a.nnz_test)) {
             atomicOr(&a.plan->csr_bad, CSR_BAD_INDPTR); a.plan->csr_where = u;
-        } else { ntr = a1 - a0; npos = b1 - b0; }
+        } else { ntr = a1 - a0; npos = a.reco ? 0 : b1 - b0; }
+        if (a.reco == 3 && ntr > a.cand_row_cap) atomicMax(&a.plan->cand_long_row, 0x7fffffff - u);
     }
-    const int cand = a.reco == 2 ? ntr : a.n - ntr;                 // (reco 2: the row lists the candidates themselves, rm_candidates.hpp)
+    const int cand = a.reco >= 2 ? ntr : a.n - ntr;                 // (reco 2, 3: the row lists the candidates themselves, rm_candidates.hpp)
     bool isnan_user = !live || npos <= 0 || (ntr + npos >= a.n && !(a.req & RQ_NDCG)) || cand < a.min_items_pool ||
                       (!a.cold && ntr == 0) || npos < a.min_pos_test;
     if (a.reco) isnan_user = !live || cand < 1;                     // whoever has a candidate is served
