@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _binding
 
-__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_candidates", "calc_reco_metrics_from_scores", "recommend_topk", "recommend_topk_from_candidates", "recommend_topk_from_scores",
+__all__ = ["calc_reco_metrics", "calc_reco_metrics_from_candidates", "calc_reco_metrics_from_item_weights", "calc_reco_metrics_from_scores",
+           "recommend_topk", "recommend_topk_from_candidates", "recommend_topk_from_item_weights", "recommend_topk_from_scores",
            "split_reco_train_test"]
 __version__ = "0.1.0"
 
@@ -900,3 +901,170 @@ def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_sc
         scores = _cpu_tensor_as_array(torch, scores, kind)
     S, lds = _row_major_with_ld(scores.astype(dtype, copy=False))
     return _binding.recommend_scores(S, lds, excl_p, excl_i, k, bool(return_scores))
+
+
+# ---- item-item models: scores = X_hist @ W, formed on the device from the history rows ---------------------------------------------
+def _item_weights(W, what):
+    """(torch or None, kind, dtype) of a weight matrix: a 2-d numeric NumPy array, or a float32 / float64 torch tensor"""
+    torch = _torch_if_tensor(W)
+    _fail_if(torch is None and not isinstance(W, np.ndarray), "'W' must be a NumPy array or a torch tensor.")
+    _fail_if(W.ndim != 2, "'W' must be a 2-dimensional array.")
+    kind = _tensor_kind(torch, W) if torch else None
+    _fail_if(isinstance(kind, str) or (torch is None and W.dtype == np.float16), "16-bit 'W' is not supported %s: pass float32 (or float64) weights." % what)
+    _fail_if(kind is None if torch else W.dtype.kind not in "fiub", "'W' must be a numeric array.")
+    _fail_if(0 in tuple(W.shape), "Input matrices cannot be empty.")
+    dtype = (np.float64 if kind is np.float64 else np.float32) if torch else np.float32 if W.dtype == np.float32 else np.float64
+    return torch, kind, dtype
+
+
+def _history_arrays(X_hist, dtype):
+    """(hist_p, hist_i, hist_v) for the binding: int32 CSR, rows as they are, values in `dtype`"""
+    X_hist = _csr_int32(X_hist)
+    values = X_hist.data if X_hist.data.dtype == dtype else X_hist.data.astype(dtype)
+    return tuple(np.ascontiguousarray(a) for a in (X_hist.indptr, X_hist.indices, values))
+
+
+def _device_weights(call):
+    """the `source` of a `_DeviceCall` over W: (address, row stride, n_in) -- m and n follow from the caller"""
+    return call.S.data_ptr(), call.S.stride(0), call.S.shape[0]
+
+
+def calc_reco_metrics_from_item_weights(
+    X_train, X_test,
+    W,
+    k=5,
+    X_hist=None,
+    as_df=True,
+    precision=True,
+    trunc_precision=False,
+    recall=False,
+    average_precision=True,
+    trunc_average_precision=False,
+    ndcg=True,
+    hit=False,
+    rr=False,
+    roc_auc=False,
+    pr_auc=False,
+    all_metrics=False,
+    rename_k=True,
+    min_pos_test=1,
+    min_items_pool=2,
+    consider_cold_start=True,
+    cumulative=False,
+    nthreads=-1,
+):
+    """The metrics of :func:`calc_reco_metrics` for an ITEM-ITEM model -- EASE, SLIM, item-kNN: the scores are ``X_hist @ W``, with
+    ``W`` a dense ``[history columns, items]`` weight matrix, and they are formed on the device from the rows of ``W`` that a user's
+    history names.  The dense ``[users, items]`` product is never built, and neither is a dense ``X_hist``.  The reference has no such
+    call.
+
+    ``X_hist`` is the sparse user-item history WITH its values; ``None`` uses ``X_train`` (which then must be given, and
+    ``W.shape[0]`` must be the number of items).  Stored entries are the terms of a user's score, in ascending column order, an
+    explicit zero included; for a finite ``W`` the values returned are, bit for bit, those of
+    ``calc_reco_metrics(X_train, X_test, X_hist.toarray(), W.T, break_ties_with_noise=False)``.
+
+    ``W``: NumPy array, or a float32 / float64 ``torch.Tensor`` on the CPU or on a GPU (a GPU tensor is served on its device and on
+    torch's current stream); evaluation is in float32 only when ``W`` is float32, otherwise in float64, and the history values are
+    cast to that type.  16-bit ``W`` is not supported.  Everything else -- ``X_train`` / ``X_test``, ``k``, the metric flags and the
+    return value -- as in :func:`calc_reco_metrics_from_scores`; there is no tie noise and no seed.
+    """
+    requested = _requested_metrics(locals())
+    from scipy.sparse import issparse
+    torch, kind, dtype = _item_weights(W, "yet")
+    _fail_if(not issparse(X_test), "'X_test' must be a sparse matrix.")
+    n_users, n_items = X_test.shape
+    _fail_if(n_users >= _INT32_MAX, "Number of test user is larger than maximum supported.")
+    _fail_if(n_items >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    _fail_if(0 in (n_users, n_items), "Input matrices cannot be empty.")
+    _fail_if(X_test.data.shape[0] == 0, "'X_test' is empty.")
+    _fail_if(X_hist is None and X_train is None, "'X_hist' must be passed when there is no 'X_train'.")
+    X_hist = X_train if X_hist is None else X_hist
+    _fail_if(not issparse(X_hist), "'X_hist' must be a sparse matrix.")
+    _fail_if(W.shape[1] != n_items, "Number of columns of 'W' and of 'X_test' does not match.")
+    _fail_if(X_hist.shape[1] != W.shape[0], "Number of columns of 'X_hist' and of rows of 'W' does not match.")
+    _fail_if(X_hist.shape[0] < n_users, "'X_hist' and 'X_test' should have the same number of rows.")
+    X_train, consider_cold_start = _train_or_empty(X_train, X_test, dtype, consider_cold_start)
+    _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
+    _fail_if(X_train.shape[1] != n_items, "'X_train' and 'X_test' should have the same number of columns.")
+    _fail_if(X_train.shape[0] < n_users, "'X_train' and 'X_test' should have the same number of rows.")
+    _fail_if_no_ranking_metric(requested)
+    k, nthreads = int(k), int(nthreads)
+    min_pos_test, min_items_pool = int(min_pos_test), int(min_items_pool)
+    _fail_if(k < 1, "'k' must be positive.")
+    _fail_if(min_pos_test < 1 or min_items_pool < 1, "'min_pos_test' and 'min_items_pool' must be positive.")
+    if nthreads < 0:
+        nthreads += multiprocessing.cpu_count() + 1
+    _fail_if(nthreads <= 0, "'nthreads' must be positive (or negative: counted back from the number of CPUs).")
+    _fail_if(k > n_items, "'k' should be smaller than the number of items.")
+
+    # ---- everything above raises before the library is touched ----
+    split = _split_arrays(X_train, X_test, n_users, dtype)
+    X_hist = _csr_int32(X_hist)                               # (CSR first: other formats cannot be sliced by rows)
+    hist = _history_arrays(X_hist[:n_users] if X_hist.shape[0] > n_users else X_hist, dtype)
+    if torch and W.is_cuda:
+        want = {short: requested[name] for name, short, _ in _METRICS}
+        arrays = _binding._metric_outs(None, want, n_users, k, bool(cumulative), dtype)
+        call = _DeviceCall(torch, W, kind)
+        on_device = [call.empty(a.size) if a.size else None for a in arrays]
+        train_p, train_i, test_p, test_i, test_v = split
+        call._run(_binding.calc_metrics_item_weights_device, None, _device_weights(call) + (n_users, n_items), dict(
+            hist_p=call.put(hist[0]), hist_i=call.put(hist[1]), hist_v=call.put(hist[2]), nnz_hist=int(hist[1].shape[0]),
+            train_p=call.put(train_p), train_i=call.put(train_i), nnz_train=int(train_i.shape[0]),
+            test_p=call.put(test_p), test_i=call.put(test_i), test_v=call.put(test_v), nnz_test=int(test_i.shape[0]),
+            k_metrics=k, outs=[t.data_ptr() if t is not None else 0 for t in on_device], cumulative=bool(cumulative),
+            consider_cold_start=bool(consider_cold_start), min_items_pool=min_items_pool, min_pos_test=min_pos_test))
+        for a, t in zip(arrays, on_device):
+            if t is not None:
+                a.reshape(-1)[:] = t.cpu().numpy()
+        return _metrics_result(arrays, None, None, k, as_df, cumulative, rename_k)
+    if torch:
+        W = _cpu_tensor_as_array(torch, W, kind)
+    W, ldw = _row_major_with_ld(W.astype(dtype, copy=False))
+    want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
+    arrays = _binding.calc_metrics_item_weights(W, ldw, *hist, *split, k, want, bool(cumulative), bool(consider_cold_start),
+                                                min_items_pool, min_pos_test, nthreads, outs=outs)
+    return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
+
+
+def recommend_topk_from_item_weights(X_hist, W, k=10, X_train=None, users=None, return_scores=True):
+    """The ``k`` best items for every user of an ITEM-ITEM model: :func:`recommend_topk_from_scores` on ``X_hist @ W`` as
+    :func:`calc_reco_metrics_from_item_weights` forms it -- the lists those metrics are computed over.  The reference has no such call.
+
+    ``X_hist``: sparse ``[users, history columns]`` matrix with its values; ``W``: ``[history columns, items]``, NumPy or a float32 /
+    float64 ``torch.Tensor`` (CPU or GPU).  ``X_train``: optional sparse matrix of the items to leave out per user; ``None`` leaves
+    nothing out -- pass the history again to leave it out.  ``users``: optional integer array, lists for these rows only, in this
+    order.  Returns ``(ids, scores, status)`` shaped and coded as :func:`recommend_topk` returns them.
+    """
+    from scipy.sparse import issparse
+    torch, kind, dtype = _item_weights(W, "yet")
+    _fail_if(not issparse(X_hist), "'X_hist' must be a sparse matrix.")
+    n_users, n_items = X_hist.shape[0], W.shape[1]
+    _fail_if(X_hist.shape[1] != W.shape[0], "Number of columns of 'X_hist' and of rows of 'W' does not match.")
+    _fail_if(n_users >= _INT32_MAX, "Number of users is larger than maximum supported.")
+    _fail_if(max(n_items, W.shape[0]) >= _INT32_MAX, "Number of items is larger than maximum supported.")
+    k = _list_length(k, n_items)
+    if X_train is not None:
+        _fail_if(not issparse(X_train), "'X_train' must be a sparse matrix.")
+        _fail_if(tuple(X_train.shape) != (n_users, n_items), "'X_train' must have a row per user of 'X_hist' and a column per column of 'W'.")
+    users = _user_selection(users, n_users, "X_hist")
+
+    # ---- everything above raises before the library is touched ----
+    if users is not None:
+        X_hist = _csr_int32(X_hist)[users]
+    hist = _history_arrays(X_hist, dtype)
+    excl_p, excl_i = _exclusion_csr(X_train, users)
+    m = hist[0].shape[0] - 1
+    if m == 0:
+        return _no_lists(k, dtype, return_scores)
+    if torch and W.is_cuda:
+        call = _DeviceCall(torch, W, kind)
+        idx, sc, st = call.empty((m, k), torch.int32), call.empty((m, k)) if return_scores else None, call.empty((m,), torch.int32)
+        call._run(_binding.recommend_item_weights_device, None, _device_weights(call) + (m, n_items), dict(
+            hist_p=call.put(hist[0]), hist_i=call.put(hist[1]), hist_v=call.put(hist[2]), nnz_hist=int(hist[1].shape[0]),
+            excl_p=call.put(excl_p), excl_i=call.put(excl_i), nnz_excl=0 if excl_i is None else int(excl_i.shape[0]), k_top=k,
+            idx=idx.data_ptr(), score=sc.data_ptr() if return_scores else 0, status=st.data_ptr()))
+        return idx.cpu().numpy(), sc.cpu().numpy() if return_scores else None, st.cpu().numpy()
+    if torch:
+        W = _cpu_tensor_as_array(torch, W, kind)
+    W, ldw = _row_major_with_ld(W.astype(dtype, copy=False))
+    return _binding.recommend_item_weights(W, ldw, *hist, excl_p, excl_i, k, bool(return_scores))

@@ -90,6 +90,15 @@ CAND_METRIC_SIGNATURES = {"rm_calc_metrics_candidates" + form + suffix:
                           (tuple(("Xcand" + name[6:] if name.startswith("Xtrain") else "nnz_cand" if name == "nnz_train" else name, ctype)
                                  for name, ctype in _metrics(_FACTORS, host) if name not in _CAND_METRICS_LEFT_OUT), _ci)
                           for form, host in (("", True), ("_dev", False)) for suffix in ("_f32", "_f64")}
+# include/recometrics_hip_item_weights.h: item-item models -- the from-scores entries' rows with W and the history CSR in the place of S
+def _item_weights(host):
+    return ((("W", _vp), ("ldw", _sz), ("n_in", _i32), ("m", _i32), ("n", _i32), ("hist_p", _vp), ("hist_i", _vp), ("hist_v", _vp))
+            + (() if host else (("nnz_hist", _i64),)))
+
+
+ITEM_WEIGHT_SIGNATURES = {"rm_" + request + "_item_weights" + form + suffix: (pieces(_item_weights(host), host), _ci)
+                          for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
+                          for suffix in ("_f32", "_f64")}
 # test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
 TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
@@ -123,6 +132,7 @@ def load():
         _declare(_lib, HALF_FACTOR_SIGNATURES, HALF_FACTOR_SIGNATURES)
         _declare(_lib, CAND_SIGNATURES, CAND_SIGNATURES)
         _declare(_lib, CAND_METRIC_SIGNATURES, CAND_METRIC_SIGNATURES)
+        _declare(_lib, ITEM_WEIGHT_SIGNATURES, ITEM_WEIGHT_SIGNATURES)
         for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -302,7 +312,7 @@ def _invoke(entry, dtype, **values):
         params = (HALF_SIGNATURES if name in HALF_SIGNATURES else HALF_FACTOR_SIGNATURES)[name][0]
     else:
         name = entry + ("_f32" if dtype == np.float32 else "_f64")
-        params = (CAND_SIGNATURES if name in CAND_SIGNATURES else CAND_METRIC_SIGNATURES if name in CAND_METRIC_SIGNATURES else SIGNATURES)[name][0]
+        params = next((t for t in (CAND_SIGNATURES, CAND_METRIC_SIGNATURES, ITEM_WEIGHT_SIGNATURES) if name in t), SIGNATURES)[name][0]
     args = [values[param] for param, _ in params]
     if len(values) != len(params):
         raise TypeError("%s has no parameter %s" % (name, ", ".join(sorted(set(values) - {param for param, _ in params}))))
@@ -555,6 +565,62 @@ def recommend_scores_device(dtype, S, lds, m, n, excl_p, excl_i, nnz_excl, k_top
     nothing is left out, `score` = ids only).  Asynchronous on `stream` apart from one small plan read-back."""
     _invoke("rm_recommend_scores_dev", dtype, S=_dp(S), lds=lds, m=m, n=n, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
             nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream))
+
+
+def _item_weight_values(ptr, W, ldw, n_in, m, n, hist_p, hist_i, hist_v):
+    """what the eight entries of the item-item models share, by name"""
+    return dict(W=ptr(W), ldw=ldw, n_in=n_in, m=m, n=n, hist_p=ptr(hist_p), hist_i=ptr(hist_i), hist_v=ptr(hist_v))
+
+
+def calc_metrics_item_weights(W, ldw, hist_p, hist_i, hist_v, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
+                              consider_cold_start, min_items_pool, min_pos_test, nthreads=0, outs=None):
+    """Host-array entry of the metrics of an item-item model (rm_calc_metrics_item_weights_*): `W` [n_in, n] row-major with leading
+    dimension `ldw` (elements), the history CSR `hist_p` / `hist_i` / `hist_v` (values None: ones) of m rows over n_in columns, the
+    rest as `calc_metrics_scores`.  Returns the same 10-tuple."""
+    dtype = W.dtype.type
+    m, (n_in, n) = hist_p.shape[0] - 1, W.shape
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
+    _invoke("rm_calc_metrics_item_weights", dtype, nthreads=int(nthreads), **_item_weight_values(_p, W, ldw, n_in, m, n, hist_p, hist_i, hist_v),
+            **_metrics_values(_p, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+    return outs
+
+
+def calc_metrics_item_weights_device(dtype, W, ldw, n_in, m, n, hist_p, hist_i, hist_v, nnz_hist, train_p, train_i, nnz_train,
+                                     test_p, test_i, test_v, nnz_test, k_metrics, outs, cumulative=False, consider_cold_start=True,
+                                     min_items_pool=2, min_pos_test=1, stream=0):
+    """Device-pointer entry (rm_calc_metrics_item_weights_dev_*): every array argument is an integer device address (0 == NULL);
+    `outs` is a sequence of 10 addresses in METRIC_ORDER."""
+    _invoke("rm_calc_metrics_item_weights_dev", dtype, nnz_hist=nnz_hist, nnz_train=nnz_train, nnz_test=nnz_test, stream=_dp(stream),
+            **_item_weight_values(_dp, W, ldw, n_in, m, n, hist_p, hist_i, hist_v),
+            **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+
+
+def recommend_item_weights(W, ldw, hist_p, hist_i, hist_v, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
+    """Host-array entry of the lists of an item-item model (rm_recommend_item_weights_*): `W` and the history as in
+    `calc_metrics_item_weights`, the rest and the return value as `recommend_scores`."""
+    dtype = W.dtype.type
+    m, (n_in, n) = hist_p.shape[0] - 1, W.shape
+    idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
+    _invoke("rm_recommend_item_weights", dtype, Xexcl_csr_p=_host_excl_p(excl_p), Xexcl_csr_i=_p(excl_i), k_top=k_top, idx=_p(idx), score=_p(sc),
+            status=_p(st), nthreads=int(nthreads), **_item_weight_values(_p, W, ldw, n_in, m, n, hist_p, hist_i, hist_v))
+    return idx, sc, st
+
+
+def recommend_item_weights_device(dtype, W, ldw, n_in, m, n, hist_p, hist_i, hist_v, nnz_hist, excl_p, excl_i, nnz_excl, k_top,
+                                  idx, score, status, stream=0):
+    """Device-pointer entry (rm_recommend_item_weights_dev_*): every array argument is an integer device address (0 == NULL:
+    `hist_v` = ones, `excl_p` = nothing is left out, `score` = ids only)."""
+    _invoke("rm_recommend_item_weights_dev", dtype, nnz_hist=nnz_hist, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i), nnz_excl=nnz_excl,
+            k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream),
+            **_item_weight_values(_dp, W, ldw, n_in, m, n, hist_p, hist_i, hist_v))
+
+
+def item_weights_kernel_ms():
+    """ms of the gather kernel of the most recent batch of an item-weights call (out[12] of rm_get_timings; 0 when there was none);
+    waits for that kernel"""
+    lib = load()
+    buf = (C.c_double * 13)()
+    return float(buf[12]) if lib.rm_get_timings(buf, 13) >= 13 else 0.0
 
 
 def debug_scores(A, B):

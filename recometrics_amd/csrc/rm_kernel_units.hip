@@ -1,4 +1,4 @@
-// rm_kernel_units.hip -- the kernels of rm_prep / rm_finalize / rm_noise / rm_scores / rm_rowtopk / rm_candidates / rm_candmetrics.hpp, compiled apart from the host
+// rm_kernel_units.hip -- the kernels of rm_prep / rm_finalize / rm_noise / rm_scores / rm_rowtopk / rm_candidates / rm_candmetrics / rm_itemweights.hpp, compiled apart from the host
 // code that launches them (rm_lib.hip sees them `extern template`, or as declarations, and emits none: rm_kernel_units.hpp).
 //
 // This file is compiled once per translation unit with -DRM_KERNELS=k, units 3 and 4 once per precision with -DRM_F64=0 / 1
@@ -14,6 +14,7 @@
 //               6  rm_prep.hpp's readers of raw A / B with 16-bit factors (f16 / bf16 in, fp32 behind the load)
 //               7  rm_candidates.hpp: lists from candidate sets
 //               8  rm_candmetrics.hpp: metrics over candidate sets
+//               9  rm_itemweights.hpp: the scores of item-item models
 #include <hip/hip_runtime.h>
 
 #if RM_KERNELS == 0
@@ -55,8 +56,11 @@
 #elif RM_KERNELS == 8
 #include "rm_candmetrics.hpp"
 #define RM_UNIT_KERNELS(X) RM_CANDMETRICS_KERNELS_F32(X) RM_CANDMETRICS_KERNELS_F64(X)
+#elif RM_KERNELS == 9
+#include "rm_itemweights.hpp"
+#define RM_UNIT_KERNELS(X) RM_ITEMWEIGHTS_KERNELS_F32(X) RM_ITEMWEIGHTS_KERNELS_F64(X)
 #else
-#error "RM_KERNELS: 0 .. 8"
+#error "RM_KERNELS: 0 .. 9"
 #endif
 
 namespace rm {

@@ -1,5 +1,5 @@
 // rm_lib.hip -- host orchestration + the C-ABI of include/recometrics_hip.h, recometrics_hip_half.h, recometrics_hip_half_factors.h and
-// recometrics_hip_candidates.h, recometrics_hip_candidate_metrics.h  (gfx950 only).
+// recometrics_hip_candidates.h, recometrics_hip_candidate_metrics.h, recometrics_hip_item_weights.h  (gfx950 only).
 //
 // Host counterpart of reference src/recometrics.hpp:359-436 (prologue: clamps, scratch) and of the instantiation
 // shims src/recometrics_instantiated.cpp:30-143.  The reference's OpenMP loop over users (:428-437) becomes:
@@ -31,6 +31,7 @@
 #include "../../include/recometrics_hip_half_factors.h"
 #include "../../include/recometrics_hip_candidates.h"
 #include "../../include/recometrics_hip_candidate_metrics.h"
+#include "../../include/recometrics_hip_item_weights.h"
 #include "rm_device.hpp"
 #include "rm_prep.hpp"
 #include "rm_launch.hpp"
@@ -40,6 +41,7 @@
 #include "rm_rowtopk.hpp"
 #include "rm_candidates.hpp"
 #include "rm_candmetrics.hpp"
+#include "rm_itemweights.hpp"
 
 namespace {
 
@@ -210,7 +212,16 @@ std::atomic<unsigned long long> g_ws_stamp{1};
     X(WS_SORTED_TEI, "sorted_tei")              /* int[nnz_test] */ \
     X(WS_SORTED_TEV, "sorted_tev")              /* T[nnz_test] */ \
     X(WS_DBG_ZEROS, "dbg_zeros")                /* int[m + 1 + n_groups]: zeros for slot_chunk, train_p, train_i and gj (debug_scores) */ \
-    X(WS_DBG_DUMP, "dbg_dump")                  /* T[m][n]: every score (the sweep's DUMP variant, debug_scores) */
+    X(WS_DBG_DUMP, "dbg_dump")                  /* T[m][n]: every score (the sweep's DUMP variant, debug_scores) */ \
+    /* ---- item-item models (run_item_weights; the host entry's uploads) ---- */ \
+    X(WS_IW_SCORES, "iw_scores")                /* T[largest batch][n rounded up to 16 bytes]: the chunk of S = X_hist W (k_scores_item_weights; read by the from-scores stages) */ \
+    X(WS_IW_PLAN, "iw_plan")                    /* Plan: the verdict of the history's validation (zeroed by run_item_weights; k_check_csr_*) */ \
+    X(WS_IW_SORTED_HI, "iw_sorted_hi")          /* int[nnz_hist]: the caller's unsorted history rows, sorted by the host (item_weights_entry) */ \
+    X(WS_IW_SORTED_HV, "iw_sorted_hv")          /* T[nnz_hist]: ... and their values */ \
+    X(WS_IW_W, "iw_W")                          /* T[n_in][n rounded up to 16 bytes]: the host entry's copy of W (item_weights_host) */ \
+    X(WS_IW_HP, "iw_hp")                        /* int[m + 1]: ... of the history's index pointers */ \
+    X(WS_IW_HI, "iw_hi")                        /* int[nnz_hist]: ... its ids */ \
+    X(WS_IW_HV, "iw_hv")                        /* T[nnz_hist]: ... its values */
 #define RM_WS_ID(id, name) id,
 #define RM_WS_NAME(id, name) name,
 enum WsBuf { RM_WS_BUFFERS(RM_WS_ID) WS_COUNT };
@@ -455,7 +466,7 @@ struct Ctx {
         return pinned;
     }
     // rm_get_timings' out[]: the four stage times, then the launch the "sweep" timing brackets (launches, item splits, blocks, LDS bytes)
-    enum { TM_LAUNCHES = 4, TM_SPLITS, TM_BLOCKS, TM_LDS, TM_TIMED_SLOTS, TM_TOTAL_SLOTS, TM_SPLIT_REUSED, TM_HINTED, TM_COUNT };
+    enum { TM_LAUNCHES = 4, TM_SPLITS, TM_BLOCKS, TM_LDS, TM_TIMED_SLOTS, TM_TOTAL_SLOTS, TM_SPLIT_REUSED, TM_HINTED, TM_ITEM_WEIGHTS, TM_COUNT };
     double timings[TM_TIMED_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};
     int timed_slots = 0, total_slots = 0;     // slots (user lanes) of the sweep launch the "sweep" timing brackets / of the call
     void sweep_shape(double launches, double splits, double blocks, double lds, int slots)      // (slots < 0: nothing was launched, they stay)
@@ -472,6 +483,7 @@ struct Ctx {
     int *hint_counts = nullptr; bool hints_ran = false;
     bool high_priority = false;          // streams of this context are created with the highest priority (the exact passes of the tie noise)
     Plan *pinned_plan = nullptr;                                                    // page-locked landing place of the plan read-back
+    hipEvent_t iw_ev[2] = {nullptr, nullptr}; bool iw_timed = false;                // item-item models: around the gather kernel of the most recent batch
     void stage_ms(float ms[4]) const       // prep / sweep / finalize / total of the most recent pass, from its four events (which have completed)
     {
         const int from[4] = {EV_START, EV_PREP_END, EV_SWEEP_END, EV_START}, to[4] = {EV_PREP_END, EV_SWEEP_END, EV_END, EV_END};
@@ -568,6 +580,11 @@ template <class T> struct Request : Outputs<T> {
     // Metrics over candidate sets (rm_calc_metrics_candidates_*): `cand` WITHOUT `reco` -- the candidate rows in the same slots, a test
     // matrix and the ten outputs as in a metric call; the plan stage and k_metrics_candidates (rm_candmetrics.hpp), nothing else.
     bool cand = false;
+    // item-item models (rm_*_item_weights_*): the third score source -- S = X_hist W, W [n_in][n] with row stride ldw (elements), the
+    // history a CSR of m rows over n_in columns with optional values (null: ones).  run_item_weights forms S chunk by chunk
+    // (k_scores_item_weights, rm_itemweights.hpp) and runs a from-scores Call on each chunk; a Call never carries this source.
+    const T *W = nullptr; size_t ldw = 0; int n_in = 0; bool item_weights = false;
+    const int *hist_p = nullptr, *hist_i = nullptr; const T *hist_v = nullptr; long long nnz_hist = 0;
     Outputs<T> &outputs() { return *this; }
 };
 // Which pass of a call this is (the tie noise, rm_noise.hpp, makes several of one call), and the three groups of fields that say so.
@@ -2997,19 +3014,35 @@ void check_request(const Request<T> &r, bool host)
     const auto ndcg_has_values = [&] { if (r.out[5] && !r.test_v) fail("NDCG requested without test values"); };
     // host form (a null array: lists have no test matrix and need no exclusion matrix)
     const auto index_pointers = [&] {
-        for (const int *p : {r.train_p, r.test_p}) {
-            if (!p) continue;
+        for (const int *p : {r.train_p, r.test_p, r.hist_p}) {
+            if (!p || (p == r.hist_p && p == r.train_p)) continue;       // (the history may BE the train matrix: named once)
             int bad = p[0] < 0;
             for (int u = 0; u < r.m; u++) bad |= p[u + 1] < p[u];
             if (bad) {
                 int u = 0;
                 while (u < r.m && !(p[u] < 0 || p[u + 1] < p[u])) u++;
                 fail(std::string("CSR index pointers of row ") + std::to_string(u) + " are negative or decreasing ("
-                     + (p != r.train_p ? "X_test" : r.cand ? "X_cand" : "X_train") + ")");
+                     + (p == r.train_p ? (r.cand ? "X_cand" : "X_train") : p == r.test_p ? "X_test" : "X_hist") + ")");
             }
         }
         if (r.train_p && r.train_p[r.m] > 0 && !r.train_i) fail("null train indices");
     };
+    if (r.item_weights) {                                            // item-item models, metrics or lists: the from-scores rules behind S = X_hist W
+        if (r.m < 0 || r.n <= 0 || r.n_in <= 0) fail("m must not be negative, n and n_in must be positive");
+        if (!r.W || !r.hist_p) fail(null_in);
+        if (!r.reco && (!r.train_p || !r.test_p || (!r.test_i && nnz_test() > 0))) fail(null_in);
+        if (r.reco && (!r.topk_idx || !r.status)) fail("null output pointer");
+        if (r.ldw < (size_t)r.n) fail("leading dimension of the weight matrix smaller than n (got " + std::to_string(r.ldw) + of_n);
+        K_in_1_n(r.reco ? "k_top" : "k_metrics");
+        if (!r.reco) ndcg_has_values();
+        if (host) {
+            index_pointers();
+            if (r.hist_p[r.m] > 0 && !r.hist_i) fail("null history indices");
+        }
+        else if (r.nnz_hist < 0 || r.nnz_train < 0 || r.nnz_test < 0) fail("negative length of an index array");
+        else if ((r.nnz_hist > 0 && !r.hist_i) || (r.train_p && r.nnz_train > 0 && !r.train_i)) fail(null_in);
+        return;
+    }
     if (r.cand && !r.reco) {                                         // metrics over candidate sets: k_metrics may exceed a row, and n
         if (r.m < 0 || r.n <= 0 || r.k <= 0) fail(mnk);
         if (!r.A || !r.B || !r.train_p || !r.test_p || (!r.test_i && nnz_test() > 0)) fail(null_in);
@@ -3344,6 +3377,207 @@ template <class T> void rank_entry(Request<T> r, int *topk_idx, T *topk_score, l
     host_entry<T>(r, 0);
 }
 
+// ---- item-item models (include/recometrics_hip_item_weights.h): S = X_hist W chunk by chunk in front of the from-scores stages -------
+template <class T>
+Request<T> from_item_weights(const T *W, size_t ldw, int n_in, const int *hist_p, const int *hist_i, const T *hist_v, long long nnz_hist)
+{
+    Request<T> r;
+    r.W = W; r.ldw = ldw; r.n_in = n_in; r.hist_p = hist_p; r.hist_i = hist_i; r.hist_v = hist_v; r.nnz_hist = nnz_hist; r.item_weights = true;
+    return r;
+}
+// Users per batch: the chunk (ws.get rounds an allocation up by an eighth) plus the masked row run() wants of every user inside a third
+// of what is then free -- b (1.125 + 3) rows <= free memory, taken as 5 rows as the from-scores host batches take 7 for 5.25;
+// RM_BATCH_USERS caps it.  The gather's grid (column tiles x blocks of four users) stays below 2^23 blocks.
+template <class T> long long item_weight_batch_users(const Workspace &ws, int n)
+{
+    const long long row = score_row_stride(n) * (long long)sizeof(T);
+    long long batch = free_plus_owned(ws, {WS_STREAM_SCORES, WS_SEL_HI, WS_SEL_LO, WS_IW_SCORES}) / (5 * row);
+    if (g_sw.stream_budget_mb >= 0) batch = std::min<long long>(batch, stream_budget_bytes(ws) * 3 / 4 / row);
+    if (g_sw.batch_users > 0) batch = std::min<long long>(batch, (long long)g_sw.batch_users);
+    batch = std::min<long long>(batch, 4 * ((1ll << 23) / cdiv(n, ItemWeightTile<T>::COLS)));
+    return std::max<long long>(1, std::min<long long>(batch, 1 << 20));
+}
+// The history rows of all m users, validated as every CSR input is (rm_prep.hpp's checks, the column bound n_in), in a Plan of their
+// own -- the from-scores passes zero WS_PLAN batch by batch, and the gather kernel of every batch reads this verdict.
+template <class T>
+void check_history(const Request<T> &r, Plan *plan, hipStream_t stream)
+{
+    HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
+    hipLaunchKernelGGL(k_check_csr_ptr, dim3(cdiv(r.m, 256)), dim3(256), 0, stream, r.m, r.hist_p, r.nnz_hist, r.hist_p, r.nnz_hist, plan);
+    hipLaunchKernelGGL(k_check_csr_starts, dim3(cdiv(r.m, 1024)), dim3(1024), 0, stream, r.m, r.hist_p, r.hist_i, (const int *)nullptr, (const int *)nullptr, plan);
+    if (r.nnz_hist > 0)
+        hipLaunchKernelGGL(k_check_csr_flat, dim3((unsigned)std::min<long long>((r.nnz_hist / 4 + 2 + CHECK_FLAT_THREADS - 1) / CHECK_FLAT_THREADS, CHECK_FLAT_BLOCKS)),
+                           dim3(CHECK_FLAT_THREADS), 0, stream, r.m, r.n_in, r.hist_p, r.hist_i, plan, 0);
+    HIP_CHECK(hipGetLastError());
+    Plan hp;
+    HIP_CHECK(hipMemcpyAsync(&hp, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (hp.csr_bad & CSR_BAD_INDPTR)
+        throw RmError{RM_ERR_INVALID, "CSR index pointers of row " + std::to_string(hp.csr_where) + " are negative, decreasing or beyond the index array (X_hist)"};
+    if (hp.csr_bad & CSR_BAD_INDEX)
+        throw RmError{RM_ERR_INVALID, "CSR column index out of range [0, " + std::to_string(r.n_in) + ") in row " + std::to_string(hp.csr_where) + " (X_hist)"};
+    if (hp.csr_desc_all[0] != hp.csr_desc_legit[0]) throw RmError{RM_INTERNAL_UNSORTED, "CSR rows are not sorted"};
+}
+// One request with device pointers (the context's mutex is held): the history is validated once, the user range cut into batches, and
+// per batch the gather fills the chunk and the from-scores Call of that user range runs on (chunk, its stride).  A kept split and
+// warm bounds are bypassed for this source: a from-scores Call keeps and reuses neither (Pipeline::make_split_key).
+template <class T>
+void run_item_weights(const Request<T> &r, hipStream_t stream, Ctx &cx, bool host)
+{
+    typedef ItemWeightTile<T> G;
+    Workspace &ws = cx.ws;
+    const int m = r.m, n = r.n;
+    cx.acc[0] = cx.acc[1] = cx.acc[2] = cx.acc[3] = 0;
+    if (cx.ev_valid) HIP_CHECK(hipStreamWaitEvent(stream, cx.done, 0));  // (an earlier call on another stream may still read the buffers below)
+    if (!cx.iw_ev[0]) for (hipEvent_t &e : cx.iw_ev) HIP_CHECK(hipEventCreate(&e));
+    Plan *plan = ws.array<Plan>(WS_IW_PLAN, 1);
+    check_history<T>(r, plan, stream);
+    const int *train_p = r.train_p, *train_i = r.train_i;
+    if (r.reco && !train_p) {                                        // lists without an exclusion matrix: a row of zeros (run_dev)
+        int *z = ws.array<int>(WS_RECO_ZERO_P, (size_t)m + 1);
+        HIP_CHECK(hipMemsetAsync(z, 0, sizeof(int) * ((size_t)m + 1), stream));
+        train_p = z; train_i = z;
+    }
+    const size_t lds = ((size_t)n + G::VE - 1) / G::VE * G::VE;      // the chunk's row stride: whole 16-byte vectors
+    const long long batch = item_weight_batch_users<T>(ws, n);
+    const bool vec = ((((size_t)r.W) | (r.ldw * sizeof(T))) & 15) == 0;
+    const MetricLayout lay(r.out, r.cumulative ? (size_t)r.K : 1);
+    for (long long b0 = 0; b0 < m && !(host && g_interrupt); b0 += batch) {      // (the host form owns the flag: SignalGuard)
+        const int mb = (int)std::min<long long>(batch, m - b0);
+        T *S = ws.array<T>(WS_IW_SCORES, (size_t)mb * lds);
+        ItemWeightArgs<T> ka{r.W, r.ldw, n, mb, r.hist_p + b0, r.hist_i, r.hist_v, plan, S, lds, cdiv(mb, IW_THREADS / WAVE)};
+        const dim3 grid(cdiv(n, G::COLS) * ka.ublocks);              // the column tile slow, users fast
+        HIP_CHECK(hipEventRecord(cx.iw_ev[0], stream));
+        if (vec) hipLaunchKernelGGL((k_scores_item_weights<T, true>), grid, dim3(IW_THREADS), 0, stream, ka);
+        else hipLaunchKernelGGL((k_scores_item_weights<T, false>), grid, dim3(IW_THREADS), 0, stream, ka);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(cx.iw_ev[1], stream));
+        cx.iw_timed = true;
+        Call<T> c(from_scores<T>(S, lds));
+        c.m = mb; c.n = n; c.user0 = b0;
+        c.train_p = train_p + b0; c.train_i = train_i; c.nnz_train = r.train_p ? r.nnz_train : 0;
+        if (!r.reco) { c.test_p = r.test_p + b0; c.test_i = r.test_i; c.test_v = r.test_v; c.nnz_test = r.nnz_test; }
+        c.K = r.K; c.cumulative = r.cumulative; c.cold = r.cold; c.min_items_pool = r.min_items_pool; c.min_pos_test = r.min_pos_test; c.reco = r.reco;
+        c.outputs() = r.from_user((size_t)b0, lay.per, r.K);
+        run_call<T>(c, stream, cx);
+    }
+}
+// The device form, with the sorted-copy fall-back of run_dev: when a row of the history, the train or the test matrix is unsorted, copies
+// of all three are sorted on the host (rm_csr_sort_rows carries the values) and the request runs again on the copies.
+template <class T>
+void item_weights_entry(Request<T> r, hipStream_t stream, Ctx &cx, int nthreads, bool host)
+{
+    try { run_item_weights<T>(r, stream, cx, host); return; }
+    catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; }
+    const size_t m1 = (size_t)r.m + 1;
+    // (v == nullptr: rows without values -- the train matrix has none, and no value buffer: WS_COUNT names no buffer)
+    struct Rows { const int *p; const int **i; const T **v; long long nnz; WsBuf wi, wv; };
+    const Rows rows[3] = {{r.hist_p, &r.hist_i, &r.hist_v, r.nnz_hist, WS_IW_SORTED_HI, WS_IW_SORTED_HV},
+                          {r.train_p, &r.train_i, nullptr, r.nnz_train, WS_SORTED_TRI, WS_COUNT},
+                          {r.test_p, &r.test_i, &r.test_v, r.nnz_test, WS_SORTED_TEI, WS_SORTED_TEV}};
+    for (const Rows &x : rows) {
+        const size_t nnz = (size_t)std::max<long long>(x.nnz, 0);
+        if (!x.p || !nnz) continue;
+        const T *values = x.v ? *x.v : nullptr;
+        std::vector<int> p(m1), idx(nnz);
+        std::vector<T> val(values ? nnz : 0);
+        HIP_CHECK(hipMemcpyAsync(p.data(), x.p, sizeof(int) * m1, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(idx.data(), *x.i, sizeof(int) * nnz, hipMemcpyDeviceToHost, stream));
+        if (values) HIP_CHECK(hipMemcpyAsync(val.data(), values, sizeof(T) * nnz, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        if (rm_csr_sort_rows(p.data(), idx.data(), values ? (void *)val.data() : nullptr, values ? (int32_t)sizeof(T) : 0, r.m, nthreads) != RM_OK)
+            throw RmError{RM_ERR_NOMEM, "sorting a copy of the CSR rows failed"};
+        int *di = cx.ws.array<int>(x.wi, nnz);
+        HIP_CHECK(hipMemcpyAsync(di, idx.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, stream));
+        *x.i = di;
+        if (values) {
+            T *dv = cx.ws.array<T>(x.wv, nnz);
+            HIP_CHECK(hipMemcpyAsync(dv, val.data(), sizeof(T) * nnz, hipMemcpyHostToDevice, stream));
+            *x.v = dv;
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));                     // (the vectors go out of scope)
+    }
+    try { run_item_weights<T>(r, stream, cx, host); }
+    catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; throw RmError{RM_ERR_INVALID, "CSR rows are not sorted"}; }
+}
+template <class T> void item_weights_dev(const Request<T> &r, void *stream)
+{
+    if (r.m == 0) return;
+    check_request(r, false);
+    Ctx &cx = context(0);
+    std::lock_guard<std::mutex> lk(cx.mu);
+    item_weights_entry<T>(r, (hipStream_t)stream, cx, 0, false);
+}
+// The host form: W, the history and the split are uploaded once, the device form runs on the copies, the outputs come back in one
+// block.  One device -- the first of rm_set_devices, or the calling thread's current one; this source is not sharded.
+template <class T> void item_weights_host(Request<T> h, int nthreads)
+{
+    if (h.m == 0) return;
+    check_request(h, true);
+    std::vector<int> devs;
+    { std::lock_guard<std::mutex> lk(g_dev_mu); devs = g_devices; }
+    int prev = -1;
+    if (!devs.empty()) { HIP_CHECK(hipGetDevice(&prev)); HIP_CHECK(hipSetDevice(devs[0])); }
+    struct Restore { int prev; ~Restore() { if (prev >= 0) (void)hipSetDevice(prev); } } restore{prev};
+    SignalGuard guard;
+    {
+        Ctx &cx = context(0);
+        std::lock_guard<std::mutex> lk(cx.mu);
+        if (cx.ev_valid) HIP_CHECK(hipEventSynchronize(cx.done));     // (the upload buffers may still be read by the call before)
+        Workspace &ws = cx.ws;
+        hipStream_t stream = nullptr;
+        const size_t m1 = (size_t)h.m + 1, ve = 16 / sizeof(T), ldw = ((size_t)h.n + ve - 1) / ve * ve;
+        Request<T> d = h;
+        const auto put = [&](WsBuf id, const void *src, size_t bytes) -> void * {
+            void *dst = ws.get(id, std::max<size_t>(bytes, 1));
+            if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+            return dst;
+        };
+        T *dW = ws.array<T>(WS_IW_W, (size_t)h.n_in * ldw);
+        HIP_CHECK(hipMemcpy2DAsync(dW, sizeof(T) * ldw, h.W, sizeof(T) * h.ldw, sizeof(T) * (size_t)h.n, (size_t)h.n_in, hipMemcpyHostToDevice, stream));
+        d.W = dW; d.ldw = ldw;
+        d.nnz_hist = h.hist_p[h.m];
+        d.hist_p = (const int *)put(WS_IW_HP, h.hist_p, sizeof(int) * m1);
+        d.hist_i = (const int *)put(WS_IW_HI, h.hist_i, sizeof(int) * (size_t)d.nnz_hist);
+        if (h.hist_v) d.hist_v = (const T *)put(WS_IW_HV, h.hist_v, sizeof(T) * (size_t)d.nnz_hist);
+        if (h.train_p) {
+            d.nnz_train = h.train_p[h.m];
+            d.train_p = (const int *)put(WS_IN_TRP, h.train_p, sizeof(int) * m1);
+            d.train_i = (const int *)put(WS_IN_TRI, h.train_i, sizeof(int) * (size_t)d.nnz_train);
+        }
+        if (h.test_p) {
+            d.nnz_test = h.test_p[h.m];
+            d.test_p = (const int *)put(WS_IN_TEP, h.test_p, sizeof(int) * m1);
+            d.test_i = (const int *)put(WS_IN_TEI, h.test_i, sizeof(int) * (size_t)d.nnz_test);
+            if (h.test_v) d.test_v = (const T *)put(WS_IN_TEV, h.test_v, sizeof(T) * (size_t)d.nnz_test);
+        }
+        const MetricLayout lay(h.out, h.cumulative ? (size_t)h.K : 1);
+        const size_t users = (size_t)h.m, lists = users * (size_t)h.K;
+        T *block = nullptr;
+        if (h.reco) {
+            d.topk_idx = ws.array<int>(WS_O_TOPK_IDX, lists);
+            d.topk_score = h.topk_score ? ws.array<T>(WS_O_TOPK_SCORE, lists) : nullptr;
+            d.status = ws.array<int>(WS_O_STATUS, users);
+        } else {
+            block = ws.array<T>(WS_O_BLOCK, std::max<size_t>(lay.block_size(users), 1));
+            lay.point_at(block, users, d.out);
+        }
+        item_weights_entry<T>(d, stream, cx, nthreads, true);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        if (!g_interrupt) {                                          // (interrupted: some users were skipped -- nothing is handed over)
+            if (h.reco) {
+                HIP_CHECK(hipMemcpy(h.topk_idx, d.topk_idx, sizeof(int) * lists, hipMemcpyDeviceToHost));
+                if (h.topk_score) HIP_CHECK(hipMemcpy(h.topk_score, d.topk_score, sizeof(T) * lists, hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(h.status, d.status, sizeof(int) * users, hipMemcpyDeviceToHost));
+            } else {
+                for (int i = 0; i < 10; i++)
+                    if (h.out[i]) HIP_CHECK(hipMemcpy(h.out[i], d.out[i], sizeof(T) * lay.width(i) * users, hipMemcpyDeviceToHost));
+            }
+        }
+    }
+    guard.check();
+}
+
 } // namespace
 
 // =====================================================================================================================
@@ -3554,6 +3788,73 @@ extern "C" int rm_recommend_scores_dev_##SUFFIX(                                
 
 RM_RECOMMEND_SCORES_ENTRY(f32, float)
 RM_RECOMMEND_SCORES_ENTRY(f64, double)
+
+// item-item models (include/recometrics_hip_item_weights.h): the from-scores entries with S = X_hist W formed chunk by chunk
+#define RM_ITEM_WEIGHTS_ENTRY(SUFFIX, T)                                                                                \
+extern "C" int rm_calc_metrics_item_weights_##SUFFIX(                                                                   \
+    const T *W, size_t ldw, int32_t n_in, int32_t m, int32_t n,                                                         \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v,                                                      \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,                                                           \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr,                                         \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads)     \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_host<T>(metrics_request<T>(from_item_weights<T>(W, ldw, n_in, hist_p, hist_i, hist_v, 0), m, n,    \
+                                                Xtrain_csr_p, Xtrain_csr_i, 0, Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0,  \
+                                                k_metrics, cumulative, 0,                                               \
+                                                {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k,       \
+                                                 rr_at_k, roc_auc, pr_auc},                                             \
+                                                consider_cold_start, min_items_pool, min_pos_test, 0),                  \
+                             nthreads > 0 ? nthreads : 0);                                                              \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_calc_metrics_item_weights_dev_##SUFFIX(                                                               \
+    const T *W, size_t ldw, int32_t n_in, int32_t m, int32_t n,                                                         \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v, int64_t nnz_hist,                                    \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,                                        \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr, int64_t nnz_test,                       \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, void *stream)         \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_dev<T>(metrics_request<T>(from_item_weights<T>(W, ldw, n_in, hist_p, hist_i, hist_v, nnz_hist),    \
+                                               m, n, Xtrain_csr_p, Xtrain_csr_i, nnz_train, Xtest_csr_p, Xtest_csr_i,   \
+                                               Xtest_csr, nnz_test, k_metrics, cumulative, 0,                           \
+                                               {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k,        \
+                                                rr_at_k, roc_auc, pr_auc},                                              \
+                                               consider_cold_start, min_items_pool, min_pos_test, 0), stream);          \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_item_weights_##SUFFIX(                                                                      \
+    const T *W, size_t ldw, int32_t n_in, int32_t m, int32_t n,                                                         \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v,                                                      \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
+    int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_host<T>(lists_request<T>(from_item_weights<T>(W, ldw, n_in, hist_p, hist_i, hist_v, 0), m, n,      \
+                                              Xexcl_csr_p, Xexcl_csr_i, 0, k_top, idx, score, status),                  \
+                             nthreads > 0 ? nthreads : 0);                                                              \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_item_weights_dev_##SUFFIX(                                                                  \
+    const T *W, size_t ldw, int32_t n_in, int32_t m, int32_t n,                                                         \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v, int64_t nnz_hist,                                    \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
+    int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_dev<T>(lists_request<T>(from_item_weights<T>(W, ldw, n_in, hist_p, hist_i, hist_v, nnz_hist),      \
+                                             m, n, Xexcl_csr_p, Xexcl_csr_i, nnz_excl, k_top, idx, score, status),      \
+                            stream);                                                                                    \
+    });                                                                                                                 \
+}
+
+RM_ITEM_WEIGHTS_ENTRY(f32, float)
+RM_ITEM_WEIGHTS_ENTRY(f64, double)
 
 // ---- 16-bit score matrices (include/recometrics_hip_half.h): the four from-scores entries of fp32 with S in IEEE binary16 / bfloat16 ----
 #define RM_HALF_ENTRY(SUFFIX, TYPE)                                                                                     \
@@ -3828,6 +4129,11 @@ extern "C" int rm_get_timings(double *out, int n)
     if (cnt > Ctx::TM_TOTAL_SLOTS) out[Ctx::TM_TOTAL_SLOTS] = cx->total_slots;
     if (cnt > Ctx::TM_SPLIT_REUSED) out[Ctx::TM_SPLIT_REUSED] = cx->split_reused;
     if (cnt > Ctx::TM_HINTED) out[Ctx::TM_HINTED] = (cx->hints_ran && cx->ev_recorded && cx->hint_counts) ? cx->hint_counts[0] : 0;      // (EV_END is behind the counts' copy)
+    if (cnt > Ctx::TM_ITEM_WEIGHTS) {                                // ms of the most recent batch's k_scores_item_weights; 0 = none yet
+        float iw = 0;
+        if (cx->iw_timed && hipEventSynchronize(cx->iw_ev[1]) == hipSuccess) (void)hipEventElapsedTime(&iw, cx->iw_ev[0], cx->iw_ev[1]);
+        out[Ctx::TM_ITEM_WEIGHTS] = iw;
+    }
     return cnt;
 }
 
