@@ -302,7 +302,7 @@ class _DeviceCall:
 
     def __init__(self, torch, scores, kind):
         self.torch, self.kind, self.device = torch, kind, scores.device
-        self.S = self.row_major(scores)
+        self.S = self.row_major(scores) if scores.layout == torch.strided else scores.detach()      # (a sparse-CSR W: its three tensors)
         self.out_dtype = torch.float64 if kind is np.float64 else torch.float32
         self.np_dtype = np.float64 if kind is np.float64 else np.float32
         self.keep = []                                              # the uploads live until the stream has been synchronised
@@ -905,16 +905,45 @@ def recommend_topk_from_scores(scores, k=10, X_train=None, users=None, return_sc
 
 # ---- item-item models: scores = X_hist @ W, formed on the device from the history rows ---------------------------------------------
 def _item_weights(W, what):
-    """(torch or None, kind, dtype) of a weight matrix: a 2-d numeric NumPy array, or a float32 / float64 torch tensor"""
+    """(torch or None, kind, dtype, sparse) of a weight matrix: a 2-d numeric NumPy array, a float32 / float64 torch tensor, or --
+    `sparse` -- a SciPy sparse matrix / array of any format or a torch sparse-CSR tensor"""
+    from scipy.sparse import issparse
     torch = _torch_if_tensor(W)
-    _fail_if(torch is None and not isinstance(W, np.ndarray), "'W' must be a NumPy array or a torch tensor.")
+    sparse = issparse(W) or (torch is not None and W.layout == torch.sparse_csr)
+    _fail_if(torch is None and not sparse and not isinstance(W, np.ndarray), "'W' must be a NumPy array, a SciPy sparse matrix or a torch tensor.")
+    _fail_if(torch is not None and not sparse and W.layout != torch.strided, "a sparse 'W' tensor must have the sparse-CSR layout.")
     _fail_if(W.ndim != 2, "'W' must be a 2-dimensional array.")
     kind = _tensor_kind(torch, W) if torch else None
     _fail_if(isinstance(kind, str) or (torch is None and W.dtype == np.float16), "16-bit 'W' is not supported %s: pass float32 (or float64) weights." % what)
     _fail_if(kind is None if torch else W.dtype.kind not in "fiub", "'W' must be a numeric array.")
     _fail_if(0 in tuple(W.shape), "Input matrices cannot be empty.")
     dtype = (np.float64 if kind is np.float64 else np.float32) if torch else np.float32 if W.dtype == np.float32 else np.float64
-    return torch, kind, dtype
+    return torch, kind, dtype, sparse
+
+
+def _sparse_weight_arrays(torch, W, dtype):
+    """(W_p, W_i, W_v) of a sparse W on the host for the binding: int32 CSR in canonical form -- rows ascending, duplicates summed, in a
+    COPY when the caller's matrix is not canonical --, values in `dtype`.  A CPU sparse-CSR tensor goes the same way."""
+    from scipy.sparse import csr_array
+    if torch:
+        W = W.detach()
+        W = csr_array((W.values().numpy(), W.col_indices().numpy(), W.crow_indices().numpy()), shape=tuple(W.shape))
+    W = _csr_int32(W)
+    if not W.has_canonical_format:
+        W = W.copy()
+        W.sum_duplicates()
+    return tuple(np.ascontiguousarray(a) for a in (W.indptr, W.indices, W.data if W.data.dtype == dtype else W.data.astype(dtype)))
+
+
+def _device_sparse_weights(torch, call):
+    """the `source` of a `_DeviceCall` over a GPU sparse-CSR tensor: (W_p, W_i, W_v, nnz_W, n_in) -- int32 index tensors, converted on the
+    tensor's device when they are int64; the library validates the rows (and sorts unsorted ones in a copy)"""
+    W = call.S
+    W_p, W_i, W_v = W.crow_indices().to(torch.int32).contiguous(), W.col_indices().to(torch.int32).contiguous(), W.values().contiguous()
+    if W_v.numel() == 0:                                            # (no stored entry: the value array must still be one)
+        W_v = call.empty((1,), W_v.dtype)
+    call.keep.extend((W_p, W_i, W_v))
+    return W_p.data_ptr(), W_i.data_ptr() if W_i.numel() else 0, W_v.data_ptr(), int(W_i.shape[0]), W.shape[0]
 
 
 def _history_arrays(X_hist, dtype):
@@ -954,7 +983,7 @@ def calc_reco_metrics_from_item_weights(
     nthreads=-1,
 ):
     """The metrics of :func:`calc_reco_metrics` for an ITEM-ITEM model -- EASE, SLIM, item-kNN: the scores are ``X_hist @ W``, with
-    ``W`` a dense ``[history columns, items]`` weight matrix, and they are formed on the device from the rows of ``W`` that a user's
+    ``W`` a dense or sparse ``[history columns, items]`` weight matrix, and they are formed on the device from the rows of ``W`` that a user's
     history names.  The dense ``[users, items]`` product is never built, and neither is a dense ``X_hist``.  The reference has no such
     call.
 
@@ -965,12 +994,18 @@ def calc_reco_metrics_from_item_weights(
 
     ``W``: NumPy array, or a float32 / float64 ``torch.Tensor`` on the CPU or on a GPU (a GPU tensor is served on its device and on
     torch's current stream); evaluation is in float32 only when ``W`` is float32, otherwise in float64, and the history values are
-    cast to that type.  16-bit ``W`` is not supported.  Everything else -- ``X_train`` / ``X_test``, ``k``, the metric flags and the
+    cast to that type.  16-bit ``W`` is not supported.
+
+    A SPARSE ``W`` -- SLIM, item-kNN: a SciPy sparse matrix or array of any format, or a torch sparse-CSR tensor (CPU or GPU; int64
+    index tensors are converted to int32 on their device) -- is never densified: the scores are formed from its stored entries only,
+    an explicit zero being a term and an entry that is not stored being skipped, which for a finite ``W`` gives the bits of
+    ``W.toarray()``.  A matrix that is not in canonical form is brought to it in a copy (duplicates are summed there); a GPU tensor
+    goes to the library as it is, which sorts unsorted rows in a copy and refuses a column repeated inside a row.  Everything else -- ``X_train`` / ``X_test``, ``k``, the metric flags and the
     return value -- as in :func:`calc_reco_metrics_from_scores`; there is no tie noise and no seed.
     """
     requested = _requested_metrics(locals())
     from scipy.sparse import issparse
-    torch, kind, dtype = _item_weights(W, "yet")
+    torch, kind, dtype, sparse = _item_weights(W, "yet")
     _fail_if(not issparse(X_test), "'X_test' must be a sparse matrix.")
     n_users, n_items = X_test.shape
     _fail_if(n_users >= _INT32_MAX, "Number of test user is larger than maximum supported.")
@@ -1007,7 +1042,9 @@ def calc_reco_metrics_from_item_weights(
         call = _DeviceCall(torch, W, kind)
         on_device = [call.empty(a.size) if a.size else None for a in arrays]
         train_p, train_i, test_p, test_i, test_v = split
-        call._run(_binding.calc_metrics_item_weights_device, None, _device_weights(call) + (n_users, n_items), dict(
+        entry, source = ((_binding.calc_metrics_item_weights_csr_device, _device_sparse_weights(torch, call)) if sparse else
+                         (_binding.calc_metrics_item_weights_device, _device_weights(call)))
+        call._run(entry, None, source + (n_users, n_items), dict(
             hist_p=call.put(hist[0]), hist_i=call.put(hist[1]), hist_v=call.put(hist[2]), nnz_hist=int(hist[1].shape[0]),
             train_p=call.put(train_p), train_i=call.put(train_i), nnz_train=int(train_i.shape[0]),
             test_p=call.put(test_p), test_i=call.put(test_i), test_v=call.put(test_v), nnz_test=int(test_i.shape[0]),
@@ -1017,10 +1054,14 @@ def calc_reco_metrics_from_item_weights(
             if t is not None:
                 a.reshape(-1)[:] = t.cpu().numpy()
         return _metrics_result(arrays, None, None, k, as_df, cumulative, rename_k)
+    want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
+    if sparse:
+        arrays = _binding.calc_metrics_item_weights_csr(*_sparse_weight_arrays(torch, W, dtype), n_items, *hist, *split, k, want, bool(cumulative),
+                                                        bool(consider_cold_start), min_items_pool, min_pos_test, nthreads, outs=outs)
+        return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
     if torch:
         W = _cpu_tensor_as_array(torch, W, kind)
     W, ldw = _row_major_with_ld(W.astype(dtype, copy=False))
-    want, outs, block, keys = _output_storage(requested, n_users, dtype, as_df, cumulative)
     arrays = _binding.calc_metrics_item_weights(W, ldw, *hist, *split, k, want, bool(cumulative), bool(consider_cold_start),
                                                 min_items_pool, min_pos_test, nthreads, outs=outs)
     return _metrics_result(arrays, block, keys, k, as_df, cumulative, rename_k)
@@ -1031,12 +1072,13 @@ def recommend_topk_from_item_weights(X_hist, W, k=10, X_train=None, users=None, 
     :func:`calc_reco_metrics_from_item_weights` forms it -- the lists those metrics are computed over.  The reference has no such call.
 
     ``X_hist``: sparse ``[users, history columns]`` matrix with its values; ``W``: ``[history columns, items]``, NumPy or a float32 /
-    float64 ``torch.Tensor`` (CPU or GPU).  ``X_train``: optional sparse matrix of the items to leave out per user; ``None`` leaves
+    float64 ``torch.Tensor`` (CPU or GPU), or sparse -- SciPy of any format, or a torch sparse-CSR tensor -- as in
+    :func:`calc_reco_metrics_from_item_weights`.  ``X_train``: optional sparse matrix of the items to leave out per user; ``None`` leaves
     nothing out -- pass the history again to leave it out.  ``users``: optional integer array, lists for these rows only, in this
     order.  Returns ``(ids, scores, status)`` shaped and coded as :func:`recommend_topk` returns them.
     """
     from scipy.sparse import issparse
-    torch, kind, dtype = _item_weights(W, "yet")
+    torch, kind, dtype, sparse = _item_weights(W, "yet")
     _fail_if(not issparse(X_hist), "'X_hist' must be a sparse matrix.")
     n_users, n_items = X_hist.shape[0], W.shape[1]
     _fail_if(X_hist.shape[1] != W.shape[0], "Number of columns of 'X_hist' and of rows of 'W' does not match.")
@@ -1059,11 +1101,15 @@ def recommend_topk_from_item_weights(X_hist, W, k=10, X_train=None, users=None, 
     if torch and W.is_cuda:
         call = _DeviceCall(torch, W, kind)
         idx, sc, st = call.empty((m, k), torch.int32), call.empty((m, k)) if return_scores else None, call.empty((m,), torch.int32)
-        call._run(_binding.recommend_item_weights_device, None, _device_weights(call) + (m, n_items), dict(
+        entry, source = ((_binding.recommend_item_weights_csr_device, _device_sparse_weights(torch, call)) if sparse else
+                         (_binding.recommend_item_weights_device, _device_weights(call)))
+        call._run(entry, None, source + (m, n_items), dict(
             hist_p=call.put(hist[0]), hist_i=call.put(hist[1]), hist_v=call.put(hist[2]), nnz_hist=int(hist[1].shape[0]),
             excl_p=call.put(excl_p), excl_i=call.put(excl_i), nnz_excl=0 if excl_i is None else int(excl_i.shape[0]), k_top=k,
             idx=idx.data_ptr(), score=sc.data_ptr() if return_scores else 0, status=st.data_ptr()))
         return idx.cpu().numpy(), sc.cpu().numpy() if return_scores else None, st.cpu().numpy()
+    if sparse:
+        return _binding.recommend_item_weights_csr(*_sparse_weight_arrays(torch, W, dtype), n_items, *hist, excl_p, excl_i, k, bool(return_scores))
     if torch:
         W = _cpu_tensor_as_array(torch, W, kind)
     W, ldw = _row_major_with_ld(W.astype(dtype, copy=False))

@@ -99,6 +99,14 @@ def _item_weights(host):
 ITEM_WEIGHT_SIGNATURES = {"rm_" + request + "_item_weights" + form + suffix: (pieces(_item_weights(host), host), _ci)
                           for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
                           for suffix in ("_f32", "_f64")}
+# include/recometrics_hip_item_weights_csr.h: ... with a sparse W -- `W, ldw` replaced by the CSR's three arrays, `nnz_W` next to `nnz_hist`
+def _item_weights_csr(host):
+    return ((("W_p", _vp), ("W_i", _vp), ("W_v", _vp)) + _item_weights(True)[2:] + (() if host else (("nnz_hist", _i64), ("nnz_W", _i64))))
+
+
+ITEM_WEIGHT_CSR_SIGNATURES = {"rm_" + request + "_item_weights_csr" + form + suffix: (pieces(_item_weights_csr(host), host), _ci)
+                              for request, pieces in (("calc_metrics", _metrics), ("recommend", _lists)) for form, host in (("", True), ("_dev", False))
+                              for suffix in ("_f32", "_f64")}
 # test hooks the library exports beside the header's API (csrc/rm_lib.hip states what each is for): same form as SIGNATURES
 TEST_HOOKS = {"rm_debug_set_list_ids": ((("ids", C.POINTER(_i32)), ("m", _i32), ("K", _i32)), _ci)}
 
@@ -133,6 +141,7 @@ def load():
         _declare(_lib, CAND_SIGNATURES, CAND_SIGNATURES)
         _declare(_lib, CAND_METRIC_SIGNATURES, CAND_METRIC_SIGNATURES)
         _declare(_lib, ITEM_WEIGHT_SIGNATURES, ITEM_WEIGHT_SIGNATURES)
+        _declare(_lib, ITEM_WEIGHT_CSR_SIGNATURES, ITEM_WEIGHT_CSR_SIGNATURES)
         for name, (params, restype) in TEST_HOOKS.items():      # (a library from before a hook was added loads all the same)
             fn = getattr(_lib, name, None)
             if fn is not None:
@@ -312,7 +321,7 @@ def _invoke(entry, dtype, **values):
         params = (HALF_SIGNATURES if name in HALF_SIGNATURES else HALF_FACTOR_SIGNATURES)[name][0]
     else:
         name = entry + ("_f32" if dtype == np.float32 else "_f64")
-        params = next((t for t in (CAND_SIGNATURES, CAND_METRIC_SIGNATURES, ITEM_WEIGHT_SIGNATURES) if name in t), SIGNATURES)[name][0]
+        params = next((t for t in (CAND_SIGNATURES, CAND_METRIC_SIGNATURES, ITEM_WEIGHT_SIGNATURES, ITEM_WEIGHT_CSR_SIGNATURES) if name in t), SIGNATURES)[name][0]
     args = [values[param] for param, _ in params]
     if len(values) != len(params):
         raise TypeError("%s has no parameter %s" % (name, ", ".join(sorted(set(values) - {param for param, _ in params}))))
@@ -613,6 +622,61 @@ def recommend_item_weights_device(dtype, W, ldw, n_in, m, n, hist_p, hist_i, his
     _invoke("rm_recommend_item_weights_dev", dtype, nnz_hist=nnz_hist, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i), nnz_excl=nnz_excl,
             k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream),
             **_item_weight_values(_dp, W, ldw, n_in, m, n, hist_p, hist_i, hist_v))
+
+
+def _item_weight_csr_values(ptr, W_p, W_i, W_v, n_in, m, n, hist_p, hist_i, hist_v):
+    """what the eight entries of the item-item models with a sparse W share, by name"""
+    return dict(W_p=ptr(W_p), W_i=ptr(W_i), W_v=ptr(W_v), n_in=n_in, m=m, n=n, hist_p=ptr(hist_p), hist_i=ptr(hist_i), hist_v=ptr(hist_v))
+
+
+def _host_indptr(p):
+    """index pointers go over as they are, also those of a matrix without a stored entry"""
+    return None if p is None else p.ctypes.data_as(C.c_void_p)
+
+
+def calc_metrics_item_weights_csr(W_p, W_i, W_v, n, hist_p, hist_i, hist_v, train_p, train_i, test_p, test_i, test_v, k_metrics, want, cumulative,
+                                  consider_cold_start, min_items_pool, min_pos_test, nthreads=0, outs=None):
+    """`calc_metrics_item_weights` for a sparse W (rm_calc_metrics_item_weights_csr_*): the int32 CSR `W_p` / `W_i` / `W_v` of n_in rows
+    over `n` columns in the place of `W, ldw`; evaluation in the type of `W_v`."""
+    dtype = W_v.dtype.type
+    m, n_in = hist_p.shape[0] - 1, W_p.shape[0] - 1
+    outs = _metric_outs(outs, want, m, k_metrics, cumulative, dtype)
+    values = _item_weight_csr_values(_p, None, W_i, None, n_in, m, n, hist_p, hist_i, hist_v)
+    values.update(W_p=_host_indptr(W_p), W_v=_host_indptr(W_v))      # (an empty W still has its arrays)
+    _invoke("rm_calc_metrics_item_weights_csr", dtype, nthreads=int(nthreads), **values,
+            **_metrics_values(_p, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+    return outs
+
+
+def calc_metrics_item_weights_csr_device(dtype, W_p, W_i, W_v, nnz_W, n_in, m, n, hist_p, hist_i, hist_v, nnz_hist, train_p, train_i, nnz_train,
+                                         test_p, test_i, test_v, nnz_test, k_metrics, outs, cumulative=False, consider_cold_start=True,
+                                         min_items_pool=2, min_pos_test=1, stream=0):
+    """Device-pointer entry (rm_calc_metrics_item_weights_csr_dev_*): every array argument is an integer device address (0 == NULL);
+    `outs` is a sequence of 10 addresses in METRIC_ORDER."""
+    _invoke("rm_calc_metrics_item_weights_csr_dev", dtype, nnz_hist=nnz_hist, nnz_W=nnz_W, nnz_train=nnz_train, nnz_test=nnz_test, stream=_dp(stream),
+            **_item_weight_csr_values(_dp, W_p, W_i, W_v, n_in, m, n, hist_p, hist_i, hist_v),
+            **_metrics_values(_dp, train_p, train_i, test_p, test_i, test_v, k_metrics, cumulative, outs, consider_cold_start, min_items_pool, min_pos_test))
+
+
+def recommend_item_weights_csr(W_p, W_i, W_v, n, hist_p, hist_i, hist_v, excl_p, excl_i, k_top, return_scores=True, nthreads=0):
+    """`recommend_item_weights` for a sparse W (rm_recommend_item_weights_csr_*): W as in `calc_metrics_item_weights_csr`"""
+    dtype = W_v.dtype.type
+    m, n_in = hist_p.shape[0] - 1, W_p.shape[0] - 1
+    idx, sc, st = _list_outs(m, k_top, dtype, return_scores)
+    values = _item_weight_csr_values(_p, None, W_i, None, n_in, m, n, hist_p, hist_i, hist_v)
+    values.update(W_p=_host_indptr(W_p), W_v=_host_indptr(W_v))
+    _invoke("rm_recommend_item_weights_csr", dtype, Xexcl_csr_p=_host_excl_p(excl_p), Xexcl_csr_i=_p(excl_i), k_top=k_top, idx=_p(idx), score=_p(sc),
+            status=_p(st), nthreads=int(nthreads), **values)
+    return idx, sc, st
+
+
+def recommend_item_weights_csr_device(dtype, W_p, W_i, W_v, nnz_W, n_in, m, n, hist_p, hist_i, hist_v, nnz_hist, excl_p, excl_i, nnz_excl, k_top,
+                                      idx, score, status, stream=0):
+    """Device-pointer entry (rm_recommend_item_weights_csr_dev_*): every array argument is an integer device address (0 == NULL:
+    `hist_v` = ones, `excl_p` = nothing is left out, `score` = ids only)."""
+    _invoke("rm_recommend_item_weights_csr_dev", dtype, nnz_hist=nnz_hist, nnz_W=nnz_W, Xexcl_csr_p=_dp(excl_p), Xexcl_csr_i=_dp(excl_i),
+            nnz_excl=nnz_excl, k_top=k_top, idx=_dp(idx), score=_dp(score), status=_dp(status), stream=_dp(stream),
+            **_item_weight_csr_values(_dp, W_p, W_i, W_v, n_in, m, n, hist_p, hist_i, hist_v))
 
 
 def item_weights_kernel_ms():

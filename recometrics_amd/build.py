@@ -37,7 +37,10 @@ KERNEL_UNITS = {"collect4096_f32": (["-DRM_KERNELS=4", "-DRM_F64=0"], ("rm_final
                                 ("rm_candmetrics.hpp", "rm_candidates.hpp", "rm_scores.hpp", "rm_rowtopk.hpp", "rm_prep.hpp", "rm_half.hpp", "rm_finalize.hpp")),
                 # (the gather of item-item models: independent columns, plain fma -- no SLP pairing into v_pk_fma_f32 either)
                 "itemweights": (["-DRM_KERNELS=9", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-                                ("rm_itemweights.hpp", "rm_prep.hpp", "rm_half.hpp", "rm_finalize.hpp"))}
+                                ("rm_itemweights.hpp", "rm_prep.hpp", "rm_half.hpp", "rm_finalize.hpp")),
+                # (the ordered scatter of a sparse W: one read-modify-write chain through LDS, nothing to pair)
+                "itemweights_csr": (["-DRM_KERNELS=10", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                                    ("rm_itemweights_csr.hpp", "rm_itemweights.hpp", "rm_prep.hpp", "rm_half.hpp", "rm_finalize.hpp"))}
 KERNEL_HEADERS = sorted({h for _, hdrs in KERNEL_UNITS.values() for h in hdrs} | {"rm_kernel_units.hpp"})
 # (the pool starts the units in this order: the longest compiles first)
 SOURCES = ([KERNEL_SRC + ":" + u for u in KERNEL_UNITS] + ["rm_lib.hip"] + [SWEEP_SRC + ":" + u for u in SWEEP_UNITS]

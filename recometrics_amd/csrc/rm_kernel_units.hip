@@ -1,4 +1,4 @@
-// rm_kernel_units.hip -- the kernels of rm_prep / rm_finalize / rm_noise / rm_scores / rm_rowtopk / rm_candidates / rm_candmetrics / rm_itemweights.hpp, compiled apart from the host
+// rm_kernel_units.hip -- the kernels of rm_prep / rm_finalize / rm_noise / rm_scores / rm_rowtopk / rm_candidates / rm_candmetrics / rm_itemweights / rm_itemweights_csr.hpp, compiled apart from the host
 // code that launches them (rm_lib.hip sees them `extern template`, or as declarations, and emits none: rm_kernel_units.hpp).
 //
 // This file is compiled once per translation unit with -DRM_KERNELS=k, units 3 and 4 once per precision with -DRM_F64=0 / 1
@@ -15,6 +15,7 @@
 //               7  rm_candidates.hpp: lists from candidate sets
 //               8  rm_candmetrics.hpp: metrics over candidate sets
 //               9  rm_itemweights.hpp: the scores of item-item models
+//              10  rm_itemweights_csr.hpp: ... with a sparse (CSR) weight matrix, and its check for repeated column ids
 #include <hip/hip_runtime.h>
 
 #if RM_KERNELS == 0
@@ -59,8 +60,12 @@
 #elif RM_KERNELS == 9
 #include "rm_itemweights.hpp"
 #define RM_UNIT_KERNELS(X) RM_ITEMWEIGHTS_KERNELS_F32(X) RM_ITEMWEIGHTS_KERNELS_F64(X)
+#elif RM_KERNELS == 10
+#define RM_ITEMWEIGHTS_CSR_PLAIN_KERNELS
+#include "rm_itemweights_csr.hpp"
+#define RM_UNIT_KERNELS(X) RM_ITEMWEIGHTS_CSR_KERNELS_F32(X) RM_ITEMWEIGHTS_CSR_KERNELS_F64(X)
 #else
-#error "RM_KERNELS: 0 .. 9"
+#error "RM_KERNELS: 0 .. 10"
 #endif
 
 namespace rm {

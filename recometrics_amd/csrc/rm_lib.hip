@@ -32,6 +32,7 @@
 #include "../../include/recometrics_hip_candidates.h"
 #include "../../include/recometrics_hip_candidate_metrics.h"
 #include "../../include/recometrics_hip_item_weights.h"
+#include "../../include/recometrics_hip_item_weights_csr.h"
 #include "rm_device.hpp"
 #include "rm_prep.hpp"
 #include "rm_launch.hpp"
@@ -42,6 +43,7 @@
 #include "rm_candidates.hpp"
 #include "rm_candmetrics.hpp"
 #include "rm_itemweights.hpp"
+#include "rm_itemweights_csr.hpp"
 
 namespace {
 
@@ -221,7 +223,12 @@ std::atomic<unsigned long long> g_ws_stamp{1};
     X(WS_IW_W, "iw_W")                          /* T[n_in][n rounded up to 16 bytes]: the host entry's copy of W (item_weights_host) */ \
     X(WS_IW_HP, "iw_hp")                        /* int[m + 1]: ... of the history's index pointers */ \
     X(WS_IW_HI, "iw_hi")                        /* int[nnz_hist]: ... its ids */ \
-    X(WS_IW_HV, "iw_hv")                        /* T[nnz_hist]: ... its values */
+    X(WS_IW_HV, "iw_hv")                        /* T[nnz_hist]: ... its values */ \
+    X(WS_IW_CSR_WP, "iw_csr_wp")                /* int[n_in + 1]: the host entry's copy of a sparse W's index pointers (item_weights_host) */ \
+    X(WS_IW_CSR_WI, "iw_csr_wi")                /* int[nnz_W]: ... its column ids */ \
+    X(WS_IW_CSR_WV, "iw_csr_wv")                /* T[nnz_W]: ... its values */ \
+    X(WS_IW_SORTED_WI, "iw_sorted_wi")          /* int[nnz_W]: the caller's unsorted rows of a sparse W, sorted by the host (item_weights_entry) */ \
+    X(WS_IW_SORTED_WV, "iw_sorted_wv")          /* T[nnz_W]: ... and their values */
 #define RM_WS_ID(id, name) id,
 #define RM_WS_NAME(id, name) name,
 enum WsBuf { RM_WS_BUFFERS(RM_WS_ID) WS_COUNT };
@@ -585,6 +592,9 @@ template <class T> struct Request : Outputs<T> {
     // (k_scores_item_weights, rm_itemweights.hpp) and runs a from-scores Call on each chunk; a Call never carries this source.
     const T *W = nullptr; size_t ldw = 0; int n_in = 0; bool item_weights = false;
     const int *hist_p = nullptr, *hist_i = nullptr; const T *hist_v = nullptr; long long nnz_hist = 0;
+    // ... with a SPARSE W (rm_*_item_weights_csr_*; `w_csr` is set together with `item_weights`, W and ldw stay unset): a CSR of n_in rows
+    // over n columns; k_scores_item_weights_csr (rm_itemweights_csr.hpp) writes the same chunk from the stored entries only
+    const int *W_p = nullptr, *W_i = nullptr; const T *W_v = nullptr; long long nnz_W = 0; bool w_csr = false;
     Outputs<T> &outputs() { return *this; }
 };
 // Which pass of a call this is (the tie noise, rm_noise.hpp, makes several of one call), and the three groups of fields that say so.
@@ -3029,17 +3039,24 @@ void check_request(const Request<T> &r, bool host)
     };
     if (r.item_weights) {                                            // item-item models, metrics or lists: the from-scores rules behind S = X_hist W
         if (r.m < 0 || r.n <= 0 || r.n_in <= 0) fail("m must not be negative, n and n_in must be positive");
-        if (!r.W || !r.hist_p) fail(null_in);
+        if (r.w_csr ? (!r.W_p || !r.W_v) : !r.W) fail(null_in);
+        if (!r.hist_p) fail(null_in);
         if (!r.reco && (!r.train_p || !r.test_p || (!r.test_i && nnz_test() > 0))) fail(null_in);
         if (r.reco && (!r.topk_idx || !r.status)) fail("null output pointer");
-        if (r.ldw < (size_t)r.n) fail("leading dimension of the weight matrix smaller than n (got " + std::to_string(r.ldw) + of_n);
+        if (!r.w_csr && r.ldw < (size_t)r.n) fail("leading dimension of the weight matrix smaller than n (got " + std::to_string(r.ldw) + of_n);
         K_in_1_n(r.reco ? "k_top" : "k_metrics");
         if (!r.reco) ndcg_has_values();
         if (host) {
             index_pointers();
             if (r.hist_p[r.m] > 0 && !r.hist_i) fail("null history indices");
+            if (r.w_csr) {                                           // (n_in rows, not m: index_pointers does not fit)
+                for (int j = 0; j < r.n_in; j++)
+                    if (r.W_p[j] < 0 || r.W_p[j + 1] < r.W_p[j]) fail("CSR index pointers of row " + std::to_string(j) + " are negative or decreasing (W)");
+                if (r.W_p[r.n_in] > 0 && !r.W_i) fail("null weight indices");
+            }
         }
-        else if (r.nnz_hist < 0 || r.nnz_train < 0 || r.nnz_test < 0) fail("negative length of an index array");
+        else if (r.nnz_hist < 0 || r.nnz_train < 0 || r.nnz_test < 0 || r.nnz_W < 0) fail("negative length of an index array");
+        else if (r.w_csr && r.nnz_W > 0 && !r.W_i) fail(null_in);
         else if ((r.nnz_hist > 0 && !r.hist_i) || (r.train_p && r.nnz_train > 0 && !r.train_i)) fail(null_in);
         return;
     }
@@ -3385,6 +3402,14 @@ Request<T> from_item_weights(const T *W, size_t ldw, int n_in, const int *hist_p
     r.W = W; r.ldw = ldw; r.n_in = n_in; r.hist_p = hist_p; r.hist_i = hist_i; r.hist_v = hist_v; r.nnz_hist = nnz_hist; r.item_weights = true;
     return r;
 }
+template <class T>
+Request<T> from_item_weights_csr(const int *W_p, const int *W_i, const T *W_v, long long nnz_W, int n_in,
+                                 const int *hist_p, const int *hist_i, const T *hist_v, long long nnz_hist)
+{
+    Request<T> r = from_item_weights<T>(nullptr, 0, n_in, hist_p, hist_i, hist_v, nnz_hist);
+    r.W_p = W_p; r.W_i = W_i; r.W_v = W_v; r.nnz_W = nnz_W; r.w_csr = true;
+    return r;
+}
 // Users per batch: the chunk (ws.get rounds an allocation up by an eighth) plus the masked row run() wants of every user inside a third
 // of what is then free -- b (1.125 + 3) rows <= free memory, taken as 5 rows as the from-scores host batches take 7 for 5.25;
 // RM_BATCH_USERS caps it.  The gather's grid (column tiles x blocks of four users) stays below 2^23 blocks.
@@ -3399,24 +3424,41 @@ template <class T> long long item_weight_batch_users(const Workspace &ws, int n)
 }
 // The history rows of all m users, validated as every CSR input is (rm_prep.hpp's checks, the column bound n_in), in a Plan of their
 // own -- the from-scores passes zero WS_PLAN batch by batch, and the gather kernel of every batch reads this verdict.
+// (`strict`, the rows of a sparse W: a column id twice in one row is a defect too -- k_check_csr_repeats, rm_itemweights_csr.hpp; it
+// looks at neighbours, so it is asked once the rows are known to ascend: unsorted rows go through the sorted copy first)
+inline void check_csr_rows(int rows, int cols, const int *p, const int *idx, long long nnz, const char *name, bool strict, Plan *plan, hipStream_t stream)
+{
+    const dim3 flat((unsigned)std::min<long long>((nnz / 4 + 2 + CHECK_FLAT_THREADS - 1) / CHECK_FLAT_THREADS, CHECK_FLAT_BLOCKS));
+    HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
+    hipLaunchKernelGGL(k_check_csr_ptr, dim3(cdiv(rows, 256)), dim3(256), 0, stream, rows, p, nnz, p, nnz, plan);
+    hipLaunchKernelGGL(k_check_csr_starts, dim3(cdiv(rows, 1024)), dim3(1024), 0, stream, rows, p, idx, (const int *)nullptr, (const int *)nullptr, plan);
+    if (nnz > 0) hipLaunchKernelGGL(k_check_csr_flat, flat, dim3(CHECK_FLAT_THREADS), 0, stream, rows, cols, p, idx, plan, 0);
+    HIP_CHECK(hipGetLastError());
+    const auto verdict = [&] {
+        Plan hp;
+        HIP_CHECK(hipMemcpyAsync(&hp, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        return hp;
+    };
+    Plan hp = verdict();
+    const std::string of = std::string(" (") + name + ")";
+    if (hp.csr_bad & CSR_BAD_INDPTR)
+        throw RmError{RM_ERR_INVALID, "CSR index pointers of row " + std::to_string(hp.csr_where) + " are negative, decreasing or beyond the index array" + of};
+    if (hp.csr_bad & CSR_BAD_INDEX)
+        throw RmError{RM_ERR_INVALID, "CSR column index out of range [0, " + std::to_string(cols) + ") in row " + std::to_string(hp.csr_where) + of};
+    if (hp.csr_desc_all[0] != hp.csr_desc_legit[0]) throw RmError{RM_INTERNAL_UNSORTED, "CSR rows are not sorted"};
+    if (!strict || nnz < 2) return;
+    hipLaunchKernelGGL(k_check_csr_repeats, dim3((unsigned)std::min<long long>((nnz + CHECK_FLAT_THREADS - 1) / CHECK_FLAT_THREADS, CHECK_FLAT_BLOCKS)),
+                       dim3(CHECK_FLAT_THREADS), 0, stream, rows, p, idx, plan);
+    HIP_CHECK(hipGetLastError());
+    hp = verdict();
+    if (hp.csr_bad & CSR_BAD_REPEAT)
+        throw RmError{RM_ERR_INVALID, "CSR column index repeated in row " + std::to_string(hp.csr_where) + of};
+}
 template <class T>
 void check_history(const Request<T> &r, Plan *plan, hipStream_t stream)
 {
-    HIP_CHECK(hipMemsetAsync(plan, 0, sizeof(Plan), stream));
-    hipLaunchKernelGGL(k_check_csr_ptr, dim3(cdiv(r.m, 256)), dim3(256), 0, stream, r.m, r.hist_p, r.nnz_hist, r.hist_p, r.nnz_hist, plan);
-    hipLaunchKernelGGL(k_check_csr_starts, dim3(cdiv(r.m, 1024)), dim3(1024), 0, stream, r.m, r.hist_p, r.hist_i, (const int *)nullptr, (const int *)nullptr, plan);
-    if (r.nnz_hist > 0)
-        hipLaunchKernelGGL(k_check_csr_flat, dim3((unsigned)std::min<long long>((r.nnz_hist / 4 + 2 + CHECK_FLAT_THREADS - 1) / CHECK_FLAT_THREADS, CHECK_FLAT_BLOCKS)),
-                           dim3(CHECK_FLAT_THREADS), 0, stream, r.m, r.n_in, r.hist_p, r.hist_i, plan, 0);
-    HIP_CHECK(hipGetLastError());
-    Plan hp;
-    HIP_CHECK(hipMemcpyAsync(&hp, plan, sizeof(Plan), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (hp.csr_bad & CSR_BAD_INDPTR)
-        throw RmError{RM_ERR_INVALID, "CSR index pointers of row " + std::to_string(hp.csr_where) + " are negative, decreasing or beyond the index array (X_hist)"};
-    if (hp.csr_bad & CSR_BAD_INDEX)
-        throw RmError{RM_ERR_INVALID, "CSR column index out of range [0, " + std::to_string(r.n_in) + ") in row " + std::to_string(hp.csr_where) + " (X_hist)"};
-    if (hp.csr_desc_all[0] != hp.csr_desc_legit[0]) throw RmError{RM_INTERNAL_UNSORTED, "CSR rows are not sorted"};
+    check_csr_rows(r.m, r.n_in, r.hist_p, r.hist_i, r.nnz_hist, "X_hist", false, plan, stream);
 }
 // One request with device pointers (the context's mutex is held): the history is validated once, the user range cut into batches, and
 // per batch the gather fills the chunk and the from-scores Call of that user range runs on (chunk, its stride).  A kept split and
@@ -3432,6 +3474,8 @@ void run_item_weights(const Request<T> &r, hipStream_t stream, Ctx &cx, bool hos
     if (!cx.iw_ev[0]) for (hipEvent_t &e : cx.iw_ev) HIP_CHECK(hipEventCreate(&e));
     Plan *plan = ws.array<Plan>(WS_IW_PLAN, 1);
     check_history<T>(r, plan, stream);
+    // (a sparse W, once per call and before the gather reads it; the plan then holds ITS verdict -- both are clean when a kernel asks)
+    if (r.w_csr) check_csr_rows(r.n_in, n, r.W_p, r.W_i, r.nnz_W, "W", true, plan, stream);
     const int *train_p = r.train_p, *train_i = r.train_i;
     if (r.reco && !train_p) {                                        // lists without an exclusion matrix: a row of zeros (run_dev)
         int *z = ws.array<int>(WS_RECO_ZERO_P, (size_t)m + 1);
@@ -3440,16 +3484,23 @@ void run_item_weights(const Request<T> &r, hipStream_t stream, Ctx &cx, bool hos
     }
     const size_t lds = ((size_t)n + G::VE - 1) / G::VE * G::VE;      // the chunk's row stride: whole 16-byte vectors
     const long long batch = item_weight_batch_users<T>(ws, n);
-    const bool vec = ((((size_t)r.W) | (r.ldw * sizeof(T))) & 15) == 0;
+    const bool vec = ((((size_t)r.W) | (r.ldw * sizeof(T))) & 15) == 0;         // (the dense kernel's instantiation)
     const MetricLayout lay(r.out, r.cumulative ? (size_t)r.K : 1);
     for (long long b0 = 0; b0 < m && !(host && g_interrupt); b0 += batch) {      // (the host form owns the flag: SignalGuard)
         const int mb = (int)std::min<long long>(batch, m - b0);
         T *S = ws.array<T>(WS_IW_SCORES, (size_t)mb * lds);
-        ItemWeightArgs<T> ka{r.W, r.ldw, n, mb, r.hist_p + b0, r.hist_i, r.hist_v, plan, S, lds, cdiv(mb, IW_THREADS / WAVE)};
-        const dim3 grid(cdiv(n, G::COLS) * ka.ublocks);              // the column tile slow, users fast
+        const unsigned ublocks = cdiv(mb, IW_THREADS / WAVE);
         HIP_CHECK(hipEventRecord(cx.iw_ev[0], stream));
-        if (vec) hipLaunchKernelGGL((k_scores_item_weights<T, true>), grid, dim3(IW_THREADS), 0, stream, ka);
-        else hipLaunchKernelGGL((k_scores_item_weights<T, false>), grid, dim3(IW_THREADS), 0, stream, ka);
+        if (r.w_csr) {                                               // the request's source picks the kernel; the grid order is the same
+            const unsigned tiles = cdiv(n, ItemWeightCsrTile<T>::COLS);
+            ItemWeightCsrArgs<T> ka{r.W_p, r.W_i, r.W_v, n, mb, r.hist_p + b0, r.hist_i, r.hist_v, plan, S, lds, ublocks, tiles};
+            hipLaunchKernelGGL((k_scores_item_weights_csr<T>), dim3(tiles * ublocks), dim3(IW_THREADS), 0, stream, ka);
+        } else {
+            ItemWeightArgs<T> ka{r.W, r.ldw, n, mb, r.hist_p + b0, r.hist_i, r.hist_v, plan, S, lds, ublocks};
+            const dim3 grid(cdiv(n, G::COLS) * ka.ublocks);          // the column tile slow, users fast
+            if (vec) hipLaunchKernelGGL((k_scores_item_weights<T, true>), grid, dim3(IW_THREADS), 0, stream, ka);
+            else hipLaunchKernelGGL((k_scores_item_weights<T, false>), grid, dim3(IW_THREADS), 0, stream, ka);
+        }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipEventRecord(cx.iw_ev[1], stream));
         cx.iw_timed = true;
@@ -3462,21 +3513,22 @@ void run_item_weights(const Request<T> &r, hipStream_t stream, Ctx &cx, bool hos
         run_call<T>(c, stream, cx);
     }
 }
-// The device form, with the sorted-copy fall-back of run_dev: when a row of the history, the train or the test matrix is unsorted, copies
-// of all three are sorted on the host (rm_csr_sort_rows carries the values) and the request runs again on the copies.
+// The device form, with the sorted-copy fall-back of run_dev: when a row of the history, the train or the test matrix -- or of a sparse
+// W -- is unsorted, copies of all of them are sorted on the host (rm_csr_sort_rows carries the values) and the request runs again on the copies.
 template <class T>
 void item_weights_entry(Request<T> r, hipStream_t stream, Ctx &cx, int nthreads, bool host)
 {
     try { run_item_weights<T>(r, stream, cx, host); return; }
     catch (const RmError &e) { if (e.code != RM_INTERNAL_UNSORTED) throw; }
-    const size_t m1 = (size_t)r.m + 1;
-    // (v == nullptr: rows without values -- the train matrix has none, and no value buffer: WS_COUNT names no buffer)
-    struct Rows { const int *p; const int **i; const T **v; long long nnz; WsBuf wi, wv; };
-    const Rows rows[3] = {{r.hist_p, &r.hist_i, &r.hist_v, r.nnz_hist, WS_IW_SORTED_HI, WS_IW_SORTED_HV},
-                          {r.train_p, &r.train_i, nullptr, r.nnz_train, WS_SORTED_TRI, WS_COUNT},
-                          {r.test_p, &r.test_i, &r.test_v, r.nnz_test, WS_SORTED_TEI, WS_SORTED_TEV}};
+    // (v == nullptr: rows without values -- the train matrix has none, and no value buffer: WS_COUNT names no buffer; a sparse W has
+    // n_in rows, everything else m)
+    struct Rows { const int *p; const int **i; const T **v; long long nnz; int count; WsBuf wi, wv; };
+    const Rows rows[4] = {{r.hist_p, &r.hist_i, &r.hist_v, r.nnz_hist, r.m, WS_IW_SORTED_HI, WS_IW_SORTED_HV},
+                          {r.train_p, &r.train_i, nullptr, r.nnz_train, r.m, WS_SORTED_TRI, WS_COUNT},
+                          {r.test_p, &r.test_i, &r.test_v, r.nnz_test, r.m, WS_SORTED_TEI, WS_SORTED_TEV},
+                          {r.W_p, &r.W_i, &r.W_v, r.nnz_W, r.n_in, WS_IW_SORTED_WI, WS_IW_SORTED_WV}};
     for (const Rows &x : rows) {
-        const size_t nnz = (size_t)std::max<long long>(x.nnz, 0);
+        const size_t nnz = (size_t)std::max<long long>(x.nnz, 0), m1 = (size_t)x.count + 1;
         if (!x.p || !nnz) continue;
         const T *values = x.v ? *x.v : nullptr;
         std::vector<int> p(m1), idx(nnz);
@@ -3485,7 +3537,7 @@ void item_weights_entry(Request<T> r, hipStream_t stream, Ctx &cx, int nthreads,
         HIP_CHECK(hipMemcpyAsync(idx.data(), *x.i, sizeof(int) * nnz, hipMemcpyDeviceToHost, stream));
         if (values) HIP_CHECK(hipMemcpyAsync(val.data(), values, sizeof(T) * nnz, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        if (rm_csr_sort_rows(p.data(), idx.data(), values ? (void *)val.data() : nullptr, values ? (int32_t)sizeof(T) : 0, r.m, nthreads) != RM_OK)
+        if (rm_csr_sort_rows(p.data(), idx.data(), values ? (void *)val.data() : nullptr, values ? (int32_t)sizeof(T) : 0, x.count, nthreads) != RM_OK)
             throw RmError{RM_ERR_NOMEM, "sorting a copy of the CSR rows failed"};
         int *di = cx.ws.array<int>(x.wi, nnz);
         HIP_CHECK(hipMemcpyAsync(di, idx.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, stream));
@@ -3533,9 +3585,16 @@ template <class T> void item_weights_host(Request<T> h, int nthreads)
             if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
             return dst;
         };
-        T *dW = ws.array<T>(WS_IW_W, (size_t)h.n_in * ldw);
-        HIP_CHECK(hipMemcpy2DAsync(dW, sizeof(T) * ldw, h.W, sizeof(T) * h.ldw, sizeof(T) * (size_t)h.n, (size_t)h.n_in, hipMemcpyHostToDevice, stream));
-        d.W = dW; d.ldw = ldw;
+        if (h.w_csr) {                                               // the three arrays of a sparse W, once
+            d.nnz_W = h.W_p[h.n_in];
+            d.W_p = (const int *)put(WS_IW_CSR_WP, h.W_p, sizeof(int) * ((size_t)h.n_in + 1));
+            d.W_i = (const int *)put(WS_IW_CSR_WI, h.W_i, sizeof(int) * (size_t)d.nnz_W);
+            d.W_v = (const T *)put(WS_IW_CSR_WV, h.W_v, sizeof(T) * (size_t)d.nnz_W);
+        } else {
+            T *dW = ws.array<T>(WS_IW_W, (size_t)h.n_in * ldw);
+            HIP_CHECK(hipMemcpy2DAsync(dW, sizeof(T) * ldw, h.W, sizeof(T) * h.ldw, sizeof(T) * (size_t)h.n, (size_t)h.n_in, hipMemcpyHostToDevice, stream));
+            d.W = dW; d.ldw = ldw;
+        }
         d.nnz_hist = h.hist_p[h.m];
         d.hist_p = (const int *)put(WS_IW_HP, h.hist_p, sizeof(int) * m1);
         d.hist_i = (const int *)put(WS_IW_HI, h.hist_i, sizeof(int) * (size_t)d.nnz_hist);
@@ -3855,6 +3914,77 @@ extern "C" int rm_recommend_item_weights_dev_##SUFFIX(                          
 
 RM_ITEM_WEIGHTS_ENTRY(f32, float)
 RM_ITEM_WEIGHTS_ENTRY(f64, double)
+
+// ... with a sparse W (include/recometrics_hip_item_weights_csr.h): `W, ldw` replaced by `W_p, W_i, W_v` (and `nnz_W` in the device form)
+#define RM_ITEM_WEIGHTS_CSR_ENTRY(SUFFIX, T)                                                                            \
+extern "C" int rm_calc_metrics_item_weights_csr_##SUFFIX(                                                               \
+    const int32_t *W_p, const int32_t *W_i, const T *W_v, int32_t n_in, int32_t m, int32_t n,                           \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v,                                                      \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i,                                                           \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr,                                         \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, int32_t nthreads)     \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_host<T>(metrics_request<T>(from_item_weights_csr<T>(W_p, W_i, W_v, 0, n_in, hist_p, hist_i,        \
+                                                                         hist_v, 0), m, n,                              \
+                                                Xtrain_csr_p, Xtrain_csr_i, 0, Xtest_csr_p, Xtest_csr_i, Xtest_csr, 0,  \
+                                                k_metrics, cumulative, 0,                                               \
+                                                {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k,       \
+                                                 rr_at_k, roc_auc, pr_auc},                                             \
+                                                consider_cold_start, min_items_pool, min_pos_test, 0),                  \
+                             nthreads > 0 ? nthreads : 0);                                                              \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_calc_metrics_item_weights_csr_dev_##SUFFIX(                                                           \
+    const int32_t *W_p, const int32_t *W_i, const T *W_v, int32_t n_in, int32_t m, int32_t n,                           \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v, int64_t nnz_hist, int64_t nnz_W,                     \
+    const int32_t *Xtrain_csr_p, const int32_t *Xtrain_csr_i, int64_t nnz_train,                                        \
+    const int32_t *Xtest_csr_p, const int32_t *Xtest_csr_i, const T *Xtest_csr, int64_t nnz_test,                       \
+    int32_t k_metrics, int cumulative,                                                                                  \
+    T *p_at_k, T *tp_at_k, T *r_at_k, T *ap_at_k, T *tap_at_k, T *ndcg_at_k, T *hit_at_k, T *rr_at_k,                   \
+    T *roc_auc, T *pr_auc, int consider_cold_start, int32_t min_items_pool, int32_t min_pos_test, void *stream)         \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_dev<T>(metrics_request<T>(from_item_weights_csr<T>(W_p, W_i, W_v, nnz_W, n_in, hist_p, hist_i,     \
+                                                                        hist_v, nnz_hist),                              \
+                                               m, n, Xtrain_csr_p, Xtrain_csr_i, nnz_train, Xtest_csr_p, Xtest_csr_i,   \
+                                               Xtest_csr, nnz_test, k_metrics, cumulative, 0,                           \
+                                               {p_at_k, tp_at_k, r_at_k, ap_at_k, tap_at_k, ndcg_at_k, hit_at_k,        \
+                                                rr_at_k, roc_auc, pr_auc},                                              \
+                                               consider_cold_start, min_items_pool, min_pos_test, 0), stream);          \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_item_weights_csr_##SUFFIX(                                                                  \
+    const int32_t *W_p, const int32_t *W_i, const T *W_v, int32_t n_in, int32_t m, int32_t n,                           \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v,                                                      \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int32_t k_top,                                              \
+    int32_t *idx, T *score, int32_t *status, int32_t nthreads)                                                          \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_host<T>(lists_request<T>(from_item_weights_csr<T>(W_p, W_i, W_v, 0, n_in, hist_p, hist_i, hist_v,  \
+                                                                       0), m, n,                                        \
+                                              Xexcl_csr_p, Xexcl_csr_i, 0, k_top, idx, score, status),                  \
+                             nthreads > 0 ? nthreads : 0);                                                              \
+    });                                                                                                                 \
+}                                                                                                                       \
+extern "C" int rm_recommend_item_weights_csr_dev_##SUFFIX(                                                              \
+    const int32_t *W_p, const int32_t *W_i, const T *W_v, int32_t n_in, int32_t m, int32_t n,                           \
+    const int32_t *hist_p, const int32_t *hist_i, const T *hist_v, int64_t nnz_hist, int64_t nnz_W,                     \
+    const int32_t *Xexcl_csr_p, const int32_t *Xexcl_csr_i, int64_t nnz_excl, int32_t k_top,                            \
+    int32_t *idx, T *score, int32_t *status, void *stream)                                                              \
+{                                                                                                                       \
+    return guarded([&] {                                                                                                \
+        item_weights_dev<T>(lists_request<T>(from_item_weights_csr<T>(W_p, W_i, W_v, nnz_W, n_in, hist_p, hist_i,       \
+                                                                      hist_v, nnz_hist),                                \
+                                             m, n, Xexcl_csr_p, Xexcl_csr_i, nnz_excl, k_top, idx, score, status),      \
+                            stream);                                                                                    \
+    });                                                                                                                 \
+}
+
+RM_ITEM_WEIGHTS_CSR_ENTRY(f32, float)
+RM_ITEM_WEIGHTS_CSR_ENTRY(f64, double)
 
 // ---- 16-bit score matrices (include/recometrics_hip_half.h): the four from-scores entries of fp32 with S in IEEE binary16 / bfloat16 ----
 #define RM_HALF_ENTRY(SUFFIX, TYPE)                                                                                     \
